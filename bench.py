@@ -7,12 +7,18 @@
 One "step" = one pass of the hot path (FFT -> carrier detect -> fit -> shift ->
 FFT -> x conj(T) -> IFFT -> SoA) over one batch of synthetic IQ blocks that are
 already resident in HBM.  A step's batch is R launch batches of B blocks (B = the
-engine's max_batch, 32768 at N = 16384); R is chosen after a calibration burst so
-that the K timed steps last at least --min-seconds (default 2 s: a sustained rate
-on a part that clocks to its power budget, not a 40 ms burst).  The default run
-then adds bounded legs for the other single-GPU configs (`configs`: c3, t4, sparse,
-fullwin, c3t4, c1, c1_sparse), each with its own recomputable roofline figures, the CPU
-baseline, and the file legs (.card / raw file -> .toad).  Workloads (BASELINE.json `configs`):
+engine's max_batch, 32768 at N = 16384).  By default R covers every resident block
+once (c2: 32 x 32768 = 1 Mi blocks per step), so a step is the same work in every run
+and K steps are K times that work.  --min-seconds S instead picks R after a
+calibration burst so that the K timed steps last at least S (0: R = 1).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds
+the rest: HIP events around the kernels of every --profile-kernels-th launch batch
+(the `roofline` object), the first-1-Mi and one-handle rates, bounded legs for the
+other single-GPU configs (`configs`: c3, t4, sparse, fullwin, c3t4, c1, c1_sparse),
+each with its own recomputable roofline figures, the CPU baseline, and the file legs
+(.card / raw file -> .toad).  --dump-outputs DIR writes the records of the last timed
+step as DIR/<field>.npy.  Workloads (BASELINE.json `configs`):
 
   --config c2 (default, the headline): configs[1] -- block_len 16384, history 4096,
       1023-chip Gold template, K*B (default 32 * 32768 = 1 Mi) blocks per GPU
@@ -111,18 +117,24 @@ def parse_args():
                     help="engine handles (each with its own HIP stream) the steps alternate over "
                          "(default per config)")
     ap.add_argument("--profile-kernels", type=int, default=16,
-                    help="n > 0: HIP events around the kernels of every n-th step of the timed "
-                         "region (roofline leg; 1 = every step, costs ~4%%); 0 = off")
+                    help="with --full, n > 0: HIP events around the kernels of every n-th step of the "
+                         "timed region (roofline leg; 1 = every step, costs ~4%%); 0 = off")
     ap.add_argument("--variant", choices=["default", "preshift"], default="default",
                     help="default: reference Detector (the headline); preshift: the reference's "
                          "experimental PreshiftDetector (one fused kernel per block)")
     ap.add_argument("--preshift-num", type=int, default=21, help="bank size of --variant preshift")
-    ap.add_argument("--min-seconds", type=float, default=2.0,
+    ap.add_argument("--min-seconds", type=float, default=None,
                     help="lower bound on the timed region: a step becomes R launch batches of --batch "
-                         "blocks, R from a calibration burst, so that K steps last this long (0: R = 1)")
+                         "blocks, R from a calibration burst, so that K steps last this long (0: R = 1); "
+                         "default: a step is one pass over the resident blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: kernel events (roofline), the "
+                         "first-1-Mi and one-handle rates, the extra legs, the CPU baseline, the file legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step (rank 0) as DIR/<field>.npy")
     ap.add_argument("--legs", default="auto",
-                    help="comma list of extra single-GPU legs after the main one (%s); 'auto' = all of "
-                         "them on the default c2 / 1 GPU run, none otherwise; 'none'" % ",".join(LEGS))
+                    help="with --full, comma list of extra single-GPU legs after the main one (%s); 'auto' = "
+                         "all of them on the default c2 / 1 GPU run, none otherwise; 'none'" % ",".join(LEGS))
     ap.add_argument("--leg-seconds", type=float, default=0.75, help="timed region of each extra leg")
     ap.add_argument("--cpu-procs", type=int, default=-1,
                     help="worker processes of the all-cores CPU leg (-1: one per physical core, "
@@ -140,7 +152,10 @@ def parse_args():
                          "configs[3]: 1 Mi blocks in total -- split over the N ranks")
     ap.add_argument("--resident-blocks", type=int, default=0,
                     help="distinct blocks resident in HBM per rank (default per config: c2 1 Mi = 32 GiB)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def synth_on_device(torch, dev, gen, n_blocks, n, template, window, signal_frac, chunk=0, truth=None):
@@ -806,6 +821,29 @@ def write_detail(detail, tag):
     print("bench detail: " + text, file=sys.stderr)
 
 
+DUMP_RECORDS = 1 << 19      # --dump-outputs: at most this many records (72 B each as float arrays)
+
+
+def dump_outputs(leg, K, R, n_detections, out_dir):
+    """--dump-outputs: the records the last timed step wrote (this rank's), one array per field of
+    thrifty_amd._native.RECORD_DTYPE as DIR/<field>.npy (integers as float64, floats as they are; a
+    fixed seeded sample of DUMP_RECORDS of them where the step wrote more), and the number of
+    detections the compaction kept as DIR/n_detections.npy."""
+    torch = leg.torch
+    starts = sorted({(g % leg.resident_batches) * leg.B for g in range((K - 1) * R, K * R)})
+    rows = np.concatenate([np.arange(s * leg.T, (s + leg.B) * leg.T) for s in starts])
+    if len(rows) > DUMP_RECORDS:
+        rows = np.sort(np.random.default_rng(SEED).choice(rows, DUMP_RECORDS, replace=False))
+    sel = torch.as_tensor(rows, dtype=torch.int64, device=leg.dev)
+    recs = leg.rec.view(-1, 64).index_select(0, sel).cpu().numpy().view(leg.F.RECORD_DTYPE).reshape(-1)
+    os.makedirs(out_dir, exist_ok=True)
+    for name in recs.dtype.names:
+        if name != "reserved":
+            a = recs[name]
+            np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
+    np.save(os.path.join(out_dir, "n_detections.npy"), np.array([n_detections], dtype=np.float64))
+
+
 def main():
     args = parse_args()
     # the rank environment FIRST, before torch / the HIP runtime initialise: the same on every launch
@@ -861,9 +899,11 @@ def main():
     # distinct blocks resident in HBM: up to the config's limit (c2: 1 Mi blocks = 32 GiB of u8 =
     # BASELINE's "1M synthetic blocks"); longer runs cycle through them.  --scaling strong: the
     # config's blocks IN TOTAL (configs[3] as written: 1 Mi blocks sharded 8 ways), 1/world per rank
-    resident = min(cfg["resident"], max(B, K * B)) if args.min_seconds <= 0 else cfg["resident"]
+    resident = (min(cfg["resident"], max(B, K * B)) if args.min_seconds is not None and args.min_seconds <= 0
+                else cfg["resident"])
     if args.resident_blocks > 0:
         resident = max(B, args.resident_blocks)
+    one_gpu_pass = max(1, resident // B)      # launch batches of one pass over ONE GPU's resident blocks
     if strong:
         resident = max(B, resident // world)
     leg = Leg(torch, F, synth, dev, local, args.config, T=T, mix=args.mix, batch=B, resident=resident,
@@ -890,15 +930,23 @@ def main():
     kept = torch.zeros_like(leg.rec)
     torch.cuda.synchronize()
 
-    # ---- calibration burst = the round-1/2 protocol: 1 Mi blocks (32 launch batches) straight after
-    # a two-batch code-load warm-up -- reported as `value_first_1Mi`, and it sizes a step
+    # two-batch code-load warm-up
     leg.timed(0, 2)
-    # (--min-seconds 0 -- profiler passes, quick A/B runs: no burst, a step is one launch batch)
-    burst_batches = max(2, min(leg.resident_batches, (1 << 20) // B)) if args.min_seconds > 0 else 2
-    burst_dt, _ = leg.timed(0, burst_batches)
-    burst_rate = burst_batches * B / burst_dt
-    R = 1
-    if args.min_seconds > 0:
+    # ---- the step: by default one pass over the resident blocks (the same work whatever K is, and
+    # the same blocks in every run: --dump-outputs compares builds).  --min-seconds S: a calibration
+    # burst sizes it instead (--min-seconds 0 -- profiler passes, quick A/B runs: a step is one launch
+    # batch).  The burst is the round-1/2 protocol, 1 Mi blocks (32 launch batches) straight after the
+    # code load, reported as `value_first_1Mi` by --full
+    min_s = 2.0 if args.min_seconds is None else args.min_seconds     # (--full's extra rates)
+    burst_batches = burst_dt = burst_rate = None
+    if args.full or (args.min_seconds or 0) > 0:
+        burst_batches = max(2, min(leg.resident_batches, (1 << 20) // B)) if min_s > 0 else 2
+        burst_dt, _ = leg.timed(0, burst_batches)
+        burst_rate = burst_batches * B / burst_dt
+    R = one_gpu_pass
+    if args.min_seconds is not None and args.min_seconds <= 0:
+        R = 1
+    elif args.min_seconds is not None:
         R = int(max(1, np.ceil(args.min_seconds * burst_rate / (K * B))))
     if use_dist:    # every rank must run the same step size: take rank 0's
         r_t = torch.tensor([R], dtype=torch.int64, device=cdev)
@@ -906,7 +954,7 @@ def main():
         R = int(r_t.item())
     R_one_gpu = R
     if strong:
-        # the job is what ONE GPU would run for --min-seconds (K x R launch batches); N ranks split it
+        # the job is what ONE GPU would run (K x R launch batches); N ranks split it
         R = max(1, -(-R // world))
     for i in range(W):
         leg.run(i * R, R)
@@ -919,18 +967,19 @@ def main():
     # over the engine handles (double buffering: the latency-bound k_fit and the launch gaps of
     # one batch hide under the other batch's kernels); with more than one handle every
     # `profile_kernels`-th launch batch runs SOLO with HIP events around its kernels (costs that
-    # batch's overlap; inside the timed region).
-    solo_every = args.profile_kernels if len(engs) > 1 else 0
+    # batch's overlap; inside the timed region) -- with --full only: a plain run times the path alone.
+    profile_kernels = args.profile_kernels if args.full else 0
+    solo_every = profile_kernels if len(engs) > 1 else 0
     leg.reset_profile()
-    if len(engs) == 1 and args.profile_kernels > 0:
-        eng.profile_enable(args.profile_kernels)
+    if len(engs) == 1 and profile_kernels > 0:
+        eng.profile_enable(profile_kernels)
     profiled = 0
     t0 = time.perf_counter()
     for i in range(K):
         profiled += leg.run(i * R, R, solo_every)
     leg.sync()
-    if len(engs) == 1 and args.profile_kernels > 0:
-        profiled = (K * R + args.profile_kernels - 1) // args.profile_kernels
+    if len(engs) == 1 and profile_kernels > 0:
+        profiled = (K * R + profile_kernels - 1) // profile_kernels
     t_compute = time.perf_counter()
     # K7 + C1: compact detected records, gather them to rank 0 (the only collective)
     n_kept = eng.compact_device(leg.rec.data_ptr(), total * T, kept.data_ptr())     # (synchronises)
@@ -943,7 +992,6 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    prof = leg.read_profile()
     # (after the clock stopped, reporting only) every rank's own times: a sub-linear curve can be
     # attributed to a slow rank's kernels, the compaction or the gather
     mine = {"n_kept": int(n_kept), "compute_s": t_compute - t0, "compact_ms": (t_compact - t_compute) * 1e3,
@@ -956,10 +1004,12 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     per_rank = [r["n_kept"] for r in ranks]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(leg, K, R, int(gathered.shape[0]), args.dump_outputs)
     # ---- one handle alone (what the roofline's solo kernel times belong to), a short leg
     one_dt, one_n = None, 0
-    if len(engs) > 1 and args.min_seconds > 0:
-        one_n = int(max(8, min(K * R, 0.25 * args.min_seconds * burst_rate / B)))
+    if args.full and len(engs) > 1 and min_s > 0:
+        one_n = int(max(8, min(K * R, 0.25 * min_s * burst_rate / B)))
         one_dt, _ = leg.timed(0, one_n, 0, engs[:1])
 
     if rank == 0:
@@ -967,7 +1017,6 @@ def main():
         value = blocks_total / dt
         metric = ("IQ blocks/sec (16384-sample, 1024-chip template)" if n == 16384 and args.config == "c2"
                   else "IQ blocks/sec (%d-sample, %d-sample template)" % (n, leg.wlen))
-        roof, rdetail = leg.roofline(prof, profiled, dt / (K * R) * 1e3, value / world)
         line = {
             "metric": metric,
             "value": value, "unit": "blocks/s", "n_gpus": world, "steps": K, "warmup": W,
@@ -977,7 +1026,7 @@ def main():
                        "name": args.config,
                        "variant": args.variant if not pnum else "preshift(num=%d)" % pnum,
                        "blocks_per_step_per_gpu": R * B, "launch_batches_per_step": R,
-                       # (the calibrated step of ONE GPU's job; --scaling strong splits it over the ranks)
+                       # (the step of ONE GPU's job; --scaling strong splits it over the ranks)
                        "launch_batches_per_step_one_gpu": R_one_gpu,
                        "blocks_per_launch_batch": B, "templates": T,
                        "carrier_window": list(leg.cwin), "thresholds": "15*snr",
@@ -997,73 +1046,76 @@ def main():
             "compact_ms": ranks[0]["compact_ms"], "gather_ms": ranks[0]["gather_ms"],
             # the sustained-rate protocol (wall clock over >= 1 M blocks after warm-up)
             "timed_region_s": dt, "blocks_timed": blocks_total,
-            "value_first_1Mi": burst_rate if args.min_seconds > 0 else None,
-            "value_1stream": (one_n * B / one_dt) if one_dt else None,
-            "roofline": roof,
         }
-        detail = {"main": {"workload": leg.workload_text(), "roofline_detail": rdetail, "data_gen_s": leg.t_gen,
-                           "first_1Mi": {"blocks": burst_batches * B, "seconds": burst_dt,
-                                         "note": "rank 0's first %d launch batches after a two-batch code-load "
-                                                 "warm-up (the round-1/2 protocol), no gather" % burst_batches},
-                           "one_stream": ({"blocks": one_n * B, "seconds": one_dt,
-                                           "note": "one engine handle alone on rank 0, straight after the "
-                                                   "timed region"} if one_dt else None),
-                           "ranks": ranks},
-                  "configs": {}}
-        legs = []
-        if args.legs == "auto":
-            legs = (list(LEGS) if (world == 1 and args.config == "c2" and T == 1 and not pnum
-                                   and args.mix == "dense") else [])
-        elif args.legs != "none":
-            legs = [x for x in args.legs.split(",") if x]
-        host_blocks = gpu_rec = None
-        if world == 1 and args.cpu_seconds > 0:
-            ns = min(total, 16384 if n == 16384 else 2048)
-            host_blocks = leg.data[:ns].cpu().numpy()
-            gpu_rec = leg.host_records(ns)
         summary = {args.config + ("_t%d" % T if T > 1 else "") + ("_sparse" if args.mix != "dense" else ""): value}
-        if legs:
-            leg.close()      # the main leg's 32 GiB go before the other configs' data arrive
-            torch.cuda.empty_cache()
-            line["configs"] = {}
-            for key in legs:
-                line["configs"][key], detail["configs"][key] = extra_leg(
-                    torch, F, synth, dev, local, key, args.leg_seconds, cpu_ok=args.cpu_seconds > 0)
-                summary[key] = line["configs"][key]["value"]
+        if args.full:
+            prof = leg.read_profile()
+            roof, rdetail = leg.roofline(prof, profiled, dt / (K * R) * 1e3, value / world)
+            line.update({"value_first_1Mi": burst_rate if min_s > 0 else None,
+                         "value_1stream": (one_n * B / one_dt) if one_dt else None,
+                         "roofline": roof})
+            detail = {"main": {"workload": leg.workload_text(), "roofline_detail": rdetail, "data_gen_s": leg.t_gen,
+                               "first_1Mi": {"blocks": burst_batches * B, "seconds": burst_dt,
+                                             "note": "rank 0's first %d launch batches after a two-batch code-load "
+                                                     "warm-up (the round-1/2 protocol), no gather" % burst_batches},
+                               "one_stream": ({"blocks": one_n * B, "seconds": one_dt,
+                                               "note": "one engine handle alone on rank 0, straight after the "
+                                                       "timed region"} if one_dt else None),
+                               "ranks": ranks},
+                      "configs": {}}
+            legs = []
+            if args.legs == "auto":
+                legs = (list(LEGS) if (world == 1 and args.config == "c2" and T == 1 and not pnum
+                                       and args.mix == "dense") else [])
+            elif args.legs != "none":
+                legs = [x for x in args.legs.split(",") if x]
+            host_blocks = gpu_rec = None
+            if world == 1 and args.cpu_seconds > 0:
+                ns = min(total, 16384 if n == 16384 else 2048)
+                host_blocks = leg.data[:ns].cpu().numpy()
+                gpu_rec = leg.host_records(ns)
+            if legs:
+                leg.close()      # the main leg's 32 GiB go before the other configs' data arrive
                 torch.cuda.empty_cache()
-        if host_blocks is not None:
-            cb = cpu_baseline(n, h, host_blocks, np.arange(first, first + len(host_blocks)),
-                              leg.tpls[0], args.cpu_seconds, gpu_rec, pnum, leg.cwin)
-            line["cpu_baseline"] = cb
-            procs, how = physical_cores()
-            if args.cpu_procs >= 0:
-                procs, how = args.cpu_procs, "--cpu-procs"
-            if procs > 0 and not pnum:
-                ac = cpu_all_cores(n, h, host_blocks, leg.tpls[0], procs, cb["value"], window=leg.cwin)
-                ac["procs_from"] = how
-                detail["cpu_all_cores"] = ac
-                # (flat: the driver's record keeps the scalars of this object)
-                cb["all_cores_value"], cb["all_cores_procs"] = ac["value"], ac["procs"]
-            if args.card_blocks > 0 and args.config == "c2" and T == 1 and not pnum:
-                if leg.engs:     # free the benchmark's engines before the plumbing legs create their own
-                    leg.close()
-                ct = card_to_toad_leg(args.card_blocks)
-                detail["card_to_toad"] = ct
-                for k in ("cpu_blocks_per_s", "gpu_blocks_per_s", "gpu_blocks", "gpu_loop_blocks_per_s",
-                          "raw_gpu_blocks_per_s", "outputs_agree", "iter_blocks_per_s", "raw_iter_blocks_per_s",
-                          "iter_serialize_blocks_per_s", "iter_text_equals_write_toad"):
-                    if k in ct:
-                        cb["card_to_toad_" + k] = ct[k]
-                summary["card_to_toad"] = ct["gpu_blocks_per_s"]
-                if "raw_gpu_blocks_per_s" in ct:
-                    summary["raw_to_toad"] = ct["raw_gpu_blocks_per_s"]
-                # the reference's own `for detected, result in Detector(...)` loop over the same files
-                summary["detector_iter"] = ct["iter_blocks_per_s"]
-                summary["detector_iter_raw"] = ct["raw_iter_blocks_per_s"]
+                line["configs"] = {}
+                for key in legs:
+                    line["configs"][key], detail["configs"][key] = extra_leg(
+                        torch, F, synth, dev, local, key, args.leg_seconds, cpu_ok=args.cpu_seconds > 0)
+                    summary[key] = line["configs"][key]["value"]
+                    torch.cuda.empty_cache()
+            if host_blocks is not None:
+                cb = cpu_baseline(n, h, host_blocks, np.arange(first, first + len(host_blocks)),
+                                  leg.tpls[0], args.cpu_seconds, gpu_rec, pnum, leg.cwin)
+                line["cpu_baseline"] = cb
+                procs, how = physical_cores()
+                if args.cpu_procs >= 0:
+                    procs, how = args.cpu_procs, "--cpu-procs"
+                if procs > 0 and not pnum:
+                    ac = cpu_all_cores(n, h, host_blocks, leg.tpls[0], procs, cb["value"], window=leg.cwin)
+                    ac["procs_from"] = how
+                    detail["cpu_all_cores"] = ac
+                    # (flat: the driver's record keeps the scalars of this object)
+                    cb["all_cores_value"], cb["all_cores_procs"] = ac["value"], ac["procs"]
+                if args.card_blocks > 0 and args.config == "c2" and T == 1 and not pnum:
+                    if leg.engs:     # free the benchmark's engines before the plumbing legs create their own
+                        leg.close()
+                    ct = card_to_toad_leg(args.card_blocks)
+                    detail["card_to_toad"] = ct
+                    for k in ("cpu_blocks_per_s", "gpu_blocks_per_s", "gpu_blocks", "gpu_loop_blocks_per_s",
+                              "raw_gpu_blocks_per_s", "outputs_agree", "iter_blocks_per_s", "raw_iter_blocks_per_s",
+                              "iter_serialize_blocks_per_s", "iter_text_equals_write_toad"):
+                        if k in ct:
+                            cb["card_to_toad_" + k] = ct[k]
+                    summary["card_to_toad"] = ct["gpu_blocks_per_s"]
+                    if "raw_gpu_blocks_per_s" in ct:
+                        summary["raw_to_toad"] = ct["raw_gpu_blocks_per_s"]
+                    # the reference's own `for detected, result in Detector(...)` loop over the same files
+                    summary["detector_iter"] = ct["iter_blocks_per_s"]
+                    summary["detector_iter_raw"] = ct["raw_iter_blocks_per_s"]
+            write_detail(detail, "%s_n%d" % (args.config, world))
         # flat, last: the one place where every leg's blocks/s stands side by side (the driver keeps
         # the tail of stdout)
         line["summary"] = {k: round(v) for k, v in summary.items()}
-        write_detail(detail, "%s_n%d" % (args.config, world))
         print(json.dumps(line))
     if use_dist:
         dist.destroy_process_group()

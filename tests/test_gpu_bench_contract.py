@@ -1,5 +1,6 @@
-"""bench.py's output contract, on a shortened run: ONE JSON line on stdout carrying the driver's
-keys, a recomputable `roofline`, `cpu_baseline`, and the legs of the other single-GPU configs."""
+"""bench.py's output contract, on shortened runs: ONE JSON line on stdout carrying the driver's
+keys; with --full a recomputable `roofline`, `cpu_baseline`, and the legs of the other single-GPU
+configs; --dump-outputs writes the last timed step's records."""
 import json
 import os
 import sys
@@ -30,7 +31,7 @@ def test_default_run_line_has_every_contract_key():
     detail_path = os.path.join(ROOT, "gpurun_out", "bench_detail_c2_n1.json")
     if os.path.exists(detail_path):
         os.remove(detail_path)
-    res = bounded_run.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+    res = bounded_run.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
                            "--min-seconds", "0.2", "--leg-seconds", "0.1", "--cpu-seconds", "0.5",
                            "--cpu-procs", "2", "--card-blocks", "256"], cwd=ROOT, timeout=600, label="bench_default")
     assert res.returncode == 0, res.stderr[-3000:]
@@ -91,6 +92,34 @@ def test_default_run_line_has_every_contract_key():
     assert "every bin" in det["configs"]["fullwin"]["workload"]
     assert det["main"]["roofline_detail"]["compute"]["peak_tflops"] > 100
     assert det["card_to_toad"]["gpu_loop_stats"]["batches"] >= 1
+
+
+def test_plain_run_times_k_steps_of_one_pass_and_dumps_the_last_steps_records(tmp_path):
+    """Without --full: the headline alone.  A step is one pass over the resident blocks, whatever K is;
+    --dump-outputs writes the records of the last step, one float array per field."""
+    import numpy as np
+    out = tmp_path / "dump"
+    res = bounded_run.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+                           "--resident-blocks", "65536", "--dump-outputs", str(out)], cwd=ROOT, timeout=300,
+                          label="bench_plain")
+    d = _one_line(res)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "summary"):
+        assert key in d, key
+    for key in ("roofline", "configs", "cpu_baseline", "value_first_1Mi", "value_1stream"):
+        assert key not in d, key
+    c = d["config"]
+    assert d["steps"] == 3 and d["warmup"] == 1
+    assert c["launch_batches_per_step"] == 2 and c["blocks_per_step_per_gpu"] == 65536
+    assert d["blocks_timed"] == 3 * 65536
+    assert abs(d["value"] - d["blocks_timed"] / (d["ms_per_step"] * 1e-3 * d["steps"])) <= 1e-6 * d["value"]
+    files = sorted(os.listdir(out))
+    assert "block_idx.npy" in files and "corr_energy.npy" in files and "n_detections.npy" in files
+    assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+    arrays = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert np.array_equal(np.sort(arrays["block_idx"]), np.arange(65536))
+    assert all(len(a) == 65536 for k, a in arrays.items() if k != "n_detections")
+    assert arrays["n_detections"][0] == c["detections_gathered"]
 
 
 def _one_line(res):

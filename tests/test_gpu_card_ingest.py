@@ -147,20 +147,14 @@ def test_input_window_on_a_file_larger_than_the_lock_ahead_distance(golden, tmp_
 def test_device_ingest_equals_the_reference_native_card_reader(golden, tmp_path):
     """The whole `.card` front end of the engine -- thr_frame_card framing, base64 decode on the
     device -- against the reference's own native reader (fastcard/card_reader.c + lib/base64.c,
-    oracle/_ref): detection records from the text == records from the bytes the reference
-    decoded, byte for byte."""
-    from oracle import ref_readers
-    if not ref_readers.available():
-        # absent only where it cannot be built; required wherever the checkout is, or the caller says so
-        from test_ref_readers import ref_required
-        assert not ref_required(), \
-            "oracle/_ref/libfastcard_readers.so is missing: run __graft_entry__.build() / make -C oracle"
-        pytest.skip("oracle/_ref/libfastcard_readers.so not built (needs the reference checkout)")
+    oracle/_ref, or what it returned for this file where it cannot be built: test_ref_readers.ref_read):
+    detection records from the text == records from the bytes the reference decoded, byte for byte."""
+    from test_ref_readers import ref_read
     g = golden("c2")
     n = int(g["block_len"])
     path = tmp_path / "rx.card"
     path.write_text("# capture\n" + card_text(g))
-    ref, rc = ref_readers.read_blocks(str(path), n, int(g["history_len"]), card=True)
+    ref, rc = ref_read("ingest_c2", path, n, int(g["history_len"]), card=True)
     assert rc == 1 and len(ref) == len(g["blocks"])
     ref_bytes = np.stack([r[3] for r in ref])
     assert np.array_equal(ref_bytes, g["blocks"])

@@ -339,6 +339,7 @@ def test_every_fixture_holds_exactly_the_keys_its_generator_writes():
     ide = _declared("make_golden_identify.py", ["KEYS", "KEYS_AUTO", "KEYS_MAP"])
     itp = _declared("make_golden_interpol.py", ["KEYS"])
     xco = _declared("make_golden_xcorr.py", ["KEYS", "CASES"])
+    rrd = _declared("make_golden_ref_readers.py", ["CASES", "FIELDS"])
     assert sorted(os.path.basename(p) for p in glob.glob(os.path.join(GOLDEN_DIR, "xcorr_*.npz"))) == sorted(
         "xcorr_%s_%s.npz" % tuple(c) for c in xco["CASES"])
     seen = 0
@@ -352,6 +353,8 @@ def test_every_fixture_holds_exactly_the_keys_its_generator_writes():
             want = itp["KEYS"]
         elif name.startswith("xcorr_"):
             want = xco["KEYS"]
+        elif name == "ref_readers":
+            want = ["%s__%s" % (c, f) for c in rrd["CASES"] for f in rrd["FIELDS"]]
         elif name.startswith("identify_"):
             want = ide["KEYS"] + (ide["KEYS_MAP"] if name == "identify_map" else ide["KEYS_AUTO"])
         else:
