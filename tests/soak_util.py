@@ -11,54 +11,91 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
+class FitUnconverged(tuple):
+    """Oracle row of a block on which the reference's carrier fit dies: SciPy's curve_fit raises
+    RuntimeError("Optimal parameters not found") and carrier_sync.py:189 does not catch it.  Row-shaped
+    (the oracle's carrier bin and verdict, the rest zero) so that callers indexing rows keep working;
+    compare() counts it as a carrier mismatch unless the record carries THR_FLAG_FIT_UNCONVERGED."""
+
+
 def oracle_rows(args):
-    """(worker) -> (lo, [(cbin, cdet, coff, cenergy, sample, det, energy, offset, noise), ...])"""
+    """(worker) -> (lo, [(cbin, cdet, coff, cenergy, sample, det, energy, offset, noise, cnoise), ...]).
+    args: (lo, blocks, n, h, tpl, cthr, cwin, xthr[, carrier_len[, preshift_num]]); carrier_len None:
+    the template's length; preshift_num > 0: OraclePreshiftDetector with that many templates."""
     os.environ["OMP_NUM_THREADS"] = "1"
-    lo, blocks, n, h, tpl, cthr, cwin, xthr = args
+    lo, blocks, n, h, tpl, cthr, cwin, xthr = args[:8]
+    carrier_len = args[8] if len(args) > 8 else None
+    preshift_num = args[9] if len(args) > 9 else 0
     from oracle import thrifty_np as onp
-    orc = onp.OracleDetector(n, h, tpl, cthr, cwin, xthr)
+    if preshift_num:
+        orc = onp.OraclePreshiftDetector(n, h, tpl, cthr, cwin, xthr, num=preshift_num)
+    else:
+        orc = onp.OracleDetector(n, h, tpl, cthr, cwin, xthr, carrier_len=carrier_len)
     out = []
     for i in range(len(blocks)):
         try:
-            (r,) = orc.detect_u8(lo + i, blocks[i])
+            r = orc.detect_u8(lo + i, blocks[i])
+            if not preshift_num:
+                (r,) = r
         except IndexError:      # the reference raises when peak_idx + 3 >= N (carrier_sync.py:187)
             out.append(None)
+            continue
+        except RuntimeError:    # curve_fit gave up (carrier_sync.py:189)
+            mag = np.abs(np.fft.fft(onp.iq_u8_to_c64(blocks[i])))
+            det, idx, peak, noise, _ = onp.carrier_detect(mag, cthr, cwin)
+            out.append(FitUnconverged((idx, bool(det), 0.0, float(peak), -1, False, 0.0, 0.0, 0.0, float(noise))))
             continue
         c = r.corr
         out.append((r.carrier.bin, bool(r.carrier.detected), float(r.carrier.offset), float(r.carrier.energy),
                     int(c.sample) if c else -1, bool(c.detected) if c else False,
                     float(c.energy) if c else 0.0, float(c.offset) if c else 0.0,
-                    float(c.noise) if c else 0.0))
+                    float(c.noise) if c else 0.0, float(r.carrier.noise)))
     return lo, out
 
 
-def run_oracle(blocks, n, h, tpl, cthr, cwin, xthr, procs=None, chunk=64):
+def run_oracle(blocks, n, h, tpl, cthr, cwin, xthr, procs=None, chunk=64, carrier_len=None, preshift_num=0):
+    return run_oracle_many([(blocks, n, h, tpl, cthr, cwin, xthr, carrier_len, preshift_num)],
+                           procs=procs, chunk=chunk)[0]
+
+
+def run_oracle_many(configs, procs=None, chunk=64):
+    """Several oracle runs in one pool of workers: configs = [(blocks, n, h, tpl, cthr, cwin, xthr,
+    carrier_len, preshift_num), ...] -> [rows of each config]."""
     procs = procs or max(1, min(32, (os.cpu_count() or 2) // 2))
-    jobs = [(s, blocks[s:s + chunk], n, h, tpl, cthr, cwin, xthr) for s in range(0, len(blocks), chunk)]
-    rows = [None] * len(blocks)
+    jobs, where = [], []
+    for c, (blocks, *rest) in enumerate(configs):
+        for s in range(0, len(blocks), chunk):
+            jobs.append((s, blocks[s:s + chunk], *rest))
+            where.append(c)
+    out_rows = [[None] * len(c[0]) for c in configs]
     # (an executor, not mp.Pool: a worker that dies raises BrokenProcessPool instead of being
     # respawned forever, and every result has a deadline)
     from concurrent.futures import ProcessPoolExecutor
     with ProcessPoolExecutor(min(procs, len(jobs)), mp_context=mp.get_context("spawn")) as pool:
-        for lo, out in pool.map(oracle_rows, jobs, timeout=900):
-            rows[lo:lo + len(out)] = out
-    return rows
+        for c, (lo, out) in zip(where, pool.map(oracle_rows, jobs, timeout=900)):
+            out_rows[c][lo:lo + len(out)] = out
+    return out_rows
 
 
-def compare(rec, rows, blocks, flag_carrier=1, flag_corr=2, flag_index_error=4, only=None):
+def compare(rec, rows, blocks, flag_carrier=1, flag_corr=2, flag_index_error=4, only=None, flag_fit=16):
     """-> (mismatch counts, worst deviations, [indices of carrier-bin ties]).  Exact fields (bin,
     sample, verdicts) are counted over every block; the worst deviations only over the blocks
-    where `only` (bool array) is set, when given."""
+    where `only` (bool array) is set, when given.  A FitUnconverged row is a carrier mismatch
+    unless the record carries `flag_fit`."""
     from oracle import thrifty_np as onp
     mism = dict(bin=0, carrier=0, sample=0, det=0, index_error=0)
-    worst = dict(energy=0.0, offset=0.0, car_off=0.0, car_energy=0.0, noise=0.0)
+    worst = dict(energy=0.0, offset=0.0, car_off=0.0, car_energy=0.0, noise=0.0, car_noise=0.0)
     ties = []
     for i, row in enumerate(rows):
         r = rec[i]
         if row is None or (r["flags"] & flag_index_error):
             mism["index_error"] += (row is None) != bool(r["flags"] & flag_index_error)
             continue
-        cbin, cdet, coff, cen, samp, det, en, off, noise = row
+        if isinstance(row, FitUnconverged):
+            mism["bin"] += r["carrier_bin"] != row[0]
+            mism["carrier"] += not (r["flags"] & flag_fit)
+            continue
+        cbin, cdet, coff, cen, samp, det, en, off, noise = row[:9]
         if r["carrier_bin"] != cbin:
             # inherent tie: the two bins' float32 magnitudes are equal (to an ulp) in NumPy itself and
             # the two FFT implementations round differently -- counted apart, never silently
@@ -77,6 +114,8 @@ def compare(rec, rows, blocks, flag_carrier=1, flag_corr=2, flag_index_error=4, 
         if only is not None and not only[i]:
             continue
         worst["car_energy"] = max(worst["car_energy"], abs(r["carrier_energy"] - cen) / abs(cen))
+        if len(row) > 9:
+            worst["car_noise"] = max(worst["car_noise"], abs(r["carrier_noise"] - row[9]) / abs(row[9]))
         worst["car_off"] = max(worst["car_off"], abs(r["carrier_offset"] - coff))
         if r["corr_sample"] == samp:
             worst["energy"] = max(worst["energy"], abs(r["corr_energy"] - en) / abs(en))

@@ -84,6 +84,18 @@ struct ShiftParams {
     float2 segc0[kMaxSections];  // sectioned correlate stage: exp(2 pi i s (seg_start[g] / N - 1/2))
 };
 
+// Long blocks (32768, 65536): which carrier-stage form runs.  The one rule for the launch
+// (carrier_r0, detect_long.hip) and the report (thr_get_path_info, handle.hip).
+enum LongCarrierForm {
+    kLongCarSub = 0,        // k_carrier_sub + k_select (full spectrum; stddev term; stage dumps)
+    kLongCarDit = 1,        // k_carrier_dit + k_select_dit: window + fit margin inside bins [0, 128)
+    kLongCarSubPruned = 2,  // k_carrier_sub_pruned + k_select: ... inside bins [0, 128 R0)
+};
+inline LongCarrierForm long_carrier_form(const DevCfg& cfg, bool dump) {
+    if (cfg.car_prune != 1 || cfg.car_want_std != 0 || dump) return kLongCarSub;
+    return cfg.win_lo + cfg.win_count + 3 <= 128 ? kLongCarDit : kLongCarSubPruned;
+}
+
 // detect16k_preshift.hip -- PreshiftDetector variant (one fused kernel per block at 16384)
 hipError_t prepare_preshift_16k();
 hipError_t launch_preshift_16k(int fmt, const void* samples, int n_blocks, const DevCfg& cfg,

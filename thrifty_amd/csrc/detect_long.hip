@@ -1106,7 +1106,8 @@ hipError_t carrier_r0(int fmt, const void* samples, int n_blocks, const DevCfg& 
                       CarStats* stats, float2* dump_fft, int grid, hipStream_t stream) {
     typedef void (*fn_t)(const void*, int, DevCfg, const cpx*, const cpx*, float*, float*, cpx*);
     const bool st = cfg.car_want_std != 0, dump = dump_fft != nullptr;
-    if (cfg.car_prune == 1 && !st && !dump && cfg.win_lo + cfg.win_count + 3 <= 128) {
+    const LongCarrierForm form = long_carrier_form(cfg, dump);
+    if (form == kLongCarDit) {
         typedef void (*dfn_t)(const void*, int, DevCfg, const cpx*, cpx*, float*);
         dfn_t dfn = fmt == THR_IN_U8 ? &k_carrier_dit<THR_IN_U8, R0> : &k_carrier_dit<THR_IN_C64, R0>;
         hipLaunchKernelGGL(dfn, dim3(grid), dim3(NT), LDS_BYTES, stream, samples, n_blocks, cfg,
@@ -1116,7 +1117,7 @@ hipError_t carrier_r0(int fmt, const void* samples, int n_blocks, const DevCfg& 
                            partial, stats);
         return hipGetLastError();
     }
-    if (cfg.car_prune == 1 && !st && !dump) {
+    if (form == kLongCarSubPruned) {
         typedef void (*pfn_t)(const void*, int, DevCfg, const cpx*, const cpx*, float*, float*);
         pfn_t pfn = fmt == THR_IN_U8 ? &k_carrier_sub_pruned<THR_IN_U8, R0>
                                      : &k_carrier_sub_pruned<THR_IN_C64, R0>;

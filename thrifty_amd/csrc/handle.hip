@@ -455,7 +455,10 @@ int thr_get_path_info(thr_handle* h, thr_path_info* out) try {
         cor = h->sec4k ? "k_correlate_4k" : "k_correlate";
         if (!h->sec4k) thr::correlate_geom_16k(h->dev, &out->rows_lo, &out->rows_hi);
     } else if (h->lng && !h->preshift_num) {
-        car = h->dev.car_prune == 1 ? "k_carrier_dit+k_select_dit" : "k_carrier_sub+k_select";
+        const thr::LongCarrierForm form = thr::long_carrier_form(h->dev, false);
+        car = form == thr::kLongCarDit          ? "k_carrier_dit+k_select_dit"
+              : form == thr::kLongCarSubPruned ? "k_carrier_sub_pruned+k_select"
+                                                : "k_carrier_sub+k_select";
         cor = h->seg ? "k_correlate_seg" : "k_correlate_sub";
         if (h->seg) thr::correlate_geom_seg(h->dev, &out->rows_lo, &out->rows_hi);
     } else if (h->small) {
