@@ -483,14 +483,17 @@ class OraclePreshiftDetector(object):
         self.corr_thresh = corr_thresh
         self.last = None        # (int_shift, frac_shift, template index) of the last block
 
-    def detect_block(self, block_idx, x, want_data=False):
+    def detect_block(self, block_idx, x, want_data=False, force=None):
         """want_data: also return (rolled FFT#1, correlation) -- what the reference class hands out
-        under yield_data (detect.py:60-78 with the shifter / despreader of detect_preshift.py:62-80)."""
-        out = self._detect_block(block_idx, x)
+        under yield_data (detect.py:60-78 with the shifter / despreader of detect_preshift.py:62-80).
+        force: None, or (int_shift, template index) to roll by and correlate with in place of the
+        ones the carrier offset gives -- to evaluate the rest of the block at another engine's
+        choice where that offset lies within float rounding of a bank boundary."""
+        out = self._detect_block(block_idx, x, force)
         data, self._data = self._data, None
         return (out, data) if want_data else out
 
-    def _detect_block(self, block_idx, x):
+    def _detect_block(self, block_idx, x, force=None):
         assert len(x) == self.block_len
         self._data = None
         spec = np.fft.fft(x)                       # complex64 in -> complex64 out
@@ -507,8 +510,11 @@ class OraclePreshiftDetector(object):
         shift = -(np.int64(idx) + off)             # carrier_sync.py:71
         int_shift = int(np.round(shift))           # detect_preshift.py:62-65
         frac = shift - int_shift
-        rolled = np.roll(spec, int_shift)          # carrier_sync.py:241-245
         j = self.shifted.nearest(frac)
+        if force is not None:
+            int_shift, j = int(force[0]), int(force[1])
+            frac = shift - int_shift
+        rolled = np.roll(spec, int_shift)          # carrier_sync.py:241-245
         self.last = (int_shift, frac, j)
         corr = np.fft.ifft(rolled * self.shifted.spectra_conj[j])[: self.shifted.corr_len]
         self._data = (rolled, corr)
@@ -522,8 +528,8 @@ class OraclePreshiftDetector(object):
         cs = CorrStage(cdet, pk, coff, peak_mag, cnoise, cthr)
         return BlockResult(cdet, self.new_len * block_idx + pk + coff, car, cs)
 
-    def detect_u8(self, block_idx, raw, want_data=False):
-        return self.detect_block(block_idx, iq_u8_to_c64(raw), want_data)
+    def detect_u8(self, block_idx, raw, want_data=False, force=None):
+        return self.detect_block(block_idx, iq_u8_to_c64(raw), want_data, force)
 
 
 # --------------------------------------------------------------------------

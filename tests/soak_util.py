@@ -20,15 +20,24 @@ class FitUnconverged(tuple):
 
 def oracle_rows(args):
     """(worker) -> (lo, [(cbin, cdet, coff, cenergy, sample, det, energy, offset, noise, cnoise), ...]).
-    args: (lo, blocks, n, h, tpl, cthr, cwin, xthr[, carrier_len[, preshift_num]]); carrier_len None:
-    the template's length; preshift_num > 0: OraclePreshiftDetector with that many templates."""
+    args: (lo, blocks, n, h, tpl, cthr, cwin, xthr[, carrier_len[, preshift_num[, interpolator[,
+    fastdet]]]]); carrier_len None: the template's length; preshift_num > 0: OraclePreshiftDetector
+    with that many templates and that carrier interpolator (default "parabolic"), whose rows end in
+    two more fields: the (int_shift, frac_shift, template index) it chose (None without a carrier)
+    and whether the carrier offset is the Python int 0; fastdet true: OracleFastdet, its powers
+    given as roots (the record's units), ending in (-argmax, 0.0, 0) and False."""
     os.environ["OMP_NUM_THREADS"] = "1"
     lo, blocks, n, h, tpl, cthr, cwin, xthr = args[:8]
     carrier_len = args[8] if len(args) > 8 else None
     preshift_num = args[9] if len(args) > 9 else 0
+    interpolator = args[10] if len(args) > 10 else "parabolic"
+    fastdet = bool(args[11]) if len(args) > 11 else False
     from oracle import thrifty_np as onp
+    if fastdet:
+        orc = onp.OracleFastdet(n, h, tpl, cthr, cwin, xthr)
+        return lo, [_fastdet_row(orc.detect_u8(lo + i, b)) for i, b in enumerate(blocks)]
     if preshift_num:
-        orc = onp.OraclePreshiftDetector(n, h, tpl, cthr, cwin, xthr, num=preshift_num)
+        orc = onp.OraclePreshiftDetector(n, h, tpl, cthr, cwin, xthr, num=preshift_num, interpolator=interpolator)
     else:
         orc = onp.OracleDetector(n, h, tpl, cthr, cwin, xthr, carrier_len=carrier_len)
     out = []
@@ -46,21 +55,30 @@ def oracle_rows(args):
             out.append(FitUnconverged((idx, bool(det), 0.0, float(peak), -1, False, 0.0, 0.0, 0.0, float(noise))))
             continue
         c = r.corr
-        out.append((r.carrier.bin, bool(r.carrier.detected), float(r.carrier.offset), float(r.carrier.energy),
-                    int(c.sample) if c else -1, bool(c.detected) if c else False,
-                    float(c.energy) if c else 0.0, float(c.offset) if c else 0.0,
-                    float(c.noise) if c else 0.0, float(r.carrier.noise)))
+        row = (r.carrier.bin, bool(r.carrier.detected), float(r.carrier.offset), float(r.carrier.energy),
+               int(c.sample) if c else -1, bool(c.detected) if c else False,
+               float(c.energy) if c else 0.0, float(c.offset) if c else 0.0,
+               float(c.noise) if c else 0.0, float(r.carrier.noise))
+        out.append(row + (orc.last, isinstance(r.carrier.offset, int)) if preshift_num else row)
     return lo, out
 
 
-def run_oracle(blocks, n, h, tpl, cthr, cwin, xthr, procs=None, chunk=64, carrier_len=None, preshift_num=0):
-    return run_oracle_many([(blocks, n, h, tpl, cthr, cwin, xthr, carrier_len, preshift_num)],
+def _fastdet_row(w):
+    return (w.argmax, bool(w.carrier), float(w.carrier_offset), float(np.sqrt(w.carrier_max)),
+            int(w.peak_idx), bool(w.detected), float(np.sqrt(w.peak_power)), float(w.peak_offset),
+            float(np.sqrt(w.noise_power)), float(np.sqrt(w.carrier_noise)),
+            (-int(w.argmax), 0.0, 0) if w.carrier else None, False)
+
+
+def run_oracle(blocks, n, h, tpl, cthr, cwin, xthr, procs=None, chunk=64, carrier_len=None, preshift_num=0,
+               interpolator="parabolic", fastdet=False):
+    return run_oracle_many([(blocks, n, h, tpl, cthr, cwin, xthr, carrier_len, preshift_num, interpolator, fastdet)],
                            procs=procs, chunk=chunk)[0]
 
 
 def run_oracle_many(configs, procs=None, chunk=64):
     """Several oracle runs in one pool of workers: configs = [(blocks, n, h, tpl, cthr, cwin, xthr,
-    carrier_len, preshift_num), ...] -> [rows of each config]."""
+    carrier_len, preshift_num[, interpolator[, fastdet]]), ...] -> [rows of each config]."""
     procs = procs or max(1, min(32, (os.cpu_count() or 2) // 2))
     jobs, where = [], []
     for c, (blocks, *rest) in enumerate(configs):
