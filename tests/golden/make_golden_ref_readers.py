@@ -1,6 +1,6 @@
 """Stores what the reference's native block readers (oracle/_ref/libfastcard_readers.so, built by
-oracle/Makefile) return for the inputs of tests/test_ref_readers.py and of the reference-reader test of
-tests/test_gpu_card_ingest.py -> tests/golden/ref_readers.npz, so that those tests also run where the
+oracle/Makefile) return for the inputs of tests/test_ref_readers.py and of the reference-reader tests of
+tests/test_gpu_card_ingest.py and tests/test_gpu_card_tail.py -> tests/golden/ref_readers.npz, so that those tests also run where the
 library cannot be built.  Needs the library (`make -C oracle`), no GPU:
 
     python tests/golden/make_golden_ref_readers.py
@@ -17,7 +17,7 @@ os.environ["THRIFTY_RECORD_REF"] = "1"
 # the cases (test_ref_readers.ref_read's first argument) and the arrays stored per case, "<case>__<field>"
 CASES = ["card_framing_64", "card_framing_4096", "card_framing_16384", "card_history_64", "card_history_0",
          "malformed_short", "malformed_long", "malformed_meta", "raw_64_16", "raw_4096_1024", "raw_16384_4920",
-         "ingest_c2"]
+         "ingest_c2", "card_tail_64", "card_tail_128"]
 FIELDS = ["sec", "usec", "idx", "data", "rc"]
 
 
@@ -41,6 +41,11 @@ def main():
         with open(path, "w") as f:
             f.write("# capture\n" + card_text(g))
         ref_read("ingest_c2", path, int(g["block_len"]), int(g["history_len"]), card=True)
+        # the planted tails of tests/test_gpu_card_tail.py::test_the_reference_native_reader_decodes_the_same_bytes
+        from test_gpu_card_tail import ref_reader_case
+        for n in (64, 128):
+            case, path, _ = ref_reader_case(n, d)
+            ref_read(case, path, n, 0, card=True)
     have = sorted(np.load(STORED).files)
     assert have == sorted("%s__%s" % (c, f) for c in CASES for f in FIELDS), have
 

@@ -27,6 +27,7 @@ namespace {
 // order-preserving maps to unsigned keys
 __device__ __forceinline__ unsigned key_i32(int v) { return unsigned(v) ^ 0x80000000u; }
 __device__ __forceinline__ unsigned long long key_f64(double v) {
+    if (v == 0.0) v = 0.0;  // -0.0 and +0.0 compare equal in NumPy's sorts: one key, input order decides
     const unsigned long long u = (unsigned long long)__double_as_longlong(v);
     return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
