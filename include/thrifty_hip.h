@@ -50,7 +50,14 @@ extern "C" {
  *    carrier fit's MINPACK exit code), thr_get_path_info (which kernels a handle's launches take, and
  *    why); thr_detect_offsets refuses non-finite offsets (additions; records of several-template
  *    handles change in the last bits of their float fields only) */
-#define THR_ABI_VERSION 9
+/* 10: + the carrier gate -- fastcard's job, raw capture -> carrier verdict -> .card, on the device:
+ *    THR_VARIANT_GATE for thr_create_ex, thr_gate / thr_gate_stream / thr_gate_card,
+ *    thr_gate_slot_stride, thr_format_card, thr_run_gate_stream / thr_run_gate_card (the whole file ->
+ *    .card loop in one call) (additions only; thr_detect*, thr_submit*, thr_run_card / thr_run_stream,
+ *    thr_detect_offsets and thr_debug_stage* refuse a gate handle with THR_ERR_STATE; the queries,
+ *    thr_input_window*, thr_set_stream*, thr_sync, thr_profile_*, thr_debug_fft -- the carrier stage's
+ *    spectrum -- and thr_compact_device are defined for it) */
+#define THR_ABI_VERSION 10
 
 /* status codes */
 #define THR_OK 0
@@ -93,7 +100,7 @@ extern "C" {
 typedef struct thr_settings {
     int32_t block_len;        /* samples per block, power of two                   */
     int32_t history_len;      /* samples repeated from the previous block          */
-    int32_t n_templates;      /* >= 1 (the reference has exactly 1)                */
+    int32_t n_templates;      /* >= 1 (the reference has exactly 1); 0: THR_VARIANT_GATE */
     int32_t template_len;     /* samples per template (all templates equal length) */
     const double* templates;  /* [n_templates][template_len], real, time domain    */
     int32_t carrier_len;      /* Dirichlet-kernel width; 0 = template_len          */
@@ -202,10 +209,17 @@ int thr_create_fastdet(const thr_settings* settings, thr_handle** out);
  *                         (A sectioned block_len 16384 handle: the same, for its sections' rows.)
  *   THR_PATH_UNSECTIONED_GENERIC_ROWS  both of the above (block_len 16384: the generic k_correlate).
  * All paths implement the same reference semantics and agree to rounding (tests/test_gpu_*.py).
+ *
+ * THR_VARIANT_GATE (ABI 10): the carrier gate, see thr_gate below.  n_templates = 0, templates =
+ * NULL, template_len / carrier_len / corr_thresh ignored; carrier_thresh = {constant, snr, 0} in the
+ * POWER domain, narrowed to float32 like fastcard's (fargs_type.h); carrier_window = [min, max] checked
+ * like cardet_normalize_window (cardet.c:43-70: negative = from the end, min < 0 <= max refused,
+ * out of range refused, swapped if reversed).  No template spectra and no correlate buffers are built.
  */
 #define THR_VARIANT_DEFAULT 0
 #define THR_VARIANT_PRESHIFT 1
 #define THR_VARIANT_FASTDET 2
+#define THR_VARIANT_GATE 3
 #define THR_INTERP_PARABOLIC 0
 #define THR_INTERP_NONE 1
 #define THR_INTERP_GAUSSIAN 2
@@ -514,6 +528,96 @@ int thr_run_card(thr_handle* h, const char* text, size_t text_len, const thr_run
                  thr_run_stats* stats);
 int thr_run_stream(thr_handle* h, const uint8_t* stream, size_t n_bytes, int64_t first_block_idx,
                    const thr_run_opts* opts, thr_run_stats* stats);
+/*
+ * The carrier gate -- replaces the reference's `fastcard` for inputs that lie in memory
+ * (fastcard/fastcard.c:177-189 + cardet.c:7-41 + fastcard_cli.c:171-194): which blocks of a capture
+ * carry a carrier, and those blocks as base64, ready to be written as .card lines.  The handle comes
+ * from thr_create_ex(..., THR_VARIANT_GATE, ...).  Per block, in float32 like cardet:
+ *   sum = sum |X|^2 over all block_len bins, max = the first maximum of |X|^2 over the window,
+ *   noise = (sum - 2 max) / (block_len - 1) (0 when sum == 0), threshold = c + s * noise,
+ *   passed = max > threshold.
+ * (The carrier stage is the detectors': it takes the first maximum of the float32 MAGNITUDE, so the
+ * bin can differ from cardet's only where two window powers round to one magnitude.)
+ * out[i], one record per block: flags = THR_FLAG_CARRIER when passed, carrier_bin = the maximum's bin,
+ * carrier_energy = sqrt(max) and carrier_noise = sqrt(noise) -- what fastcard's info line prints
+ * (fastcard_cli.c:175-180; NaN where noise < 0) -- the float32 bits of `threshold` in the low half of
+ * `reserved`, corr_sample = -1, every other field 0.
+ * slots: the k-th passed block, in input order, gets the slot slots[k * slot_stride ...]: payload_chars
+ * = 4 * ceil(2 * block_len / 3) characters of canonical base64 ('=' padded) of its 2 * block_len raw
+ * bytes, then '\n'; the bytes from there to the next slot are not written.  thr_gate_slot_stride
+ * tells both numbers (slot_stride = payload_chars + 1 rounded up to 16).  `slots_capacity` (bytes) must
+ * hold a slot for EVERY block of the call -- all of them may pass -- else THR_ERR_ARG before any device
+ * work; *n_passed slots are written.  Only passed blocks are encoded and only their slots cross PCIe.
+ * Host pointers, synchronous, any number of blocks (chunks of at most max_batch).
+ *   thr_gate         packed u8 blocks, block_idx as in thr_detect (NULL: 0, 1, 2, ...)
+ *   thr_gate_stream  raw stream, framing and first_block_idx as in thr_detect_stream: block i is
+ *                    the 2 * block_len bytes 2 * (block_len - history_len) * i bytes into `stream`
+ *   thr_gate_card    .card text + payload offsets (thr_frame_card), decoded on the device as in
+ *                    thr_detect_card: re-filter an existing .card with another window or threshold
+ */
+int thr_gate_slot_stride(const thr_handle* h, size_t* slot_stride, size_t* payload_chars);
+int thr_gate(thr_handle* h, const uint8_t* samples, const int64_t* block_idx, size_t n_blocks, thr_record* out,
+             size_t* n_passed, char* slots, size_t slots_capacity);
+int thr_gate_stream(thr_handle* h, const uint8_t* stream, size_t n_bytes, int64_t first_block_idx, thr_record* out,
+                    size_t out_capacity, size_t* n_blocks_out, size_t* n_passed, char* slots,
+                    size_t slots_capacity);
+int thr_gate_card(thr_handle* h, const char* text, size_t text_len, const int64_t* payload_off,
+                  const int64_t* block_idx, size_t n_blocks, thr_record* out, size_t* n_passed, char* slots,
+                  size_t slots_capacity);
+/*
+ * .card lines from payload slots -- the inverse of thr_frame_card; replaces fastcard_cli.c:187-192
+ * ("%ld.%06ld %PRId64 %s\n").  Line i = timestamps[i] split into seconds and microseconds (rounded to
+ * the nearest microsecond, ties to even: a fraction >= .9999995 carries into the seconds, like
+ * thrifty_amd.block_data.card_line), block_idx[i], the first `payload_chars` characters of slot i.
+ * `out_capacity` must be >= n * (THR_CARD_HEADER_MAX + payload_chars + 1).  Host only, no device,
+ * handle-free.
+ */
+#define THR_CARD_HEADER_MAX 48
+int thr_format_card(const double* timestamps, const int64_t* block_idx, const char* slots, size_t slot_stride,
+                    size_t payload_chars, size_t n, char* out, size_t out_capacity, size_t* out_len);
+
+/*
+ * The whole `fastcard -i <file> [--card] -o <out.card>` loop in ONE call (fastcard_cli.c:143-196) for an
+ * input that lies in memory (the mmap of the file), the twin of thr_run_stream / thr_run_card and built
+ * the same way, on the entry points above: the calling thread frames a batch and gates it; a thread of
+ * the library assembles the .card lines of the passed blocks and writev()s them to `out_fd`, so the text
+ * of one batch leaves while the next is on the device (up to three batches between the two threads).
+ * Output order = input order.  If the handle has an input window around the input, the chunk copies
+ * are DMA from the page cache and the window is released behind them.
+ * thr_run_gate_stream: `stream` = the raw u8 I/Q capture from its first byte.  Framing is the
+ *   reference's (raw_reader.c:15-46, fastcard_cli.c:151-169): the reader takes block_len - history_len
+ *   new samples per block, the first `skip` blocks are dropped, kept block i (index first_block_idx + i;
+ *   fastcard: 0) is the window that starts 2 * (block_len - history_len) * (i + skip) - 2 * history_len
+ *   bytes into the stream and is read in place; where that is negative the missing history is ZERO
+ *   BYTES (the one deviation: the reference leaves it uninitialised, reader.c:49).  Every block of a
+ *   batch is stamped with the wall clock when the batch is framed (`timestamp` NaN) or with `timestamp`.
+ * thr_run_gate_card: `text` = .card text; timestamps and indices are the input lines', the first `skip`
+ *   records are dropped, and the output line of a passed block is its input line, copied.
+ * rec_out (optional): the record of EVERY block gated, in input order (rec_capacity too small ->
+ * THR_ERR_ARG when it overflows).  A failed write() ends the run with THR_ERR_DEVICE.
+ */
+typedef struct thr_gate_run_opts {
+    uint32_t struct_bytes;        /* sizeof(thr_gate_run_opts) -- guards the layout                  */
+    int32_t batch_blocks;         /* blocks per batch; 0 = the handle's max_batch (at most ~64 MiB of input) */
+    int32_t out_fd;               /* >= 0: the .card lines are written here; -1: verdicts only       */
+    int32_t skip;                 /* leading blocks read and dropped (fastcard -k; its default is 1) */
+    double timestamp;             /* thr_run_gate_stream only, see above                             */
+    thr_record* rec_out;          /* NULL, or room for rec_capacity records                          */
+    size_t rec_capacity;
+} thr_gate_run_opts;
+typedef struct thr_gate_run_stats {
+    uint64_t blocks, passed, batches;
+    uint64_t bytes_in;            /* input bytes                                                     */
+    uint64_t text_bytes;          /* bytes written to out_fd                                         */
+    double total_s;               /* the whole call; the calling thread:                             */
+    double frame_s, gate_s, wait_s;   /* framing, inside thr_gate*, waiting for a free batch buffer  */
+    double format_s, write_s;     /* the library thread: line headers, writev()                      */
+} thr_gate_run_stats;
+int thr_run_gate_stream(thr_handle* h, const uint8_t* stream, size_t n_bytes, int64_t first_block_idx,
+                        const thr_gate_run_opts* opts, thr_gate_run_stats* stats);
+int thr_run_gate_card(thr_handle* h, const char* text, size_t text_len, const thr_gate_run_opts* opts,
+                      thr_gate_run_stats* stats);
+
 /* The settings a handle was created with (`templates` is NULL: the array is not retained). */
 int thr_get_settings(const thr_handle* h, thr_settings* out);
 

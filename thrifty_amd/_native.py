@@ -24,7 +24,7 @@ FLAG_INT_OFFSET = 8
 FLAG_FIT_UNCONVERGED = 16
 N_KERNEL_SLOTS = 5
 
-ABI_VERSION = 9     # THR_ABI_VERSION of include/thrifty_hip.h
+ABI_VERSION = 10    # THR_ABI_VERSION of include/thrifty_hip.h
 
 EXPORTS = [
     "thr_abi_version", "thr_last_error", "thr_create", "thr_destroy", "thr_detect",
@@ -34,13 +34,16 @@ EXPORTS = [
     "thr_submit", "thr_submit_card", "thr_submit_stream", "thr_collect", "thr_inputs_consumed", "thr_poll",
     "thr_set_stream_default", "thr_format_toad",
     "thr_run_card", "thr_run_stream", "thr_get_settings", "thr_input_window_ex", "thr_input_window_release", "thr_detect_offsets", "thr_set_wait_mode", "thr_debug_window", "thr_debug_window_times", "thr_debug_correlate_geom", "thr_debug_sections", "thr_debug_pipe_times", "thr_get_path_info",
+    "thr_gate", "thr_gate_stream", "thr_gate_card", "thr_gate_slot_stride", "thr_format_card",
+    "thr_run_gate_stream", "thr_run_gate_card",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
-VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET = 0, 1, 2      # THR_VARIANT_*
+VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
 INTERPOLATORS = {"parabolic": 0, "none": 1, "gaussian": 2, "cosine": 3}      # THR_INTERP_*
 PATHS = {"auto": 0, "multipass": 1, "unsectioned": 2, "generic_rows": 3, "unsectioned_generic_rows": 4}      # THR_PATH_*
 MAX_IN_FLIGHT = 3       # THR_MAX_IN_FLIGHT
 TOAD_LINE_MAX = 384     # THR_TOAD_LINE_MAX
+CARD_HEADER_MAX = 48    # THR_CARD_HEADER_MAX
 
 
 class ThrSettings(C.Structure):
@@ -86,6 +89,24 @@ class ThrRunStats(C.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
+
+
+class ThrGateRunOpts(C.Structure):
+    _fields_ = [
+        ("struct_bytes", C.c_uint32), ("batch_blocks", C.c_int32), ("out_fd", C.c_int32), ("skip", C.c_int32),
+        ("timestamp", C.c_double), ("rec_out", C.c_void_p), ("rec_capacity", C.c_size_t),
+    ]
+
+
+class ThrGateRunStats(C.Structure):
+    _fields_ = [
+        ("blocks", C.c_uint64), ("passed", C.c_uint64), ("batches", C.c_uint64), ("bytes_in", C.c_uint64),
+        ("text_bytes", C.c_uint64), ("total_s", C.c_double), ("frame_s", C.c_double), ("gate_s", C.c_double),
+        ("wait_s", C.c_double), ("format_s", C.c_double), ("write_s", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 # numpy mirror of thr_record (64 bytes)
@@ -204,6 +225,15 @@ def load_library():
     lib.thr_debug_stage_offsets.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, vp, vp, vp]
     lib.thr_identify.argtypes = [C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp,
                                  vp, C.POINTER(C.c_size_t)]
+    szp = C.POINTER(C.c_size_t)
+    lib.thr_gate_slot_stride.argtypes = [vp, szp, szp]
+    lib.thr_gate.argtypes = [vp, vp, vp, C.c_size_t, vp, szp, vp, C.c_size_t]
+    lib.thr_gate_stream.argtypes = [vp, vp, C.c_size_t, C.c_int64, vp, C.c_size_t, szp, szp, vp, C.c_size_t]
+    lib.thr_gate_card.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp, szp, vp, C.c_size_t]
+    lib.thr_format_card.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, szp]
+    lib.thr_run_gate_stream.argtypes = [vp, vp, C.c_size_t, C.c_int64, C.POINTER(ThrGateRunOpts),
+                                        C.POINTER(ThrGateRunStats)]
+    lib.thr_run_gate_card.argtypes = [vp, vp, C.c_size_t, C.POINTER(ThrGateRunOpts), C.POINTER(ThrGateRunStats)]
     _lib = lib
     return lib
 
@@ -245,6 +275,33 @@ def format_toad(recs, timestamps, new_len, rxid=None, with_txid=False, carrier_o
     _check(lib, lib.thr_format_toad(recs.ctypes.data, ts.ctypes.data, n, int(new_len),
                                     0 if rxid is None else 1, 0 if rxid is None else int(rxid),
                                     int(bool(with_txid)), int(carrier_offset_f32),
+                                    buf.ctypes.data, buf.size, C.byref(used)))
+    return buf[:used.value].tobytes()
+
+
+def gate_payload_chars(block_len):
+    """Base64 characters of one block's 2 * block_len raw bytes ('=' padding included)."""
+    return (2 * int(block_len) + 2) // 3 * 4
+
+
+def gate_slot_stride(block_len):
+    """Bytes from one payload slot of the gate to the next: payload, newline, rounded up to 16."""
+    return (gate_payload_chars(block_len) + 1 + 15) // 16 * 16
+
+
+def format_card(timestamps, block_idx, slots, block_len):
+    """thr_format_card: .card text (bytes, one line per slot) from the gate's payload slots
+    (uint8 [n, slot_stride] or flat) -- the text `block_data.card_line` produces."""
+    lib = load_library()
+    ts = np.ascontiguousarray(timestamps, dtype=np.float64).reshape(-1)
+    idx = np.ascontiguousarray(block_idx, dtype=np.int64).reshape(-1)
+    n = len(ts)
+    stride, chars = gate_slot_stride(block_len), gate_payload_chars(block_len)
+    sl = np.ascontiguousarray(slots, dtype=np.uint8).reshape(-1)
+    assert len(idx) == n and sl.size >= n * stride
+    buf = np.empty(max(1, n * (CARD_HEADER_MAX + chars + 1)), dtype=np.uint8)
+    used = C.c_size_t(0)
+    _check(lib, lib.thr_format_card(ts.ctypes.data, idx.ctypes.data, sl.ctypes.data, stride, chars, n,
                                     buf.ctypes.data, buf.size, C.byref(used)))
     return buf[:used.value].tobytes()
 
@@ -379,6 +436,99 @@ atexit.register(_close_live_engines)
 
 class Engine(object):
     """One detector handle == one (device, stream).  Not thread-safe per handle."""
+
+    @classmethod
+    def gate(cls, block_len, history_len, window=(0, -1), threshold=(100.0, 2.0), device_id=0, max_batch=2048,
+             path="auto"):
+        """The carrier gate (THR_VARIANT_GATE): fastcard's verdict `max > c + s * noise` (power domain,
+        threshold = (c, s)) over the inclusive, non-wrapping bin window [min, max], and the passed
+        blocks as base64.  No templates; only the gate_* methods and the queries apply."""
+        lib = load_library()
+        st = ThrSettings()
+        st.block_len, st.history_len = int(block_len), int(history_len)
+        st.n_templates, st.template_len, st.templates = 0, 0, None
+        st.carrier_window[0], st.carrier_window[1] = int(window[0]), int(window[1])
+        st.carrier_thresh[0], st.carrier_thresh[1], st.carrier_thresh[2] = float(threshold[0]), float(threshold[1]), 0.0
+        st.device_id, st.max_batch = int(device_id), int(max_batch)
+        handle = C.c_void_p()
+        _check(lib, lib.thr_create_ex(C.byref(st), VARIANT_GATE, 0, PATHS[path], C.byref(handle)))
+        self = cls.__new__(cls)
+        self.path, self.preshift_num = path, 0
+        self._lib, self._h = lib, handle
+        _live_engines.add(self)
+        self.block_len, self.history_len, self.n_templates = int(block_len), int(history_len), 0
+        self.max_batch = int(max_batch)
+        self.slot_stride, self.payload_chars = gate_slot_stride(block_len), gate_payload_chars(block_len)
+        return self
+
+    def _gate_out(self, nb, slots):
+        if slots is None:
+            slots = np.empty(max(1, nb) * self.slot_stride, dtype=np.uint8)
+        assert slots.dtype == np.uint8 and slots.flags.c_contiguous
+        return np.zeros(nb, dtype=RECORD_DTYPE), slots
+
+    def gate_blocks(self, blocks, block_idx=None, slots=None):
+        """thr_gate: u8 [B, 2N] -> (records [B], n_passed, slots uint8 -- slot k = the k-th passed
+        block's base64 payload and newline at [k * slot_stride ...]).  `slots`: a caller buffer (uint8,
+        at least B * slot_stride bytes; only the passed slots' payload + newline bytes are written)."""
+        a = np.ascontiguousarray(np.asarray(blocks, dtype=np.uint8)).reshape(-1, 2 * self.block_len)
+        nb = a.shape[0]
+        out, slots = self._gate_out(nb, slots)
+        idx, idx_p = self._idx_ptr(block_idx, nb)
+        n = C.c_size_t(0)
+        _check(self._lib, self._lib.thr_gate(self._h, a.ctypes.data, idx_p, nb, out.ctypes.data, C.byref(n),
+                                             slots.ctypes.data, slots.size))
+        return out, n.value, slots
+
+    def gate_stream(self, stream, first_block_idx=0, slots=None):
+        """thr_gate_stream: raw u8 I/Q bytes, overlapping blocks framed on the device (see
+        detect_stream) -> (records [n_whole_blocks], n_passed, slots)."""
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        stride = 2 * (self.block_len - self.history_len)
+        nb = 0 if buf.size < 2 * self.block_len else (buf.size - 2 * self.block_len) // stride + 1
+        out, slots = self._gate_out(nb, slots)
+        got, n = C.c_size_t(0), C.c_size_t(0)
+        _check(self._lib, self._lib.thr_gate_stream(self._h, buf.ctypes.data, buf.size, int(first_block_idx),
+                                                    out.ctypes.data, nb, C.byref(got), C.byref(n),
+                                                    slots.ctypes.data, slots.size))
+        assert got.value == nb
+        return out, n.value, slots
+
+    def gate_card(self, text, payload_off, block_idx=None, slots=None):
+        """thr_gate_card: .card text + payload offsets (see detect_card) -> (records, n_passed, slots)."""
+        buf = np.frombuffer(text, dtype=np.uint8)
+        off = np.ascontiguousarray(np.asarray(payload_off, dtype=np.int64))
+        nb = off.shape[0]
+        out, slots = self._gate_out(nb, slots)
+        idx, idx_p = self._idx_ptr(block_idx, nb)
+        n = C.c_size_t(0)
+        _check(self._lib, self._lib.thr_gate_card(self._h, buf.ctypes.data, buf.size, off.ctypes.data, idx_p, nb,
+                                                  out.ctypes.data, C.byref(n), slots.ctypes.data, slots.size))
+        return out, n.value, slots
+
+    def run_gate(self, data, card=False, out_fd=None, skip=0, timestamp=None, batch_blocks=0, rec_out=None,
+                 first_block_idx=0):
+        """thr_run_gate_stream / thr_run_gate_card: gate the whole input `data` (bytes-like: the mapped
+        capture or .card file) inside the library; the .card lines go to the descriptor `out_fd`, every
+        block's record into `rec_out` (a RECORD_DTYPE array) if given.  -> the statistics as a dict."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        o = ThrGateRunOpts()
+        o.struct_bytes = C.sizeof(ThrGateRunOpts)
+        o.batch_blocks, o.skip = int(batch_blocks or 0), int(skip)
+        o.out_fd = -1 if out_fd is None else int(out_fd)
+        o.timestamp = float("nan") if timestamp is None else float(timestamp)
+        if rec_out is not None:
+            assert rec_out.dtype == RECORD_DTYPE and rec_out.flags.c_contiguous
+            o.rec_out, o.rec_capacity = rec_out.ctypes.data, rec_out.size
+        st = ThrGateRunStats()
+        ptr = buf.ctypes.data if buf.size else None
+        if card:
+            rc = self._lib.thr_run_gate_card(self._h, ptr, buf.size, C.byref(o), C.byref(st))
+        else:
+            rc = self._lib.thr_run_gate_stream(self._h, ptr, buf.size, int(first_block_idx), C.byref(o), C.byref(st))
+        del buf
+        _check(self._lib, rc)
+        return st.as_dict()
 
     def __init__(self, block_len, history_len, templates, carrier_thresh, carrier_window,
                  corr_thresh, carrier_len=0, device_id=0, max_batch=256, preshift_num=0,

@@ -1,6 +1,8 @@
 // The data-path entry points: thr_detect* / thr_submit* / thr_collect, compaction, debug hooks.
 #include "host_internal.hpp"
 
+#include "card_gate.hpp"
+
 extern "C" {
 
 int thr_detect_device(thr_handle* h, const void* d_samples, int format,
@@ -126,6 +128,8 @@ int thr_detect_card(thr_handle* h, const char* text, size_t text_len, const int6
 static int submit_enter(thr_handle* h, const char* who, size_t n_blocks, uint64_t* ticket, int* slot) {
     if (!ticket) return fail(THR_ERR_ARG, "%s: null ticket pointer", who);
     *ticket = 0;
+    if (thr_is_gate(h))
+        return fail(THR_ERR_STATE, "%s: a carrier-gate handle (THR_VARIANT_GATE) has no detect stage: use thr_gate*()", who);
     if (n_blocks > size_t(h->cfg.max_batch))
         return fail(THR_ERR_ARG, "%s: n_blocks %zu exceeds max_batch %d (one submit = one batch)", who,
                     n_blocks, h->cfg.max_batch);

@@ -1,6 +1,8 @@
 // The engine handle: error state, per-handle constants, creation / destruction, queries.
 #include "host_internal.hpp"
 
+#include "card_gate.hpp"
+
 namespace thr {
 namespace host {
 
@@ -316,6 +318,7 @@ int build_constants(thr_handle* h) {
             if (pb) HIP_TRY(hipMalloc(&h->d_park, pb));
         }
     }
+    if (nt == 0) return THR_OK;     // carrier gate: no template spectra
     float2* d_spec = nullptr;
     HIP_TRY(hipMalloc(&d_spec, spec.size() * sizeof(float2)));
     HIP_TRY(hipMemcpy(d_spec, spec.data(), spec.size() * sizeof(float2), hipMemcpyHostToDevice));
@@ -383,6 +386,26 @@ static int create_fastdet(const thr_settings* s, thr_handle** out, int path) {
     if (s->carrier_window[0] < 0 && s->carrier_window[1] >= 0)   // cardet.c:44-48
         return fail(THR_ERR_ARG, "Carrier frequency window range not supported.");
     return create_impl(s, 1, out, 2, path);
+}
+
+// Carrier gate (fastcard's verdict, cardet.c:7-70): the carrier stage and nothing behind it.  The
+// window is cardet_normalize_window's -- inclusive, never wrapping -- and goes to the carrier kernels as
+// (first bin, count); thresholds are float32 like fargs_t's.
+static int create_gate(const thr_settings* s, thr_handle** out, int path) {
+    if (!s || !out) return fail(THR_ERR_ARG, "thr_create_ex: null argument");
+    if (s->n_templates != 0 || s->templates)
+        return fail(THR_ERR_ARG, "the gate variant takes no templates (n_templates = 0, templates = NULL)");
+    if (s->carrier_thresh[2] != 0.0)
+        return fail(THR_ERR_ARG, "the gate threshold is constant + snr * noise_power (no stddev term)");
+    const int n = s->block_len;
+    int lo = s->carrier_window[0], hi = s->carrier_window[1];
+    if (lo < 0 && hi >= 0)                                        // cardet.c:44-48
+        return fail(THR_ERR_ARG, "Carrier frequency window range not supported.");
+    if (lo < 0) lo += n;
+    if (hi < 0) hi += n;
+    if (n > 0 && (lo < 0 || hi < 0 || lo >= n || hi >= n))        // cardet.c:57-62
+        return fail(THR_ERR_ARG, "Carrier frequency window out of range.");
+    return create_impl(s, 0, out, THR_VARIANT_GATE, path);
 }
 
 int thr_create_fastdet(const thr_settings* s, thr_handle** out) try {
@@ -468,6 +491,10 @@ int thr_get_path_info(thr_handle* h, thr_path_info* out) try {
         car = "g_* (multi-pass)";
         cor = "g_* (multi-pass)";
     }
+    if (thr_is_gate(h)) {      // carrier gate: the carrier stage, then k_gate_verdict + k_b64_encode (card_gate.hip)
+        cor = "none";
+        out->rows_lo = out->rows_hi = -1;
+    }
     std::snprintf(out->carrier_kernel, sizeof(out->carrier_kernel), "%s", car);
     std::snprintf(out->correlate_kernel, sizeof(out->correlate_kernel), "%s", cor);
     static const char* const why[] = {
@@ -477,7 +504,11 @@ int thr_get_path_info(thr_handle* h, thr_path_info* out) try {
         "corr_thresh has a stddev term, whose sums run over every kept lag",
         "the unique window of this history / template length needs more sections than pay",
         "this block length has no sectioned form"};
-    if (out->n_sections)
+    if (thr_is_gate(h))
+        std::snprintf(out->text, sizeof(out->text),
+                      "block_len %d, carrier gate: carrier stage %s, then k_gate_verdict + k_b64_encode; no correlate stage",
+                      n, car);
+    else if (out->n_sections)
         std::snprintf(out->text, sizeof(out->text),
                       "block_len %d, %d template(s): carrier stage %s, correlate stage %s in %d sections of %d samples",
                       n, h->cfg.n_templates, car, cor, out->n_sections, out->section_len);
@@ -535,6 +566,7 @@ int thr_create_ex(const thr_settings* s, int variant, int variant_arg, int path,
         case THR_VARIANT_DEFAULT: return create_impl(s, 0, out, -1, path);
         case THR_VARIANT_PRESHIFT: return create_preshift(s, variant_arg, out, path);
         case THR_VARIANT_FASTDET: return create_fastdet(s, out, path);
+        case THR_VARIANT_GATE: return create_gate(s, out, path);
     }
     return fail(THR_ERR_ARG, "thr_create_ex: unknown variant %d", variant);
 } catch (...) {
@@ -564,12 +596,16 @@ static int create_body(thr_handle*& h, const thr_settings* s, int preshift_num, 
     if (n <= 0 || (n & (n - 1))) return fail(THR_ERR_ARG, "block_len %d is not a power of two", n);
     if (n < 64 || n > (1 << 20))
         return fail(THR_ERR_ARG, "block_len %d out of range [64, 1048576]", n);
-    if (s->n_templates < 1 || s->n_templates > thr::kMaxTemplates)
+    const bool gate = variant == THR_VARIANT_GATE;
+    if (gate) {
+        if (s->history_len < 0 || s->history_len >= n)
+            return fail(THR_ERR_ARG, "history_len %d must satisfy 0 <= history_len < block_len", s->history_len);
+    } else if (s->n_templates < 1 || s->n_templates > thr::kMaxTemplates)
         return fail(THR_ERR_ARG, "n_templates %d out of range [1, %d]", s->n_templates,
                     thr::kMaxTemplates);
-    if (!s->templates || s->template_len < 1 || s->template_len > n)
+    else if (!s->templates || s->template_len < 1 || s->template_len > n)
         return fail(THR_ERR_ARG, "bad template (len %d)", s->template_len);
-    if (s->history_len < s->template_len - 1 || s->history_len >= n)
+    else if (s->history_len < s->template_len - 1 || s->history_len >= n)
         return fail(THR_ERR_ARG, "history_len %d must satisfy template_len-1 <= history_len < block_len",
                     s->history_len);  // soa_estimator.py:32 asserts the lower bound
     if (s->max_batch < 1) return fail(THR_ERR_ARG, "max_batch must be >= 1");
@@ -580,9 +616,16 @@ static int create_body(thr_handle*& h, const thr_settings* s, int preshift_num, 
     if (s->device_id < 0 || s->device_id >= ndev)
         return fail(THR_ERR_ARG, "device_id %d out of range (%d devices)", s->device_id, ndev);
 
-    h = new thr_handle();
+    thr_gate_handle* gh = gate ? new thr_gate_handle() : nullptr;
+    h = gate ? gh : new thr_handle();
+    if (gate) h->dev.variant = THR_VARIANT_GATE;      // (from the first moment: thr_destroy deletes by this tag)
     h->cfg = *s;
     h->cfg.templates = nullptr;  // not retained beyond this call (re-pointed below)
+    if (gate) {
+        h->cfg.n_templates = h->cfg.template_len = 0;
+        gh->gate_c = float(s->carrier_thresh[0]);
+        gh->gate_s = float(s->carrier_thresh[1]);
+    }
     h->device = s->device_id;
     h->preshift_num = preshift_num;
     h->path = path;
@@ -613,8 +656,16 @@ static int create_body(thr_handle*& h, const thr_settings* s, int preshift_num, 
         d.history_len = s->history_len;
         d.n_templates = s->n_templates;
         d.carrier_len = s->carrier_len > 0 ? s->carrier_len : s->template_len;
-        if ((rc = window_indices(s->carrier_window[0], s->carrier_window[1], n, &d.win_lo,
-                                 &d.win_count)) != THR_OK)
+        if (gate) {       // cardet_normalize_window (checked by create_gate): [min, max], swapped if reversed
+            int lo = s->carrier_window[0], hi = s->carrier_window[1];
+            if (lo < 0) lo += n;
+            if (hi < 0) hi += n;
+            d.n_templates = 0;
+            d.carrier_len = 1;
+            d.win_lo = std::min(lo, hi);
+            d.win_count = std::abs(hi - lo) + 1;
+        } else if ((rc = window_indices(s->carrier_window[0], s->carrier_window[1], n, &d.win_lo,
+                                        &d.win_count)) != THR_OK)
             break;
         // soa_estimator.py:20-39
         const int corr_len = n - s->template_len + 1;
@@ -622,7 +673,7 @@ static int create_body(thr_handle*& h, const thr_settings* s, int preshift_num, 
         d.corr_lo = pad / 2;
         d.corr_hi = corr_len - (pad - pad / 2);
         d.corr_len = corr_len;
-        if (d.corr_hi <= d.corr_lo) {
+        if (!gate && d.corr_hi <= d.corr_lo) {
             rc = fail(THR_ERR_ARG, "empty correlation window [%d, %d)", d.corr_lo, d.corr_hi);
             break;
         }
@@ -635,9 +686,9 @@ static int create_body(thr_handle*& h, const thr_settings* s, int preshift_num, 
         if (hipMalloc(&d.timeline, 128 * sizeof(unsigned long long)) == hipSuccess)
             hipMemset(d.timeline, 0, 128 * sizeof(unsigned long long));
 #endif
-        d.variant = variant >= 0 ? variant : (preshift_num ? 1 : 0);
+        d.variant = variant >= 0 ? variant : (preshift_num ? 1 : 0);     // (THR_VARIANT_GATE: the tag of a thr_gate_handle)
         d.interp = d.variant == 1 ? interp : 0;
-        d.car_want_std = s->carrier_thresh[2] != 0.0;
+        d.car_want_std = !gate && s->carrier_thresh[2] != 0.0;     // (the gate has no stddev term)
         d.car_prune = 0;
         bool prune_ok = !d.car_want_std;
 #ifdef THR_DEV
@@ -656,17 +707,17 @@ static int create_body(thr_handle*& h, const thr_settings* s, int preshift_num, 
         h->small = thr::small_supported(n) && !multipass && !preshift_num;
         // long blocks: the correlate stage in overlap-save sections wherever the template allows
         const bool unsectioned = path == THR_PATH_UNSECTIONED || path == THR_PATH_UNSECTIONED_GENERIC_ROWS;
-        h->seg = h->lng && !unsectioned && plan_sections(d, s->template_len);
+        h->seg = h->lng && !gate && !unsectioned && plan_sections(d, s->template_len);
         if (!h->seg) d.n_seg = 0;
         // block_len 16384, short template(s), no stddev term: the correlate stage as 4096-sample
         // sections (detect16k_sec.hip); stage dumps and every other launch keep k_correlate
-        h->sec4k = h->fast && !preshift_num && d.variant == 0 && !d.cor_want_std &&
+        h->sec4k = h->fast && !gate && !preshift_num && d.variant == 0 && !d.cor_want_std &&
                    !unsectioned && plan_sections_4k(d, s->template_len);
         if (!h->seg && !h->sec4k) d.n_seg = 0;
         // why not sectioned: the first reason that applies (thr_get_path_info)
         h->why_unsectioned = (h->seg || h->sec4k)                       ? THR_WHY_SECTIONED
                              : (multipass || unsectioned)               ? THR_WHY_PATH
-                             : (preshift_num || d.variant != 0)         ? THR_WHY_VARIANT
+                             : (preshift_num || d.variant != 0 || gate) ? THR_WHY_VARIANT
                              : !(h->fast || h->lng)                     ? THR_WHY_BLOCK_LEN
                              : (h->fast && d.cor_want_std)              ? THR_WHY_STDDEV
                                                                         : THR_WHY_GEOMETRY;
@@ -709,18 +760,22 @@ static int create_body(thr_handle*& h, const thr_settings* s, int preshift_num, 
             // (the exchange rows no longer grow with it -- one row set per workgroup -- so the
             // sub-batch is as large as the small per-block buffers allow: fewer kernel ramps and
             // tails, +3.7 % from 4096 to 16384 blocks)
-            h->long_batch = std::min(s->max_batch, std::max(64, 16384 / s->n_templates));
+            h->long_batch = std::min(s->max_batch, std::max(64, 16384 / std::max(1, s->n_templates)));
             const size_t lb = size_t(h->long_batch);
             const size_t win_w = size_t(std::min(h->dev.win_count + 6, n));
             // (the decimation-in-time carrier stage parks R0 complex values per window bin here)
             CREATE_TRY(hipMalloc(&h->d_win_pow, lb * win_w * sizeof(float) * 2 * r0));
             CREATE_TRY(hipMalloc(&h->d_partial, lb * r0 * 2 * sizeof(float)));
+            if (gate) {      // (no correlate stage: none of its exchange buffers)
+                h->long_chunk = 0;
+            } else {
             h->long_chunk = std::min(h->long_batch, thr::long_chunk_blocks(n, s->n_templates));
             const size_t lc = size_t(h->long_chunk);
             // (one chunk of the two-kernel form, or one row per workgroup of the fused form)
             const size_t rows = std::max(lc, size_t(std::min(h->long_batch, h->n_cu)));
             CREATE_TRY(hipMalloc(&h->d_dsub, rows * s->n_templates * size_t(n) * sizeof(float2)));
             CREATE_TRY(hipMalloc(&h->d_xhat_scratch, size_t(h->n_cu) * 16384 * sizeof(float2)));
+            }
             if (h->seg)
                 CREATE_TRY(hipMalloc(&h->d_seg_stats, lb * s->n_templates * size_t(d.n_seg) * sizeof(thr::CorrStats)));
         }
@@ -736,8 +791,16 @@ static int create_body(thr_handle*& h, const thr_settings* s, int preshift_num, 
         h->stream = h->own_stream;
         const size_t mb = size_t(s->max_batch);
         CREATE_TRY(hipMalloc(&h->d_stats, mb * sizeof(thr::CarStats)));
-        CREATE_TRY(hipMalloc(&h->d_shifts, mb * sizeof(thr::ShiftParams)));
-        CREATE_TRY(hipMalloc(&h->d_corr_stats, mb * s->n_templates * sizeof(thr::CorrStats)));
+        if (gate) {
+            CREATE_TRY(hipMalloc(&gh->d_gate_pos, mb * sizeof(int)));
+            CREATE_TRY(hipMalloc(&gh->d_gate_count, 2 * sizeof(int)));
+            CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&gh->h_gate_count), 2 * sizeof(int), hipHostMallocDefault));
+            CREATE_TRY(hipMalloc(&gh->d_gate_rec, mb * sizeof(thr_record)));
+            CREATE_TRY(hipMalloc(&gh->d_gate_off, 2 * mb * sizeof(long long)));
+        } else {
+            CREATE_TRY(hipMalloc(&h->d_shifts, mb * sizeof(thr::ShiftParams)));
+            CREATE_TRY(hipMalloc(&h->d_corr_stats, mb * s->n_templates * sizeof(thr::CorrStats)));
+        }
         if (h->sec4k)
             CREATE_TRY(hipMalloc(&h->d_seg_stats, mb * s->n_templates * size_t(d.n_seg) * sizeof(thr::CorrStats)));
         CREATE_TRY(hipMalloc(&h->d_work_list, mb * sizeof(int)));
@@ -785,12 +848,23 @@ void thr_destroy(thr_handle* h) {
         (void)hipEventDestroy(e.a);
         (void)hipEventDestroy(e.b);
     }
+    thr_gate_handle* gh = thr_gate_of(h);
+    if (gh) {
+        if (gh->h_gate_count) (void)hipHostFree(gh->h_gate_count);
+        if (gh->h_gate_slots) (void)hipHostFree(gh->h_gate_slots);
+        for (void* b : {static_cast<void*>(gh->d_gate_pos), static_cast<void*>(gh->d_gate_count), static_cast<void*>(gh->d_gate_rec),
+                        gh->d_gate_slots, gh->d_gate_text, static_cast<void*>(gh->d_gate_off)})
+            if (b) (void)hipFree(b);
+    }
     void* bufs[] = {h->d_tables, h->d_twn, h->d_tspec, h->d_stats, h->d_shifts, h->d_corr_stats, h->d_gen_scratch, h->d_tspec_nat, h->d_bank, h->d_gtw, h->d_tspec16k, h->d_tspec4k, h->d_ctab_pair, h->d_park, h->d_seg_stats, h->d_win_pow, h->d_partial, h->d_dsub, h->d_work_list,
                     h->d_work_count, h->d_xhat_scratch, h->d_ncompact, h->d_compact_tiles, h->d_in, h->d_idx, h->d_rec, h->d_forced};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    delete h;
+    if (gh)
+        delete gh;
+    else
+        delete h;
 }
 
 int thr_set_wait_mode(thr_handle* h, int sleeping) try {

@@ -1,6 +1,8 @@
 // The double-buffered chunk pipeline of the host entry points: staging, run_batch*, record copies.
 #include "host_internal.hpp"
 
+#include "card_gate.hpp"
+
 namespace thr {
 namespace host {
 
@@ -436,6 +438,8 @@ int run_batch_small(thr_handle* h, const void* d_samples, int format,
 int run_batch(thr_handle* h, const void* d_samples, int format, const long long* d_block_idx,
               int n_blocks, thr_record* d_out, float2* dump_fft, float2* dump_xhat,
               float2* dump_corr, int dump_template, bool carrier_only, size_t stride) {
+    if (thr_is_gate(h) && !carrier_only)
+        return fail(THR_ERR_STATE, "a carrier-gate handle (THR_VARIANT_GATE) has no detect stage: use thr_gate*()");
     // stride 0: blocks packed back to back; otherwise raw-stream framing (overlapping blocks)
     h->dev.blk_stride = stride ? stride : size_t(h->cfg.block_len) * (format == THR_IN_U8 ? 2 : 8);
 #ifdef THR_DEV
@@ -560,6 +564,8 @@ int chunk_card(thr_handle* h, int b, const char* text, size_t text_len, const in
 
 // entry checks shared by the synchronous host entry points: device, staging, no open tickets
 int pipe_enter_sync(thr_handle* h, const char* who) {
+    if (thr_is_gate(h))
+        return fail(THR_ERR_STATE, "%s: a carrier-gate handle (THR_VARIANT_GATE) has no detect stage: use thr_gate*()", who);
     HIP_TRY(hipSetDevice(h->device));
     const int rc = ensure_pipe(h);
     if (rc != THR_OK) return rc;

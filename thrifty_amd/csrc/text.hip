@@ -254,5 +254,45 @@ int thr_format_toad(const thr_record* recs, const double* timestamps, size_t n, 
     return thr::on_exception("thr_format_toad");
 }
 
+// .card lines (fastcard_cli.c:187-192, "%ld.%06ld %PRId64 %s\n") from the gate's payload slots: the
+// inverse of thr_frame_card.  The timestamp is split like thrifty_amd.block_data.card_line splits it:
+// round(t * 1e6) to the nearest integer, ties to even, then floor-divided into seconds and microseconds.
+int thr_format_card(const double* timestamps, const int64_t* block_idx, const char* slots, size_t slot_stride,
+                    size_t payload_chars, size_t n, char* out, size_t out_capacity, size_t* out_len) try {
+    if ((!timestamps || !block_idx || !slots) && n) return fail(THR_ERR_ARG, "thr_format_card: null argument");
+    if (!out || !out_len) return fail(THR_ERR_ARG, "thr_format_card: null output");
+    *out_len = 0;
+    if (slot_stride < payload_chars)
+        return fail(THR_ERR_ARG, "thr_format_card: slot stride %zu below the payload length %zu", slot_stride,
+                    payload_chars);
+    const size_t line_max = size_t(THR_CARD_HEADER_MAX) + payload_chars + 1;
+    if (out_capacity / line_max < n)
+        return fail(THR_ERR_ARG, "thr_format_card: %zu bytes for %zu lines, need %zu", out_capacity, n, n * line_max);
+    char* p = out;
+    for (size_t i = 0; i < n; ++i) {
+        if (!(std::fabs(timestamps[i]) < 1e12))
+            return fail(THR_ERR_ARG, "thr_format_card: timestamp %g of line %zu out of range", timestamps[i], i);
+        const long long us = std::llrint(timestamps[i] * 1e6);      // (default rounding mode: ties to even)
+        long long sec = us / 1000000, frac = us % 1000000;
+        if (frac < 0) {
+            frac += 1000000;
+            sec -= 1;
+        }
+        p = put_int(p, sec);
+        *p++ = '.';
+        for (long long d = 100000; d >= 1; d /= 10) *p++ = char('0' + (frac / d) % 10);
+        *p++ = ' ';
+        p = put_int(p, block_idx[i]);
+        *p++ = ' ';
+        std::memcpy(p, slots + i * slot_stride, payload_chars);
+        p += payload_chars;
+        *p++ = '\n';
+    }
+    *out_len = size_t(p - out);
+    return THR_OK;
+} catch (...) {
+    return thr::on_exception("thr_format_card");
+}
+
 
 }  // extern "C"
