@@ -57,7 +57,11 @@ extern "C" {
  *    thr_detect_offsets and thr_debug_stage* refuse a gate handle with THR_ERR_STATE; the queries,
  *    thr_input_window*, thr_set_stream*, thr_sync, thr_profile_*, thr_debug_fft -- the carrier stage's
  *    spectrum -- and thr_compact_device are defined for it) */
-#define THR_ABI_VERSION 10
+/* 11: + template extraction -- the reference's `thrifty template_extract` (template_extract.py:36-58) on
+ *    the device: thr_extract_create / _destroy / _reset, thr_extract_feed / _feed_card / _feed_stream,
+ *    thr_extract_submit_card / _submit_stream, thr_extract_result, thr_run_extract_card /
+ *    thr_run_extract_stream (additions only) */
+#define THR_ABI_VERSION 11
 
 /* status codes */
 #define THR_OK 0
@@ -617,6 +621,78 @@ int thr_run_gate_stream(thr_handle* h, const uint8_t* stream, size_t n_bytes, in
                         const thr_gate_run_opts* opts, thr_gate_run_stats* stats);
 int thr_run_gate_card(thr_handle* h, const char* text, size_t text_len, const thr_gate_run_opts* opts,
                       thr_gate_run_stats* stats);
+
+/*
+ * Template extraction -- replaces the reference's `thrifty template_extract` (template_extract.py:36-58:
+ * iterate Detector(yield_data=True) over a capture, keep the detection with the largest correlation
+ * energy among those with |corr offset| <= max_offset, inverse-transform its shifted spectrum, take
+ * abs(signal[sample : sample + template_len]), scale by 2 / (mean + std), subtract the mean).  The
+ * carrier shift multiplies every sample by a unit-modulus phasor, so abs(ifft(shifted spectrum)) IS the
+ * magnitude of the block's input samples: no spectrum leaves the device.  A thr_extract rides on a
+ * default single-template detector handle (preshift, fastdet, gate and several-template handles:
+ * THR_ERR_ARG).  Every batch goes through the handle's ordinary detect path; behind its kernels, on the
+ * same stream and with no host decision in between, one kernel folds the batch's best qualifying
+ * record into a running best in device memory and one copies that block's input samples aside if the
+ * batch improved the best.
+ *   qualifies: THR_FLAG_CORR set and |corr_offset| <= max_offset;
+ *   best: the largest corr_energy, compared as the float32 the record holds; among equal energies the
+ *     block fed EARLIEST wins (the reference's test is a strict `>`).  The result does not depend on
+ *     how the run is cut into batches.
+ * The handle must outlive the extraction object, which is destroyed first; same single-threaded rule
+ * as the handle.  While no feed is in progress the handle may be used for anything else.
+ *
+ * thr_extract_feed / _feed_card / _feed_stream: thr_detect / thr_detect_card / thr_detect_stream for
+ *   these blocks, plus the fold.  `timestamps` ([n_blocks], or NULL: 0.0) travel with the blocks so
+ *   that the winner's can be reported; `out` (NULL allowed) receives the batch's records as usual.
+ *   After an error the running best may include part of the failed call's blocks: reset.
+ * thr_extract_submit_card / _submit_stream: the same for ONE batch through thr_submit_card /
+ *   thr_submit_stream -- the ticket is the handle's, collected with thr_collect as usual (`timestamps`
+ *   need only live for the call; a stream batch carries one `timestamp`); `out` must not be NULL.
+ * thr_extract_result: waits, runs the extraction kernel over the kept block and copies out: `best` = the
+ *   winning record, `timestamp` its timestamp, template_out[0 .. template_len) the template (float64;
+ *   `capacity` in doubles, too small -> THR_ERR_ARG), `n_qualifying` the number of records that
+ *   qualified.  Any output may be NULL.  Nothing has qualified -> THR_ERR_STATE with a message that says
+ *   so (the reference dies with a TypeError there); *n_qualifying is written in that case too.  The
+ *   state is left as it is: more blocks may be fed and the result taken again.
+ * thr_extract_reset: forget everything fed so far.
+ * Arithmetic of the extraction kernel: u8 samples become float32 as (v - 127.4f) / 128 like everywhere
+ * else, magnitudes, sums, mean and population standard deviation are float64, summed in a fixed tree.
+ */
+typedef struct thr_extract thr_extract;
+int thr_extract_create(thr_handle* h, double max_offset, thr_extract** out);
+void thr_extract_destroy(thr_extract* x);
+int thr_extract_reset(thr_extract* x);
+int thr_extract_feed(thr_extract* x, const void* samples, int format, const int64_t* block_idx,
+                     const double* timestamps, size_t n_blocks, thr_record* out);
+int thr_extract_feed_card(thr_extract* x, const char* text, size_t text_len, const int64_t* payload_off,
+                          const int64_t* block_idx, const double* timestamps, size_t n_blocks, thr_record* out);
+int thr_extract_feed_stream(thr_extract* x, const uint8_t* stream, size_t n_bytes, int64_t first_block_idx,
+                            const double* timestamps, thr_record* out, size_t out_capacity, size_t* n_blocks_out);
+int thr_extract_submit_card(thr_extract* x, const char* text, size_t text_len, const int64_t* payload_off,
+                            const int64_t* block_idx, const double* timestamps, size_t n_blocks, thr_record* out,
+                            uint64_t* ticket);
+int thr_extract_submit_stream(thr_extract* x, const uint8_t* stream, size_t n_bytes, int64_t first_block_idx,
+                              double timestamp, thr_record* out, size_t out_capacity, size_t* n_blocks_out,
+                              uint64_t* ticket);
+int thr_extract_result(thr_extract* x, thr_record* best, double* timestamp, double* template_out, size_t capacity,
+                       uint64_t* n_qualifying);
+/*
+ * The whole-capture loop of an extraction in ONE call, the twin of thr_run_card / thr_run_stream and
+ * built the same way on the entry points above: the calling thread frames batches, keeps up to
+ * THR_MAX_IN_FLIGHT of them submitted with the fold and the keep enqueued behind each, and collects
+ * them in order.  `x` must belong to `h`; the extraction continues from whatever `x` has been fed
+ * (e.g. a raw capture's zero-history lead-in blocks through thr_extract_feed); take the template with
+ * thr_extract_result afterwards.  `opts` / `stats` as for thr_run_card, except that neither an output
+ * descriptor nor a record array is required: no text is formatted unless opts->out_fd >= 0 (then the
+ * .toad lines of the detections are written there, by the calling thread), rec_out receives the
+ * detected records if given.  A THR_FLAG_INDEX_ERROR block ends the run with THR_ERR_INDEX like
+ * thr_run_card (the reference's loop dies there); batches behind it were already in flight, so the
+ * extraction must be reset before it is used again.  An input window around the input is honoured.
+ */
+int thr_run_extract_card(thr_handle* h, const char* text, size_t text_len, const thr_run_opts* opts,
+                         thr_extract* x, thr_run_stats* stats);
+int thr_run_extract_stream(thr_handle* h, const uint8_t* stream, size_t n_bytes, int64_t first_block_idx,
+                           const thr_run_opts* opts, thr_extract* x, thr_run_stats* stats);
 
 /* The settings a handle was created with (`templates` is NULL: the array is not retained). */
 int thr_get_settings(const thr_handle* h, thr_settings* out);

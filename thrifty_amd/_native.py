@@ -24,7 +24,7 @@ FLAG_INT_OFFSET = 8
 FLAG_FIT_UNCONVERGED = 16
 N_KERNEL_SLOTS = 5
 
-ABI_VERSION = 10    # THR_ABI_VERSION of include/thrifty_hip.h
+ABI_VERSION = 11    # THR_ABI_VERSION of include/thrifty_hip.h
 
 EXPORTS = [
     "thr_abi_version", "thr_last_error", "thr_create", "thr_destroy", "thr_detect",
@@ -36,6 +36,9 @@ EXPORTS = [
     "thr_run_card", "thr_run_stream", "thr_get_settings", "thr_input_window_ex", "thr_input_window_release", "thr_detect_offsets", "thr_set_wait_mode", "thr_debug_window", "thr_debug_window_times", "thr_debug_correlate_geom", "thr_debug_sections", "thr_debug_pipe_times", "thr_get_path_info",
     "thr_gate", "thr_gate_stream", "thr_gate_card", "thr_gate_slot_stride", "thr_format_card",
     "thr_run_gate_stream", "thr_run_gate_card",
+    "thr_extract_create", "thr_extract_destroy", "thr_extract_reset", "thr_extract_feed", "thr_extract_feed_card",
+    "thr_extract_feed_stream", "thr_extract_submit_card", "thr_extract_submit_stream", "thr_extract_result",
+    "thr_run_extract_card", "thr_run_extract_stream",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -234,6 +237,19 @@ def load_library():
     lib.thr_run_gate_stream.argtypes = [vp, vp, C.c_size_t, C.c_int64, C.POINTER(ThrGateRunOpts),
                                         C.POINTER(ThrGateRunStats)]
     lib.thr_run_gate_card.argtypes = [vp, vp, C.c_size_t, C.POINTER(ThrGateRunOpts), C.POINTER(ThrGateRunStats)]
+    lib.thr_extract_create.argtypes = [vp, C.c_double, C.POINTER(vp)]
+    lib.thr_extract_destroy.argtypes = [vp]
+    lib.thr_extract_destroy.restype = None
+    lib.thr_extract_reset.argtypes = [vp]
+    lib.thr_extract_feed.argtypes = [vp, vp, C.c_int, vp, vp, C.c_size_t, vp]
+    lib.thr_extract_feed_card.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp]
+    lib.thr_extract_feed_stream.argtypes = [vp, vp, C.c_size_t, C.c_int64, vp, vp, C.c_size_t, szp]
+    lib.thr_extract_submit_card.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp, u64p]
+    lib.thr_extract_submit_stream.argtypes = [vp, vp, C.c_size_t, C.c_int64, C.c_double, vp, C.c_size_t, szp, u64p]
+    lib.thr_extract_result.argtypes = [vp, vp, C.POINTER(C.c_double), vp, C.c_size_t, u64p]
+    lib.thr_run_extract_card.argtypes = [vp, vp, C.c_size_t, C.POINTER(ThrRunOpts), vp, C.POINTER(ThrRunStats)]
+    lib.thr_run_extract_stream.argtypes = [vp, vp, C.c_size_t, C.c_int64, C.POINTER(ThrRunOpts), vp,
+                                           C.POINTER(ThrRunStats)]
     _lib = lib
     return lib
 
@@ -929,3 +945,115 @@ class Engine(object):
                                                             template_id, off.ctypes.data if off is not None else None,
                                                             xhat.ctypes.data, corr.ctypes.data))
         return xhat, corr
+
+
+class Extraction(object):
+    """A template extraction riding on an Engine (thr_extract_*): feed it the blocks of a capture in any
+    batching, through any of the engine's input forms, then take `result()`.  The engine must be the
+    default single-template detector and must stay open while this object is."""
+
+    def __init__(self, engine, max_offset=0.2):
+        self._lib, self._eng = engine._lib, engine
+        self.max_offset = float(max_offset)
+        x = C.c_void_p()
+        _check(self._lib, self._lib.thr_extract_create(engine._h, self.max_offset, C.byref(x)))
+        self._x = x
+
+    def close(self):
+        if getattr(self, "_x", None):
+            if getattr(self._eng, "_h", None):      # (an engine that is gone took the device state with it)
+                self._lib.thr_extract_destroy(self._x)
+            self._x = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # noqa: BLE001
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def reset(self):
+        _check(self._lib, self._lib.thr_extract_reset(self._x))
+
+    @staticmethod
+    def _stamps(timestamps, nb):
+        if timestamps is None:
+            return None, None
+        ts = np.ascontiguousarray(np.asarray(timestamps, dtype=np.float64))
+        assert ts.shape == (nb,)
+        return ts, ts.ctypes.data
+
+    def feed(self, blocks, timestamps=None, block_idx=None):
+        """thr_extract_feed: u8 [B, 2N] or complex64 [B, N] blocks -> the batch's records [B]."""
+        eng = self._eng
+        a, fmt = eng._as_input(blocks)
+        nb = a.shape[0]
+        out = np.zeros(nb, dtype=RECORD_DTYPE)
+        idx, idx_p = eng._idx_ptr(block_idx, nb)
+        ts, ts_p = self._stamps(timestamps, nb)
+        _check(self._lib, self._lib.thr_extract_feed(self._x, a.ctypes.data, fmt, idx_p, ts_p, nb, out.ctypes.data))
+        return out
+
+    def feed_card(self, text, payload_off, timestamps=None, block_idx=None):
+        """thr_extract_feed_card: .card text + payload offsets (see Engine.detect_card) -> records [B]."""
+        buf = np.frombuffer(text, dtype=np.uint8)
+        off = np.ascontiguousarray(np.asarray(payload_off, dtype=np.int64))
+        nb = off.shape[0]
+        out = np.zeros(nb, dtype=RECORD_DTYPE)
+        idx, idx_p = self._eng._idx_ptr(block_idx, nb)
+        ts, ts_p = self._stamps(timestamps, nb)
+        _check(self._lib, self._lib.thr_extract_feed_card(self._x, buf.ctypes.data, buf.size, off.ctypes.data, idx_p,
+                                                          ts_p, nb, out.ctypes.data))
+        return out
+
+    def feed_stream(self, stream, first_block_idx=0, timestamps=None):
+        """thr_extract_feed_stream: raw u8 I/Q bytes, overlapping blocks framed on the device (see
+        Engine.detect_stream) -> records [n_whole_blocks]."""
+        eng = self._eng
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        stride = 2 * (eng.block_len - eng.history_len)
+        nb = 0 if buf.size < 2 * eng.block_len else (buf.size - 2 * eng.block_len) // stride + 1
+        out = np.zeros(nb, dtype=RECORD_DTYPE)
+        ts, ts_p = self._stamps(timestamps, nb)
+        got = C.c_size_t(0)
+        _check(self._lib, self._lib.thr_extract_feed_stream(self._x, buf.ctypes.data if buf.size else None, buf.size,
+                                                            int(first_block_idx), ts_p, out.ctypes.data, max(1, nb),
+                                                            C.byref(got)))
+        assert got.value == nb
+        return out
+
+    def run(self, data, card=True, first_block_idx=0, timestamp=None, batch_blocks=0, out_fd=None, rxid=None,
+            rec_out=None):
+        """thr_run_extract_card / thr_run_extract_stream: the whole input `data` (bytes-like: the mapped
+        .card file, or a raw stream whose first 2 * block_len bytes are block `first_block_idx`) inside
+        the library.  -> the statistics as a dict (`index_error`: the run ended at the reference's
+        IndexError block)."""
+        eng = self._eng
+        buf = np.frombuffer(data, dtype=np.uint8)
+        o = eng._run_opts(out_fd, rxid, False, 0, batch_blocks, rec_out, timestamp)
+        st = ThrRunStats()
+        ptr = buf.ctypes.data if buf.size else None
+        if card:
+            rc = self._lib.thr_run_extract_card(eng._h, ptr, buf.size, C.byref(o), self._x, C.byref(st))
+        else:
+            rc = self._lib.thr_run_extract_stream(eng._h, ptr, buf.size, int(first_block_idx), C.byref(o), self._x,
+                                                  C.byref(st))
+        del buf
+        return eng._run_done(rc, st)
+
+    def result(self, template_len):
+        """thr_extract_result -> (record, timestamp, template float64[template_len], n_qualifying).
+        ValueError (with the library's sentence) if no record has qualified."""
+        rec = np.zeros(1, dtype=RECORD_DTYPE)
+        ts, n = C.c_double(0), C.c_uint64(0)
+        out = np.empty(int(template_len), dtype=np.float64)
+        rc = self._lib.thr_extract_result(self._x, rec.ctypes.data, C.byref(ts), out.ctypes.data, out.size, C.byref(n))
+        if rc == ERR_STATE:
+            raise ValueError(self._lib.thr_last_error().decode())
+        _check(self._lib, rc)
+        return rec[0], ts.value, out, n.value

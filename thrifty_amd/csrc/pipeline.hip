@@ -2,6 +2,7 @@
 #include "host_internal.hpp"
 
 #include "card_gate.hpp"
+#include "template_extract.hpp"
 
 namespace thr {
 namespace host {
@@ -503,6 +504,8 @@ int chunk_samples(thr_handle* h, int b, const void* src, int format, size_t blk_
     rc = run_batch(h, p.d_in[b], format, p.d_idx[b], int(nb), p.d_rec[b], nullptr, nullptr, nullptr, 0,
                    false, stride);
     if (rc != THR_OK) return rc;
+    // (a template extraction in progress folds the batch's records and keeps the winner's samples here)
+    if ((rc = extract_after_chunk(h, b, p.d_in[b], format, stride, first, nb)) != THR_OK) return rc;
     lap(3);
     rc = pipe_records_enqueued(h, b, dst, nb * size_t(h->cfg.n_templates), first, false);
     lap(4);
@@ -555,6 +558,7 @@ int chunk_card(thr_handle* h, int b, const char* text, size_t text_len, const in
     rc = run_batch(h, p.d_in[b], THR_IN_U8, p.d_idx[b], int(nb), p.d_rec[b], nullptr, nullptr, nullptr,
                    0, false);
     if (rc != THR_OK) return rc;
+    if ((rc = extract_after_chunk(h, b, p.d_in[b], THR_IN_U8, 0, first, nb)) != THR_OK) return rc;
     lap(3);
     rc = pipe_records_enqueued(h, b, dst, nb * size_t(h->cfg.n_templates), first, true);
     lap(4);
