@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import conftest
+from extract_ref import TOL, cuts, same
 from thrifty_amd import _native as F
 from thrifty_amd import block_data, fastdet, synth, template_extract
 from thrifty_amd.detect import Detector, DetectorSettings
@@ -22,7 +23,6 @@ def load_golden(name):
 
 
 FIXTURES = ["extract_1024", "extract_2048", "extract_16384"]
-TOL = 1e-12
 _engines = {}
 
 
@@ -44,17 +44,6 @@ def settings_of(g, template=None):
                             corr_thresh=tuple(g["corr_thresh"]))
 
 
-def cuts(total, sizes):
-    """Batch boundaries: `sizes` is one int (batches of that size) or the list of sizes."""
-    sizes = [sizes] * -(-total // sizes) if isinstance(sizes, int) else sizes
-    at, out = 0, []
-    for s in sizes:
-        out.append((at, min(total, at + s)))
-        at += s
-    assert out[-1][1] == total
-    return out
-
-
 def run(name, blocks, idx, stamps, sizes=48, max_offset=0.2):
     """Feed `blocks` in batches -> (record, timestamp, template, n_qualifying)."""
     g = load_golden(name)
@@ -63,11 +52,6 @@ def run(name, blocks, idx, stamps, sizes=48, max_offset=0.2):
             recs = x.feed(blocks[lo:hi], stamps[lo:hi], idx[lo:hi])
             assert np.array_equal(recs["block_idx"], idx[lo:hi])
         return x.result(len(g["template"]))
-
-
-def same(a, b):
-    """Two results of the engine: identical record, bit-identical template, same count."""
-    return a[0].tobytes() == b[0].tobytes() and a[2].tobytes() == b[2].tobytes() and a[3] == b[3]
 
 
 # ------------------------------------------------------------------ 1. parity with the reference
