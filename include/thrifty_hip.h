@@ -60,7 +60,9 @@ extern "C" {
 /* 11: + template extraction -- the reference's `thrifty template_extract` (template_extract.py:36-58) on
  *    the device: thr_extract_create / _destroy / _reset, thr_extract_feed / _feed_card / _feed_stream,
  *    thr_extract_submit_card / _submit_stream, thr_extract_result, thr_run_extract_card /
- *    thr_run_extract_stream (additions only) */
+ *    thr_run_extract_stream (additions only)
+ *    within 11, a pure addition (no existing entry point or struct changes, the number stays):
+ *    + thr_match / thr_debug_match_times -- the reference's `thrifty match` (matchmaker.py:17-79) */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -828,6 +830,34 @@ int thr_identify(int device_id, size_t n, const int32_t* rxid, const int32_t* bl
                  const double* timestamp, const int32_t* carrier_bin, const double* carrier_offset,
                  const double* energy, const thr_freq_range* map, size_t n_map, int32_t* txid_out,
                  uint8_t* keep_out, int64_t* kept_order_out, size_t* n_kept_out);
+
+/*
+ * match: detections of one transmission seen by several receivers (thrifty/matchmaker.py:17-79).
+ * Columns in, columns out (host pointers, synchronous, handle-free like thr_identify); the detections
+ * are in timestamp order.
+ *  1. Groups, per txid: in input order the first detection no group holds yet is a LEADER i; its group
+ *     is i and every later detection j of that txid with not (timestamp[j] > timestamp[i] + window)
+ *     -- float64, equality stays inside; the next leader is the first detection of the txid behind it.
+ *  2. One entry per receiver: inside a group, in input order, a receiver's first detection is its
+ *     entry; every further detection j of that receiver records the collision (entry so far, j) and
+ *     the entry becomes `entry if energy[entry] > energy[j] else j` (equal energies and a NaN on
+ *     either side: the later one).
+ *  3. Per leader in ascending input index: the group's entries in the order in which their receivers
+ *     first appeared in the group (dict order of Python 3.7+).  At least `min_match` entries: a match,
+ *     match_idx_out[match_ptr_out[m] .. match_ptr_out[m + 1]); fewer: the LEADER's index alone goes to
+ *     miss_out.  collision_out[c] = {entry so far, j}, ordered by (leader, j).
+ * match_ptr_out holds n + 1, match_idx_out and miss_out n, collision_out 2 * n values; the counts say
+ * how many were written.  n == 0: THR_OK, three zero counts.  The one deviation from the reference:
+ * timestamps that decrease somewhere or hold a NaN (the reference's result then depends on the order)
+ * are refused with THR_ERR_ARG and a message naming the first such detection.
+ */
+int thr_match(int device_id, size_t n, const int32_t* rxid, const int32_t* txid,
+              const double* timestamp, const double* energy, double window, int min_match,
+              int64_t* match_ptr_out, int64_t* match_idx_out, size_t* n_matches_out,
+              int64_t* miss_out, size_t* n_misses_out,
+              int64_t* collision_out, size_t* n_collisions_out);
+/* Milliseconds of the calling thread's last thr_match: {copies in, kernels, copies out} (HIP events). */
+int thr_debug_match_times(double* ms_out /* [3] */);
 
 #ifdef __cplusplus
 }

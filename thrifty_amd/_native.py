@@ -39,6 +39,7 @@ EXPORTS = [
     "thr_extract_create", "thr_extract_destroy", "thr_extract_reset", "thr_extract_feed", "thr_extract_feed_card",
     "thr_extract_feed_stream", "thr_extract_submit_card", "thr_extract_submit_stream", "thr_extract_result",
     "thr_run_extract_card", "thr_run_extract_stream",
+    "thr_match", "thr_debug_match_times",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -250,6 +251,8 @@ def load_library():
     lib.thr_run_extract_card.argtypes = [vp, vp, C.c_size_t, C.POINTER(ThrRunOpts), vp, C.POINTER(ThrRunStats)]
     lib.thr_run_extract_stream.argtypes = [vp, vp, C.c_size_t, C.c_int64, C.POINTER(ThrRunOpts), vp,
                                            C.POINTER(ThrRunStats)]
+    lib.thr_match.argtypes = [C.c_int, C.c_size_t, vp, vp, vp, vp, C.c_double, C.c_int, vp, vp, szp, vp, szp, vp, szp]
+    lib.thr_debug_match_times.argtypes = [C.POINTER(C.c_double)]
     _lib = lib
     return lib
 
@@ -370,6 +373,41 @@ def identify(rxid, block, timestamp, carrier_bin, carrier_offset, energy, freq_r
                                  txid.ctypes.data, keep.ctypes.data, order.ctypes.data,
                                  C.byref(n_kept)))
     return txid, keep.astype(bool), order[:n_kept.value]
+
+
+MATCH_WORKGROUP = 256      # kBlock of csrc/match.hip: the workgroup size of every matcher kernel
+
+
+def match(rxid, txid, timestamp, energy, window, min_match=2, device_id=0):
+    """thr_match on columns of detections in timestamp order -> (match_ptr int64[m + 1],
+    match_idx int64[match_ptr[-1]], misses int64[k], collisions int64[c, 2]): match m is
+    match_idx[match_ptr[m]:match_ptr[m + 1]].  ValueError if the timestamps decrease or hold a NaN."""
+    lib = load_library()
+    n = len(rxid)
+    cols = [np.ascontiguousarray(rxid, dtype=np.int32), np.ascontiguousarray(txid, dtype=np.int32),
+            np.ascontiguousarray(timestamp, dtype=np.float64), np.ascontiguousarray(energy, dtype=np.float64)]
+    assert all(c.ndim == 1 and len(c) == n for c in cols)
+    ptr = np.zeros(n + 1, dtype=np.int64)
+    idx = np.zeros(n, dtype=np.int64)
+    miss = np.zeros(n, dtype=np.int64)
+    coll = np.zeros((n, 2), dtype=np.int64)
+    n_match, n_miss, n_coll = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    rc = lib.thr_match(int(device_id), n, *[c.ctypes.data for c in cols], float(window), int(min_match),
+                       ptr.ctypes.data, idx.ctypes.data, C.byref(n_match), miss.ctypes.data, C.byref(n_miss),
+                       coll.ctypes.data, C.byref(n_coll))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    ptr = ptr[:n_match.value + 1]
+    return ptr, idx[:int(ptr[-1])], miss[:n_miss.value], coll[:n_coll.value]
+
+
+def match_times():
+    """{copies in, kernels, copies out} of this thread's last match(), milliseconds (HIP events)."""
+    lib = load_library()
+    ms = (C.c_double * 3)()
+    _check(lib, lib.thr_debug_match_times(ms))
+    return tuple(ms)
 
 
 class HostPin(object):
