@@ -62,7 +62,8 @@ extern "C" {
  *    thr_extract_submit_card / _submit_stream, thr_extract_result, thr_run_extract_card /
  *    thr_run_extract_stream (additions only)
  *    within 11, a pure addition (no existing entry point or struct changes, the number stays):
- *    + thr_match / thr_debug_match_times -- the reference's `thrifty match` (matchmaker.py:17-79) */
+ *    + thr_match / thr_debug_match_times -- the reference's `thrifty match` (matchmaker.py:17-79)
+ *    + thr_tdoa / thr_debug_tdoa_times -- the reference's `thrifty tdoa` (tdoa_est.py:43-105, 234-303) */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -858,6 +859,54 @@ int thr_match(int device_id, size_t n, const int32_t* rxid, const int32_t* txid,
               int64_t* collision_out, size_t* n_collisions_out);
 /* Milliseconds of the calling thread's last thr_match: {copies in, kernels, copies out} (HIP events). */
 int thr_debug_match_times(double* ms_out /* [3] */);
+
+/*
+ * tdoa: time differences of arrival of mobile transmissions, the receivers' clocks synchronised
+ * through beacon matches (thrifty/tdoa_est.py:43-105 and 234-303, stat_tools.py:8-41).  Host pointers,
+ * synchronous, handle-free like thr_match.
+ * In: detection columns (rx = DENSE receiver index 0 .. n_rx - 1, timestamp, soa, corr energy and
+ * noise); the matches as CSR (match_ptr[n_matches + 1], match_idx), as thr_match returns them;
+ * match_beacon[m] = index 0 .. n_beacons - 1 of the beacon that sent match m, -1 for a mobile match;
+ * dist[n_rx][n_beacons] = receiver-to-beacon distances; window (s), sample_rate (Hz), deg 1..3.
+ *  1. Every beacon match, in match order, appends each of its itertools.combinations(match, 2)
+ *     (det0 = the lower receiver) to the list of its receiver pair.  The lists stay in match order
+ *     (the reference's sort with a never-negative cmp is a no-op).
+ *  2. Every combination of every mobile match is a TASK, in match then combination order: Python's
+ *     bisect_left(list, t0 - window) / bisect_right(list, t0 + window) on the list's det0 timestamps
+ *     -- the same loops, so an unsorted list gives what Python gives; with more than one pair in the
+ *     window the median / MAD mask of stat_tools.is_outlier on soa0 - soa1 (float64, operation for
+ *     operation); fewer than deg + 1 pairs kept: a failure; a least-squares polynomial of soa0 on
+ *     soa1 + (dist[rx0][b] - dist[rx1][b]) / 2.997e8 * sample_rate, fitted in a centred and scaled
+ *     variable; tdoa = (soa0 - fit(soa1)) / sample_rate of the task's own detections;
+ *     |tdoa| >= 30e3 / 2.997e8: a failure.
+ *  3. row r: row_rx_out[2r..] = {rx0, rx1} (dense), row_det_out[2r..] = {det0, det1},
+ *     row_val_out[3r..] = {tdoa [s], snr, model_quality}, in task order.  Group g (a mobile match with
+ *     at least one row, in match order): group_id_out[g] = its index in the matches, rows
+ *     group_ptr_out[g] .. group_ptr_out[g + 1].  fail_out[2f..] = {det0, det1} in task order.
+ *     n_window_out / n_kept_out (either may be null): per task the pairs in the window and the pairs
+ *     the mask kept.
+ * Sizes: the caller passes n_tasks = the sum of k (k - 1) / 2 over the mobile matches (k = entries of
+ * the match); row_rx_out, row_det_out, fail_out hold 2 * n_tasks, row_val_out 3 * n_tasks, n_window_out
+ * and n_kept_out n_tasks, group_id_out n_matches and group_ptr_out n_matches + 1 values; the counts say
+ * how many were written (n_tasks == 0: THR_OK with three zero counts once the arguments and device_id
+ * have been checked; nothing is launched).  Windows of up to 256 pairs are ranked from LDS; longer
+ * ones are recomputed from the columns inside the rank count, whose cost grows with the square of the
+ * window, so a window of thousands of pairs is correct but slow.  The beacon of a pair is its match's
+ * (match_beacon); the reference reads it off the pair's det0, which is the same for matches of one
+ * txid, as thr_match makes them.  Deviations from the reference: a receiver pair without a list is an empty
+ * window (reference: KeyError); kept abscissae with fewer than deg + 1 distinct values are a failure
+ * (reference: LAPACK's minimum-norm solution); a match with two detections of one receiver, an index
+ * out of range or an n_tasks that is not the sum above: THR_ERR_ARG before anything is launched.
+ */
+int thr_tdoa(int device_id, size_t n_det, const int32_t* rx, const double* timestamp, const double* soa,
+             const double* energy, const double* noise, size_t n_matches, const int64_t* match_ptr,
+             const int64_t* match_idx, const int32_t* match_beacon, int n_rx, int n_beacons,
+             const double* dist, double window, double sample_rate, int deg, size_t n_tasks,
+             int32_t* row_rx_out, int64_t* row_det_out, double* row_val_out, size_t* n_rows_out,
+             int64_t* group_id_out, int64_t* group_ptr_out, size_t* n_groups_out,
+             int64_t* fail_out, size_t* n_fail_out, int32_t* n_window_out, int32_t* n_kept_out);
+/* Milliseconds of the calling thread's last thr_tdoa: {copies in, kernels, copies out} (HIP events). */
+int thr_debug_tdoa_times(double* ms_out /* [3] */);
 
 #ifdef __cplusplus
 }

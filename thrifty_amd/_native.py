@@ -40,6 +40,7 @@ EXPORTS = [
     "thr_extract_feed_stream", "thr_extract_submit_card", "thr_extract_submit_stream", "thr_extract_result",
     "thr_run_extract_card", "thr_run_extract_stream",
     "thr_match", "thr_debug_match_times",
+    "thr_tdoa", "thr_debug_tdoa_times",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -253,6 +254,9 @@ def load_library():
                                            C.POINTER(ThrRunStats)]
     lib.thr_match.argtypes = [C.c_int, C.c_size_t, vp, vp, vp, vp, C.c_double, C.c_int, vp, vp, szp, vp, szp, vp, szp]
     lib.thr_debug_match_times.argtypes = [C.POINTER(C.c_double)]
+    lib.thr_tdoa.argtypes = ([C.c_int, C.c_size_t] + [vp] * 5 + [C.c_size_t, vp, vp, vp, C.c_int, C.c_int, vp,
+                             C.c_double, C.c_double, C.c_int, C.c_size_t, vp, vp, vp, szp, vp, vp, szp, vp, szp, vp, vp])
+    lib.thr_debug_tdoa_times.argtypes = [C.POINTER(C.c_double)]
     _lib = lib
     return lib
 
@@ -1095,3 +1099,58 @@ class Extraction(object):
             raise ValueError(self._lib.thr_last_error().decode())
         _check(self._lib, rc)
         return rec[0], ts.value, out, n.value
+
+
+TDOA_TASKS_PER_WORKGROUP = 4    # kWaves of csrc/tdoa.hip: one wavefront per task, four to a workgroup
+TDOA_LDS_WINDOW = 256           # kLdsWindow: longer windows are ranked from the columns instead of LDS
+
+
+def tdoa(rx, timestamp, soa, energy, noise, match_ptr, match_idx, match_beacon, dist, window, sample_rate,
+         deg=2, device_id=0):
+    """thr_tdoa on detection columns (rx: dense receiver index), the matches as CSR, the beacon index of
+    every match (-1: mobile) and dist[receiver][beacon] -> dict of row_rx int32[r, 2] (dense),
+    row_det int64[r, 2], tdoa / snr / model_quality float64[r], group_id int64[g], group_ptr int64[g + 1],
+    failures int64[f, 2], n_window / n_kept int32[tasks].  ValueError for what thr_tdoa refuses."""
+    lib = load_library()
+    cols = [np.ascontiguousarray(rx, dtype=np.int32)] + [np.ascontiguousarray(c, dtype=np.float64)
+                                                          for c in (timestamp, soa, energy, noise)]
+    if len(set(len(c) for c in cols)) != 1:
+        raise ValueError("tdoa: the detection columns differ in length")
+    ptr = np.ascontiguousarray(match_ptr, dtype=np.int64)
+    idx = np.ascontiguousarray(match_idx, dtype=np.int64)
+    beacon = np.ascontiguousarray(match_beacon, dtype=np.int32)
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    if ptr.ndim != 1 or len(ptr) != len(beacon) + 1 or dist.ndim != 2 or (len(ptr) and int(ptr[-1]) != len(idx)):
+        raise ValueError("tdoa: match_ptr, match_idx, match_beacon or dist have the wrong shape")
+    k = np.diff(ptr)
+    n_tasks = int((k * (k - 1) // 2)[beacon < 0].sum())
+    n_matches = len(beacon)
+    row_rx = np.zeros((n_tasks, 2), dtype=np.int32)
+    row_det = np.zeros((n_tasks, 2), dtype=np.int64)
+    row_val = np.zeros((n_tasks, 3), dtype=np.float64)
+    fail = np.zeros((n_tasks, 2), dtype=np.int64)
+    group_id = np.zeros(n_matches, dtype=np.int64)
+    group_ptr = np.zeros(n_matches + 1, dtype=np.int64)
+    n_window = np.zeros(n_tasks, dtype=np.int32)
+    n_kept = np.zeros(n_tasks, dtype=np.int32)
+    n_rows, n_groups, n_fail = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    rc = lib.thr_tdoa(int(device_id), len(cols[0]), *[c.ctypes.data for c in cols], n_matches, ptr.ctypes.data,
+                      idx.ctypes.data, beacon.ctypes.data, dist.shape[0], dist.shape[1], dist.ctypes.data,
+                      float(window), float(sample_rate), int(deg), n_tasks, row_rx.ctypes.data, row_det.ctypes.data,
+                      row_val.ctypes.data, C.byref(n_rows), group_id.ctypes.data, group_ptr.ctypes.data,
+                      C.byref(n_groups), fail.ctypes.data, C.byref(n_fail), n_window.ctypes.data, n_kept.ctypes.data)
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    r, g = n_rows.value, n_groups.value
+    return {"row_rx": row_rx[:r], "row_det": row_det[:r], "tdoa": row_val[:r, 0].copy(), "snr": row_val[:r, 1].copy(),
+            "model_quality": row_val[:r, 2].copy(), "group_id": group_id[:g], "group_ptr": group_ptr[:g + 1],
+            "failures": fail[:n_fail.value], "n_window": n_window, "n_kept": n_kept}
+
+
+def tdoa_times():
+    """{copies in, kernels, copies out} of this thread's last tdoa(), milliseconds (HIP events)."""
+    lib = load_library()
+    ms = (C.c_double * 3)()
+    _check(lib, lib.thr_debug_tdoa_times(ms))
+    return tuple(ms)

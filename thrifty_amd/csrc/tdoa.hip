@@ -1,0 +1,735 @@
+// tdoa on the device (reference thrifty/tdoa_est.py:43-105, 234-303; thrifty/stat_tools.py:8-41): time
+// differences of arrival of mobile transmissions, the receivers' clocks tied together by beacon matches.
+//   1. every beacon match expands into its k(k-1)/2 detection pairs (det0 = the lower receiver); the pairs
+//      go, in match order, into one list per receiver pair (a stable sort by the pair key: histogram,
+//      exclusive scan, scatter -- hipCUB's radix sort over the key's bits);
+//   2. every mobile match expands the same way into TASKS; one wavefront runs one task: Python's two
+//      bisections on the list's det0 timestamps (sorted or not), the median / MAD outlier mask on
+//      soa0 - soa1 in the reference's float64 operations, a least-squares polynomial of soa0 on
+//      soa1 + beacon_sdoa over the kept pairs, and the row;
+//   3. rows, failures and the group table are compacted into the reference's orders by prefix sums.
+// The fit is not LAPACK's: it runs in u = (x - mean) / max|x - mean| on y - mean(y) (normal equations of
+// size deg + 1, partial pivoting, Horner in u), which keeps the digits the raw Vandermonde of abscissae
+// near 1e9..1e11 loses.  Everything that decides WHICH pairs are used is the reference's arithmetic.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/thrifty_hip.h"
+
+// the outlier mask must equal numpy's bit for bit: no a * b + c may become an fma in this file (the
+// build also passes -ffp-contract=off for it, thrifty_amd/build.py: PER_FILE_FLAGS)
+#pragma clang fp contract(off)
+
+namespace thr {
+int fail_msg(int code, const char* fmt, ...);
+int on_exception(const char* who) noexcept;  // handle.hip
+}
+
+namespace {
+
+constexpr int kBlock = 256;               // workgroup size of every kernel here
+constexpr int kWave = 64;                 // one task per wavefront
+constexpr int kWaves = kBlock / kWave;    // tasks per workgroup of k_estimate (_native.TDOA_TASKS_PER_WORKGROUP)
+constexpr int kLdsWindow = 256;           // windows up to this many pairs are staged in LDS (_native.TDOA_LDS_WINDOW)
+constexpr int kMaxReceivers = 1024;       // pair key = rx0 * R + rx1 in 20 bits
+constexpr double kSpeedOfLight = 2.997e8;           // the reference's constant (tdoa_est.py:25)
+constexpr double kMaxTdoa = 30e3 / kSpeedOfLight;   // tdoa_est.py:26
+
+__global__ void k_iota(unsigned* idx, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) idx[i] = unsigned(i);
+}
+// (energy / noise)**2 of every detection: snr and model_quality are means of these
+__global__ void k_quality(const double* __restrict__ energy, const double* __restrict__ noise, int n,
+                          double* __restrict__ q) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double r = energy[i] / noise[i];
+    q[i] = r * r;
+}
+// pairs of match m: beacon pairs or tasks; slot n_matches holds 0 so that the exclusive sums end in the totals
+__global__ void k_pair_counts(const long long* __restrict__ ptr, const int* __restrict__ beacon, int n_matches,
+                              unsigned* __restrict__ n_beacon_pairs, unsigned* __restrict__ n_tasks) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m > n_matches) return;
+    unsigned pairs = 0;
+    bool is_beacon = false;
+    if (m < n_matches) {
+        const unsigned k = unsigned(ptr[m + 1] - ptr[m]);
+        pairs = k * (k - 1u) / 2u;
+        if (k == 0) pairs = 0;
+        is_beacon = beacon[m] >= 0;
+    }
+    n_beacon_pairs[m] = is_beacon ? pairs : 0u;
+    n_tasks[m] = is_beacon ? 0u : pairs;
+}
+// itertools.combinations(match, 2) in its order, det0 = the detection of the lower receiver
+__global__ void k_expand(const long long* __restrict__ ptr, const long long* __restrict__ idx,
+                         const int* __restrict__ beacon, const int* __restrict__ rx, int n_matches, int n_rx,
+                         const unsigned* __restrict__ beacon_base, const unsigned* __restrict__ task_base,
+                         unsigned* __restrict__ pair_key, int* __restrict__ pair_det0, int* __restrict__ pair_det1,
+                         int* __restrict__ pair_beacon, int* __restrict__ task_det0, int* __restrict__ task_det1) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_matches) return;
+    const long long first = ptr[m];
+    const int k = int(ptr[m + 1] - first), b = beacon[m];
+    size_t slot = b >= 0 ? beacon_base[m] : task_base[m];
+    for (int i = 0; i < k; ++i)
+        for (int j = i + 1; j < k; ++j, ++slot) {
+            int d0 = int(idx[first + i]), d1 = int(idx[first + j]);
+            if (rx[d0] > rx[d1]) {
+                const int t = d0;
+                d0 = d1;
+                d1 = t;
+            }
+            if (b >= 0) {
+                pair_key[slot] = unsigned(rx[d0]) * unsigned(n_rx) + unsigned(rx[d1]);
+                pair_det0[slot] = d0;
+                pair_det1[slot] = d1;
+                pair_beacon[slot] = b;
+            } else {
+                task_det0[slot] = d0;
+                task_det1[slot] = d1;
+            }
+        }
+}
+// the columns the estimator reads, in bucket order (perm = the stable sort of the pairs by key)
+__global__ void k_gather_pairs(const unsigned* __restrict__ perm, const int* __restrict__ pair_det0,
+                               const int* __restrict__ pair_det1, const int* __restrict__ pair_beacon,
+                               const double* __restrict__ ts, const double* __restrict__ soa,
+                               const double* __restrict__ q, int n_pairs, double* __restrict__ b_ts,
+                               double* __restrict__ b_soa0, double* __restrict__ b_soa1, double* __restrict__ b_q0,
+                               double* __restrict__ b_q1, int* __restrict__ b_beacon) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs) return;
+    const unsigned src = perm[p];
+    const int d0 = pair_det0[src], d1 = pair_det1[src];
+    b_ts[p] = ts[d0];
+    b_soa0[p] = soa[d0];
+    b_soa1[p] = soa[d1];
+    b_q0[p] = q[d0];
+    b_q1[p] = q[d1];
+    b_beacon[p] = pair_beacon[src];
+}
+// bucket_ptr[key] = first position of `key` in the sorted keys (n_keys + 1 entries, the last one n_pairs)
+__global__ void k_bucket_bounds(const unsigned* __restrict__ key_sorted, int n_pairs, int n_keys,
+                                unsigned* __restrict__ bucket_ptr) {
+    const int key = blockIdx.x * blockDim.x + threadIdx.x;
+    if (key > n_keys) return;
+    int lo = 0, hi = n_pairs;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (key_sorted[mid] < unsigned(key))
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    bucket_ptr[key] = unsigned(lo);
+}
+
+// ---------------------------------------------------------------- the estimator: one wavefront per task
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);  // commutative: every lane the same bits
+    return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+    for (int o = kWave / 2; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, kWave));
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+    for (int o = kWave / 2; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, kWave));
+    return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+    return v;
+}
+// the value of the one lane that holds it (`mine`), unchanged bits; 0 if no lane does (NaN input)
+__device__ __forceinline__ double wave_pick(double v, bool mine) {
+    const unsigned long long who = __ballot(mine);
+    if (who == 0) return 0.0;
+    return __shfl(v, __ffsll((long long)who) - 1, kWave);
+}
+// LDS written by some lanes of this wavefront, read by others: order the accesses, nothing more (the
+// wavefronts of a workgroup run different tasks and never meet at a workgroup barrier)
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The window of one task: pairs [0, n) of a bucket.  value(i) is sdoa_i = soa0 - soa1 (deviation ==
+// false) or sqrt((sdoa_i - median)**2) (deviation == true), from LDS when the window was staged there
+// and recomputed from the columns otherwise -- the same float64 operations either way.
+struct Window {
+    const double* soa0;
+    const double* soa1;
+    const double* lds;  // null: not staged
+    int n;
+    bool deviation;
+    double median;
+    __device__ __forceinline__ double compute(int i) const {
+        double v = soa0[i] - soa1[i];
+        if (deviation) {
+            const double c = v - median;
+            v = __dsqrt_rn(c * c);
+        }
+        return v;
+    }
+    __device__ __forceinline__ double value(int i) const { return lds ? lds[i] : compute(i); }
+};
+// np.median: the element of rank (n - 1) / 2, or the mean of the two middle ones.  Every element's rank
+// is counted against all others (ties broken by position, so the ranks are a permutation): exact for
+// every n; lanes stride over the elements, so a window longer than a wavefront takes several trips.
+__device__ double wave_median(const Window& w, int lane) {
+    const int r_lo = (w.n - 1) / 2, r_hi = w.n / 2;
+    double v_lo = 0.0, v_hi = 0.0;
+    bool has_lo = false, has_hi = false;
+    for (int i = lane; i < w.n; i += kWave) {
+        const double v = w.value(i);
+        int rank = 0;
+        for (int j = 0; j < w.n; ++j) {
+            const double o = w.value(j);
+            rank += (o < v || (o == v && j < i)) ? 1 : 0;
+        }
+        if (rank == r_lo) {
+            v_lo = v;
+            has_lo = true;
+        }
+        if (rank == r_hi) {
+            v_hi = v;
+            has_hi = true;
+        }
+    }
+    v_lo = wave_pick(v_lo, has_lo);
+    if (r_lo == r_hi) return v_lo;
+    v_hi = wave_pick(v_hi, has_hi);
+    return (v_lo + v_hi) / 2.0;
+}
+
+template <int DEG>
+__global__ __launch_bounds__(kBlock) void k_estimate(
+    const int* __restrict__ task_det0, const int* __restrict__ task_det1, const int* __restrict__ rx,
+    const double* __restrict__ ts, const double* __restrict__ soa, const double* __restrict__ q,
+    const unsigned* __restrict__ bucket_ptr, int n_rx, int n_beacons, const double* __restrict__ b_ts,
+    const double* __restrict__ b_soa0, const double* __restrict__ b_soa1, const double* __restrict__ b_q0,
+    const double* __restrict__ b_q1, const int* __restrict__ b_beacon, const double* __restrict__ dist,
+    double window, double sample_rate, int n_tasks, unsigned* __restrict__ ok, double* __restrict__ out_val,
+    int* __restrict__ out_n_window, int* __restrict__ out_n_kept) {
+    __shared__ double s_window[kWaves][kLdsWindow];
+    constexpr int M = DEG + 1;
+    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+    const int task = blockIdx.x * kWaves + wave;
+    if (task >= n_tasks) return;  // the whole wavefront
+    const int d0 = task_det0[task], d1 = task_det1[task];
+    const int rx0 = rx[d0], rx1 = rx[d1];
+    const unsigned key = unsigned(rx0) * unsigned(n_rx) + unsigned(rx1);
+    const int bucket = int(bucket_ptr[key]), n_list = int(bucket_ptr[key + 1]) - bucket;
+    const double* list_ts = b_ts + bucket;
+    const double t0 = ts[d0];
+
+    // bisect_left(list, t0 - window), bisect_right(list, t0 + window): Python's loops, whatever the order
+    // of the list (every lane runs them; the loads are one address per wavefront)
+    const double start = t0 - window, stop = t0 + window;
+    int lo = 0, hi = n_list;
+    while (lo < hi) {
+        const int mid = (lo + hi) / 2;
+        if (list_ts[mid] < start)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    const int left = lo;
+    lo = 0, hi = n_list;
+    while (lo < hi) {
+        const int mid = (lo + hi) / 2;
+        if (stop < list_ts[mid])
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    const int n_window = lo > left ? lo - left : 0;
+    const double* w_soa0 = b_soa0 + bucket + left;
+    const double* w_soa1 = b_soa1 + bucket + left;
+    const double* w_q0 = b_q0 + bucket + left;
+    const double* w_q1 = b_q1 + bucket + left;
+    const int* w_beacon = b_beacon + bucket + left;
+
+    // is_outlier(sdoa) if the window holds more than one pair: dropped where 0.6745 * diff / mad > 3.5
+    // (mad == 0: 0 / 0 is NaN and stays, x / 0 is inf and goes)
+    const bool masked = n_window > 1;
+    double* lds = n_window <= kLdsWindow ? s_window[wave] : nullptr;
+    Window w{w_soa0, w_soa1, nullptr, n_window, false, 0.0};
+    double mad = 0.0;
+    if (masked) {
+        if (lds) {
+            for (int i = lane; i < n_window; i += kWave) lds[i] = w.compute(i);
+            wave_sync();
+            w.lds = lds;
+        }
+        w.median = wave_median(w, lane);
+        w.deviation = true;
+        if (lds) {
+            wave_sync();  // every rank is counted before the values are replaced
+            for (int i = lane; i < n_window; i += kWave) lds[i] = w.compute(i);
+            wave_sync();
+        }
+        mad = wave_median(w, lane);
+    }
+    auto kept = [&](int i) { return !masked || !(0.6745 * w.value(i) / mad > 3.5); };
+    // x = soa1 + beacon_sdoa, beacon_sdoa = (dist(rx0, b) - dist(rx1, b)) / c * sample_rate; y = soa0
+    auto abscissa = [&](int i) {
+        const int b = w_beacon[i];
+        const double tdoa = (dist[size_t(rx0) * n_beacons + b] - dist[size_t(rx1) * n_beacons + b]) / kSpeedOfLight;
+        return w_soa1[i] + tdoa * sample_rate;
+    };
+
+    // pass 1: how many are kept, the means, model_quality
+    int n_kept = 0;
+    double sum_x = 0.0, sum_y = 0.0, sum_q0 = 0.0, sum_q1 = 0.0;
+    for (int i = lane; i < n_window; i += kWave)
+        if (kept(i)) {
+            ++n_kept;
+            sum_x += abscissa(i);
+            sum_y += w_soa0[i];
+            sum_q0 += w_q0[i];
+            sum_q1 += w_q1[i];
+        }
+    n_kept = wave_sum(n_kept);
+    if (lane == 0) {
+        if (out_n_window) out_n_window[task] = n_window;
+        if (out_n_kept) out_n_kept[task] = n_kept;
+    }
+    bool good = n_kept >= M;
+    double tdoa = 0.0, quality = 0.0;
+    if (good) {
+        const double mean_x = wave_sum(sum_x) / n_kept, mean_y = wave_sum(sum_y) / n_kept;
+        quality = (wave_sum(sum_q0) / n_kept + wave_sum(sum_q1) / n_kept) / 2.0;
+        // pass 2: the scale, and DEG + 1 distinct abscissae (the smallest, the next larger one, ...)
+        double below = -INFINITY, scale = 0.0;
+        for (int k = 0; k < M && good; ++k) {
+            double next = INFINITY;
+            for (int i = lane; i < n_window; i += kWave)
+                if (kept(i)) {
+                    const double x = abscissa(i);
+                    if (x > below) next = fmin(next, x);
+                    if (k == 0) scale = fmax(scale, fabs(x - mean_x));
+                }
+            next = wave_min(next);
+            good = next < INFINITY;
+            below = next;
+        }
+        scale = wave_max(scale);
+        if (good) {
+            // pass 3: the moments of u = (x - mean_x) / scale in [-1, 1] against v = y - mean_y
+            double s[2 * DEG + 1], t[M];
+#pragma unroll
+            for (int k = 0; k <= 2 * DEG; ++k) s[k] = 0.0;
+#pragma unroll
+            for (int k = 0; k < M; ++k) t[k] = 0.0;
+            for (int i = lane; i < n_window; i += kWave)
+                if (kept(i)) {
+                    const double u = (abscissa(i) - mean_x) / scale, v = w_soa0[i] - mean_y;
+                    double p = 1.0;
+#pragma unroll
+                    for (int k = 0; k <= 2 * DEG; ++k) {
+                        s[k] += p;
+                        if (k < M) t[k] += p * v;
+                        p *= u;
+                    }
+                }
+#pragma unroll
+            for (int k = 0; k <= 2 * DEG; ++k) s[k] = wave_sum(s[k]);
+#pragma unroll
+            for (int k = 0; k < M; ++k) t[k] = wave_sum(t[k]);
+            // normal equations, Gaussian elimination with partial pivoting (every lane the same)
+            double a[M][M + 1];
+#pragma unroll
+            for (int r = 0; r < M; ++r) {
+#pragma unroll
+                for (int c = 0; c < M; ++c) a[r][c] = s[r + c];
+                a[r][M] = t[r];
+            }
+#pragma unroll
+            for (int c = 0; c < M; ++c) {
+#pragma unroll
+                for (int r = c + 1; r < M; ++r)
+                    if (fabs(a[r][c]) > fabs(a[c][c])) {
+#pragma unroll
+                        for (int k = 0; k <= M; ++k) {
+                            const double swap = a[c][k];
+                            a[c][k] = a[r][k];
+                            a[r][k] = swap;
+                        }
+                    }
+#pragma unroll
+                for (int r = c + 1; r < M; ++r) {
+                    const double f = a[r][c] / a[c][c];
+#pragma unroll
+                    for (int k = c; k <= M; ++k) a[r][k] -= f * a[c][k];
+                }
+            }
+            double coef[M];
+#pragma unroll
+            for (int r = M - 1; r >= 0; --r) {
+                double acc = a[r][M];
+#pragma unroll
+                for (int k = r + 1; k < M; ++k) acc -= a[r][k] * coef[k];
+                coef[r] = acc / a[r][r];
+            }
+            // tdoa = (det0.soa - fit(det1.soa)) / sample_rate, fit(x) = mean_y + p(u(x)): the large parts
+            // cancel before the small one is subtracted
+            const double u = (soa[d1] - mean_x) / scale;
+            double p = coef[M - 1];
+#pragma unroll
+            for (int k = M - 2; k >= 0; --k) p = p * u + coef[k];
+            tdoa = ((soa[d0] - mean_y) - p) / sample_rate;
+            good = !(fabs(tdoa) >= kMaxTdoa);
+        }
+    }
+    if (lane == 0) {
+        ok[task] = good ? 1u : 0u;
+        out_val[3 * size_t(task)] = tdoa;
+        out_val[3 * size_t(task) + 1] = (q[d0] + q[d1]) / 2.0;
+        out_val[3 * size_t(task) + 2] = quality;
+    }
+}
+
+// ---------------------------------------------------------------- the output orders
+__global__ void k_fail_flags(const unsigned* __restrict__ ok, int n_tasks, unsigned* __restrict__ fail) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t <= n_tasks) fail[t] = t < n_tasks ? 1u - ok[t] : 0u;
+}
+// rows and failures in task order (= match order, then combination order)
+__global__ void k_emit_rows(const unsigned* __restrict__ ok, const unsigned* __restrict__ ok_excl,
+                            const unsigned* __restrict__ fail_excl, const int* __restrict__ task_det0,
+                            const int* __restrict__ task_det1, const int* __restrict__ rx,
+                            const double* __restrict__ val, int n_tasks, int* __restrict__ row_rx,
+                            long long* __restrict__ row_det, double* __restrict__ row_val,
+                            long long* __restrict__ fail) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tasks) return;
+    const int d0 = task_det0[t], d1 = task_det1[t];
+    if (ok[t]) {
+        const size_t r = ok_excl[t];
+        row_rx[2 * r] = rx[d0];
+        row_rx[2 * r + 1] = rx[d1];
+        row_det[2 * r] = d0;
+        row_det[2 * r + 1] = d1;
+        for (int k = 0; k < 3; ++k) row_val[3 * r + k] = val[3 * size_t(t) + k];
+    } else {
+        const size_t f = fail_excl[t];
+        fail[2 * f] = d0;
+        fail[2 * f + 1] = d1;
+    }
+}
+// a mobile match with at least one row is a group
+__global__ void k_group_flags(const int* __restrict__ beacon, const unsigned* __restrict__ task_base,
+                              const unsigned* __restrict__ ok_excl, int n_matches, unsigned* __restrict__ flag) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m > n_matches) return;
+    flag[m] = (m < n_matches && beacon[m] < 0 && ok_excl[task_base[m + 1]] > ok_excl[task_base[m]]) ? 1u : 0u;
+}
+__global__ void k_emit_groups(const unsigned* __restrict__ flag, const unsigned* __restrict__ flag_excl,
+                              const unsigned* __restrict__ task_base, const unsigned* __restrict__ ok_excl,
+                              int n_matches, long long* __restrict__ group_id, long long* __restrict__ group_ptr) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_matches || !flag[m]) return;
+    group_id[flag_excl[m]] = m;
+    group_ptr[flag_excl[m]] = (long long)ok_excl[task_base[m]];
+}
+
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+    template <class T>
+    T* as() { return static_cast<T*>(p); }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+};
+
+#define T_TRY(expr)                                                                          \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess)                                                                \
+            return thr::fail_msg(THR_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// exclusive sum of n unsigned values (n >= 1), the shared temporary grown on demand
+hipError_t exclusive_sum(DevBuf& tmp, size_t& tmp_bytes, const unsigned* in, unsigned* out, int n, hipStream_t s) {
+    size_t need = 0;
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, in, out, n, s);
+    if (e != hipSuccess) return e;
+    if (need > tmp_bytes) {
+        if (tmp.p) (void)hipFree(tmp.p);
+        tmp.p = nullptr;
+        if ((e = tmp.alloc(need)) != hipSuccess) return e;
+        tmp_bytes = need;
+    }
+    return hipcub::DeviceScan::ExclusiveSum(tmp.p, need, in, out, n, s);
+}
+
+inline dim3 grid_for(size_t n) { return dim3(unsigned((n + kBlock - 1) / kBlock)); }
+
+thread_local double g_times_ms[3] = {0, 0, 0};  // last thr_tdoa of this thread: copies in, kernels, copies out
+
+}  // namespace
+
+extern "C" int thr_tdoa(int device_id, size_t n_det, const int32_t* rx, const double* timestamp, const double* soa,
+                        const double* energy, const double* noise, size_t n_matches, const int64_t* match_ptr,
+                        const int64_t* match_idx, const int32_t* match_beacon, int n_rx, int n_beacons,
+                        const double* dist, double window, double sample_rate, int deg, size_t n_tasks,
+                        int32_t* row_rx_out, int64_t* row_det_out, double* row_val_out, size_t* n_rows_out,
+                        int64_t* group_id_out, int64_t* group_ptr_out, size_t* n_groups_out, int64_t* fail_out,
+                        size_t* n_fail_out, int32_t* n_window_out, int32_t* n_kept_out) try {
+    if (n_rows_out) *n_rows_out = 0;
+    if (n_groups_out) *n_groups_out = 0;
+    if (n_fail_out) *n_fail_out = 0;
+    g_times_ms[0] = g_times_ms[1] = g_times_ms[2] = 0;
+    if (!n_rows_out || !n_groups_out || !n_fail_out || !group_ptr_out || !match_ptr)
+        return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: null argument");
+    if (deg < 1 || deg > 3) return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: deg must be 1, 2 or 3, not %d", deg);
+    if (n_rx < 1 || n_rx > kMaxReceivers)
+        return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: 1 to %d receivers, not %d", kMaxReceivers, n_rx);
+    if (n_beacons < 0 || (n_beacons > 0 && !dist)) return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: bad beacon table");
+    if (n_det > size_t(1) << 28 || n_matches > size_t(1) << 28)
+        return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: too many detections or matches");
+    if (n_matches && (!rx || !timestamp || !soa || !energy || !noise || !match_idx || !match_beacon))
+        return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: null argument");
+
+    // ---- everything a kernel will index with is checked here, before anything is launched
+    if (match_ptr[0] != 0) return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: match_ptr[0] must be 0");
+    size_t total_tasks = 0, total_pairs = 0;
+    std::vector<size_t> seen(size_t(n_rx), 0);  // seen[r] = m + 1: receiver r occurs in match m
+    for (size_t m = 0; m < n_matches; ++m) {
+        const int64_t a = match_ptr[m], e = match_ptr[m + 1];
+        if (e < a) return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: match_ptr decreases at match %zu", m);
+        if (match_beacon[m] < -1 || match_beacon[m] >= n_beacons)
+            return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: match %zu names beacon %d of %d", m, match_beacon[m], n_beacons);
+        for (int64_t i = a; i < e; ++i) {
+            const int64_t d = match_idx[i];
+            if (d < 0 || size_t(d) >= n_det)
+                return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: match %zu holds detection %lld of %zu", m, (long long)d, n_det);
+            if (rx[d] < 0 || rx[d] >= n_rx)
+                return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: detection %lld has receiver index %d of %d", (long long)d, rx[d], n_rx);
+            if (seen[size_t(rx[d])] == m + 1)
+                return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: match %zu holds two detections of one receiver (detection %lld)",
+                                     m, (long long)d);
+            seen[size_t(rx[d])] = m + 1;
+        }
+        const size_t k = size_t(e - a), pairs = k * (k ? k - 1 : 0) / 2;
+        (match_beacon[m] >= 0 ? total_pairs : total_tasks) += pairs;
+    }
+    if (total_tasks > size_t(1) << 28 || total_pairs > size_t(1) << 28)
+        return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: too many detection pairs");
+    if (total_tasks != n_tasks)
+        return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: the mobile matches hold %zu detection pairs, n_tasks says %zu",
+                             total_tasks, n_tasks);
+    if (n_tasks && (!row_rx_out || !row_det_out || !row_val_out || !group_id_out || !fail_out))
+        return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: null argument");
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return thr::fail_msg(THR_ERR_DEVICE, "no HIP device available (this engine has no CPU fallback)");
+    if (device_id < 0 || device_id >= ndev) return thr::fail_msg(THR_ERR_ARG, "bad device_id %d", device_id);
+    group_ptr_out[0] = 0;
+    if (n_tasks == 0) return THR_OK;  // no mobile detection pair: nothing to launch (the times stay zero)
+    T_TRY(hipSetDevice(device_id));
+    const int n = int(n_det), nm = int(n_matches), nt = int(n_tasks), np = int(total_pairs);
+    const int n_keys = n_rx * n_rx;
+    const size_t n_idx = size_t(match_ptr[n_matches]);
+    const dim3 blk(kBlock);
+    hipStream_t s = nullptr;
+    Event ev[4];
+    for (Event& e : ev) T_TRY(hipEventCreate(&e.e));
+
+    DevBuf d_rx, d_ts, d_soa, d_en, d_no, d_ptr, d_idx, d_beacon, d_dist;
+    T_TRY(d_rx.alloc(size_t(n) * 4));
+    T_TRY(d_ts.alloc(size_t(n) * 8));
+    T_TRY(d_soa.alloc(size_t(n) * 8));
+    T_TRY(d_en.alloc(size_t(n) * 8));
+    T_TRY(d_no.alloc(size_t(n) * 8));
+    T_TRY(d_ptr.alloc((size_t(nm) + 1) * 8));
+    T_TRY(d_idx.alloc(n_idx * 8));
+    T_TRY(d_beacon.alloc(size_t(nm) * 4));
+    T_TRY(d_dist.alloc(size_t(n_rx) * size_t(n_beacons) * 8));
+    T_TRY(hipEventRecord(ev[0].e, s));
+    T_TRY(hipMemcpy(d_rx.p, rx, size_t(n) * 4, hipMemcpyHostToDevice));
+    T_TRY(hipMemcpy(d_ts.p, timestamp, size_t(n) * 8, hipMemcpyHostToDevice));
+    T_TRY(hipMemcpy(d_soa.p, soa, size_t(n) * 8, hipMemcpyHostToDevice));
+    T_TRY(hipMemcpy(d_en.p, energy, size_t(n) * 8, hipMemcpyHostToDevice));
+    T_TRY(hipMemcpy(d_no.p, noise, size_t(n) * 8, hipMemcpyHostToDevice));
+    T_TRY(hipMemcpy(d_ptr.p, match_ptr, (size_t(nm) + 1) * 8, hipMemcpyHostToDevice));
+    if (n_idx) T_TRY(hipMemcpy(d_idx.p, match_idx, n_idx * 8, hipMemcpyHostToDevice));
+    T_TRY(hipMemcpy(d_beacon.p, match_beacon, size_t(nm) * 4, hipMemcpyHostToDevice));
+    if (n_beacons) T_TRY(hipMemcpy(d_dist.p, dist, size_t(n_rx) * size_t(n_beacons) * 8, hipMemcpyHostToDevice));
+    T_TRY(hipEventRecord(ev[1].e, s));
+
+    // ---- 1. pairs per match, their slots, the expansion
+    DevBuf d_q, d_cnt_b, d_cnt_t, d_base_b, d_base_t, d_tmp;
+    DevBuf d_key, d_pd0, d_pd1, d_pb, d_td0, d_td1;
+    size_t tmp_bytes = 0;
+    T_TRY(d_q.alloc(size_t(n) * 8));
+    T_TRY(d_cnt_b.alloc((size_t(nm) + 1) * 4));
+    T_TRY(d_cnt_t.alloc((size_t(nm) + 1) * 4));
+    T_TRY(d_base_b.alloc((size_t(nm) + 1) * 4));
+    T_TRY(d_base_t.alloc((size_t(nm) + 1) * 4));
+    T_TRY(d_key.alloc(size_t(np) * 4));
+    T_TRY(d_pd0.alloc(size_t(np) * 4));
+    T_TRY(d_pd1.alloc(size_t(np) * 4));
+    T_TRY(d_pb.alloc(size_t(np) * 4));
+    T_TRY(d_td0.alloc(size_t(nt) * 4));
+    T_TRY(d_td1.alloc(size_t(nt) * 4));
+    hipLaunchKernelGGL(k_quality, grid_for(n), blk, 0, s, d_en.as<double>(), d_no.as<double>(), n, d_q.as<double>());
+    hipLaunchKernelGGL(k_pair_counts, grid_for(size_t(nm) + 1), blk, 0, s, d_ptr.as<long long>(), d_beacon.as<int>(), nm,
+                       d_cnt_b.as<unsigned>(), d_cnt_t.as<unsigned>());
+    T_TRY(hipGetLastError());
+    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_cnt_b.as<unsigned>(), d_base_b.as<unsigned>(), nm + 1, s));
+    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_cnt_t.as<unsigned>(), d_base_t.as<unsigned>(), nm + 1, s));
+    hipLaunchKernelGGL(k_expand, grid_for(nm), blk, 0, s, d_ptr.as<long long>(), d_idx.as<long long>(),
+                       d_beacon.as<int>(), d_rx.as<int>(), nm, n_rx, d_base_b.as<unsigned>(), d_base_t.as<unsigned>(),
+                       d_key.as<unsigned>(), d_pd0.as<int>(), d_pd1.as<int>(), d_pb.as<int>(), d_td0.as<int>(),
+                       d_td1.as<int>());
+    T_TRY(hipGetLastError());
+
+    // ---- 2. the beacon pairs into their receiver pair's list, match order kept
+    DevBuf d_key_s, d_iota, d_perm, d_bucket, d_bts, d_bs0, d_bs1, d_bq0, d_bq1, d_bb;
+    T_TRY(d_bucket.alloc((size_t(n_keys) + 2) * 4));
+    T_TRY(d_bts.alloc(size_t(np) * 8));
+    T_TRY(d_bs0.alloc(size_t(np) * 8));
+    T_TRY(d_bs1.alloc(size_t(np) * 8));
+    T_TRY(d_bq0.alloc(size_t(np) * 8));
+    T_TRY(d_bq1.alloc(size_t(np) * 8));
+    T_TRY(d_bb.alloc(size_t(np) * 4));
+    if (np > 0) {
+        T_TRY(d_key_s.alloc(size_t(np) * 4));
+        T_TRY(d_iota.alloc(size_t(np) * 4));
+        T_TRY(d_perm.alloc(size_t(np) * 4));
+        hipLaunchKernelGGL(k_iota, grid_for(np), blk, 0, s, d_iota.as<unsigned>(), np);
+        T_TRY(hipGetLastError());
+        int key_bits = 1;
+        while ((1 << key_bits) < n_keys) ++key_bits;
+        size_t need = 0;
+        T_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, d_key.as<unsigned>(), d_key_s.as<unsigned>(),
+                                                 d_iota.as<unsigned>(), d_perm.as<unsigned>(), np, 0, key_bits, s));
+        if (need > tmp_bytes) {
+            if (d_tmp.p) (void)hipFree(d_tmp.p);
+            d_tmp.p = nullptr;
+            T_TRY(d_tmp.alloc(need));
+            tmp_bytes = need;
+        }
+        T_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, need, d_key.as<unsigned>(), d_key_s.as<unsigned>(),
+                                                 d_iota.as<unsigned>(), d_perm.as<unsigned>(), np, 0, key_bits, s));
+        hipLaunchKernelGGL(k_gather_pairs, grid_for(np), blk, 0, s, d_perm.as<unsigned>(), d_pd0.as<int>(),
+                           d_pd1.as<int>(), d_pb.as<int>(), d_ts.as<double>(), d_soa.as<double>(), d_q.as<double>(), np,
+                           d_bts.as<double>(), d_bs0.as<double>(), d_bs1.as<double>(), d_bq0.as<double>(),
+                           d_bq1.as<double>(), d_bb.as<int>());
+        hipLaunchKernelGGL(k_bucket_bounds, grid_for(size_t(n_keys) + 1), blk, 0, s, d_key_s.as<unsigned>(), np, n_keys,
+                           d_bucket.as<unsigned>());
+        T_TRY(hipGetLastError());
+    } else {
+        T_TRY(hipMemsetAsync(d_bucket.p, 0, (size_t(n_keys) + 2) * 4, s));  // no beacon match: every list is empty
+    }
+
+    // ---- 3. one wavefront per task
+    DevBuf d_ok, d_val, d_nwin, d_nkept;
+    T_TRY(d_ok.alloc((size_t(nt) + 1) * 4));
+    T_TRY(d_val.alloc(size_t(nt) * 24));
+    T_TRY(d_nwin.alloc(size_t(nt) * 4));
+    T_TRY(d_nkept.alloc(size_t(nt) * 4));
+    T_TRY(hipMemsetAsync(d_ok.p, 0, (size_t(nt) + 1) * 4, s));
+    const dim3 est_grid(unsigned((nt + kWaves - 1) / kWaves));
+#define LAUNCH_ESTIMATE(DEG)                                                                                        \
+    hipLaunchKernelGGL(k_estimate<DEG>, est_grid, blk, 0, s, d_td0.as<int>(), d_td1.as<int>(), d_rx.as<int>(),        \
+                       d_ts.as<double>(), d_soa.as<double>(), d_q.as<double>(), d_bucket.as<unsigned>(), n_rx,        \
+                       n_beacons, d_bts.as<double>(), d_bs0.as<double>(), d_bs1.as<double>(), d_bq0.as<double>(),     \
+                       d_bq1.as<double>(), d_bb.as<int>(), d_dist.as<double>(), window, sample_rate, nt,              \
+                       d_ok.as<unsigned>(), d_val.as<double>(), d_nwin.as<int>(), d_nkept.as<int>())
+    if (deg == 1)
+        LAUNCH_ESTIMATE(1);
+    else if (deg == 2)
+        LAUNCH_ESTIMATE(2);
+    else
+        LAUNCH_ESTIMATE(3);
+#undef LAUNCH_ESTIMATE
+    T_TRY(hipGetLastError());
+
+    // ---- 4. rows, failures and groups in the reference's orders
+    DevBuf d_ok_ex, d_fail, d_fail_ex, d_gflag, d_gflag_ex, d_row_rx, d_row_det, d_row_val, d_fail_out, d_gid, d_gptr;
+    T_TRY(d_ok_ex.alloc((size_t(nt) + 1) * 4));
+    T_TRY(d_fail.alloc((size_t(nt) + 1) * 4));
+    T_TRY(d_fail_ex.alloc((size_t(nt) + 1) * 4));
+    T_TRY(d_gflag.alloc((size_t(nm) + 1) * 4));
+    T_TRY(d_gflag_ex.alloc((size_t(nm) + 1) * 4));
+    T_TRY(d_row_rx.alloc(size_t(nt) * 8));
+    T_TRY(d_row_det.alloc(size_t(nt) * 16));
+    T_TRY(d_row_val.alloc(size_t(nt) * 24));
+    T_TRY(d_fail_out.alloc(size_t(nt) * 16));
+    T_TRY(d_gid.alloc(size_t(nm) * 8));
+    T_TRY(d_gptr.alloc(size_t(nm) * 8));
+    hipLaunchKernelGGL(k_fail_flags, grid_for(size_t(nt) + 1), blk, 0, s, d_ok.as<unsigned>(), nt, d_fail.as<unsigned>());
+    T_TRY(hipGetLastError());
+    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_ok.as<unsigned>(), d_ok_ex.as<unsigned>(), nt + 1, s));
+    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_fail.as<unsigned>(), d_fail_ex.as<unsigned>(), nt + 1, s));
+    hipLaunchKernelGGL(k_emit_rows, grid_for(nt), blk, 0, s, d_ok.as<unsigned>(), d_ok_ex.as<unsigned>(),
+                       d_fail_ex.as<unsigned>(), d_td0.as<int>(), d_td1.as<int>(), d_rx.as<int>(), d_val.as<double>(), nt,
+                       d_row_rx.as<int>(), d_row_det.as<long long>(), d_row_val.as<double>(),
+                       d_fail_out.as<long long>());
+    hipLaunchKernelGGL(k_group_flags, grid_for(size_t(nm) + 1), blk, 0, s, d_beacon.as<int>(), d_base_t.as<unsigned>(),
+                       d_ok_ex.as<unsigned>(), nm, d_gflag.as<unsigned>());
+    T_TRY(hipGetLastError());
+    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_gflag.as<unsigned>(), d_gflag_ex.as<unsigned>(), nm + 1, s));
+    hipLaunchKernelGGL(k_emit_groups, grid_for(nm), blk, 0, s, d_gflag.as<unsigned>(), d_gflag_ex.as<unsigned>(),
+                       d_base_t.as<unsigned>(), d_ok_ex.as<unsigned>(), nm, d_gid.as<long long>(),
+                       d_gptr.as<long long>());
+    T_TRY(hipGetLastError());
+    T_TRY(hipEventRecord(ev[2].e, s));
+
+    unsigned n_rows = 0, n_fail = 0, n_groups = 0;
+    T_TRY(hipMemcpy(&n_rows, d_ok_ex.as<unsigned>() + nt, 4, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(&n_fail, d_fail_ex.as<unsigned>() + nt, 4, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(&n_groups, d_gflag_ex.as<unsigned>() + nm, 4, hipMemcpyDeviceToHost));
+    if (size_t(n_rows) + size_t(n_fail) != n_tasks || n_groups > n_rows)
+        return thr::fail_msg(THR_ERR_DEVICE, "thr_tdoa: %u rows and %u failures for %zu tasks", n_rows, n_fail, n_tasks);
+    T_TRY(hipMemcpy(row_rx_out, d_row_rx.p, size_t(n_rows) * 8, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(row_det_out, d_row_det.p, size_t(n_rows) * 16, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(row_val_out, d_row_val.p, size_t(n_rows) * 24, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(fail_out, d_fail_out.p, size_t(n_fail) * 16, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(group_id_out, d_gid.p, size_t(n_groups) * 8, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(group_ptr_out, d_gptr.p, size_t(n_groups) * 8, hipMemcpyDeviceToHost));
+    group_ptr_out[n_groups] = int64_t(n_rows);
+    if (n_window_out) T_TRY(hipMemcpy(n_window_out, d_nwin.p, size_t(nt) * 4, hipMemcpyDeviceToHost));
+    if (n_kept_out) T_TRY(hipMemcpy(n_kept_out, d_nkept.p, size_t(nt) * 4, hipMemcpyDeviceToHost));
+    T_TRY(hipEventRecord(ev[3].e, s));
+    T_TRY(hipEventSynchronize(ev[3].e));
+    for (int k = 0; k < 3; ++k) {
+        float ms = 0;
+        T_TRY(hipEventElapsedTime(&ms, ev[k].e, ev[k + 1].e));
+        g_times_ms[k] = ms;
+    }
+    *n_rows_out = n_rows;
+    *n_groups_out = n_groups;
+    *n_fail_out = n_fail;
+    return THR_OK;
+} catch (...) {
+    return thr::on_exception("thr_tdoa");
+}
+
+extern "C" int thr_debug_tdoa_times(double* ms_out) try {
+    if (!ms_out) return thr::fail_msg(THR_ERR_ARG, "thr_debug_tdoa_times: null argument");
+    for (int k = 0; k < 3; ++k) ms_out[k] = g_times_ms[k];
+    return THR_OK;
+} catch (...) {
+    return thr::on_exception("thr_debug_tdoa_times");
+}
