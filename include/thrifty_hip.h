@@ -63,7 +63,8 @@ extern "C" {
  *    thr_run_extract_stream (additions only)
  *    within 11, a pure addition (no existing entry point or struct changes, the number stays):
  *    + thr_match / thr_debug_match_times -- the reference's `thrifty match` (matchmaker.py:17-79)
- *    + thr_tdoa / thr_debug_tdoa_times -- the reference's `thrifty tdoa` (tdoa_est.py:43-105, 234-303) */
+ *    + thr_tdoa / thr_debug_tdoa_times -- the reference's `thrifty tdoa` (tdoa_est.py:43-105, 234-303)
+ *    + thr_pos / thr_debug_pos_times -- the reference's `thrifty pos` (pos_est.py:31-156) */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -907,6 +908,40 @@ int thr_tdoa(int device_id, size_t n_det, const int32_t* rx, const double* times
              int64_t* fail_out, size_t* n_fail_out, int32_t* n_window_out, int32_t* n_kept_out);
 /* Milliseconds of the calling thread's last thr_tdoa: {copies in, kernels, copies out} (HIP events). */
 int thr_debug_tdoa_times(double* ms_out /* [3] */);
+
+/* pos -- the reference's `thrifty pos` (thrifty/pos_est.py) on host columns: synchronous, no handle, no
+ * state but the device's.  Group g (one mobile transmission) holds rows group_ptr[g] .. group_ptr[g + 1]
+ * (group_ptr[0] == 0, non-decreasing); row i is a TDOA row_tdoa[i] [s] between the receivers row_rx0[i]
+ * and row_rx1[i] -- DENSE indices into rx_coords[n_rx][dims] (n_rx <= 64, finite) -- with row_snr[i].
+ *  dims == 2: p minimises sum (tdoa_i c - (|rx0_i - p| - |rx1_i - p|))^2, c = 2.997e8, inside the box
+ *     min(rx) - 10 km .. max(rx) + 10 km per axis, by a Levenberg-Marquardt iteration from x0[2] of at
+ *     most max_iter steps (csrc/pos.hip describes it; the reference uses SciPy's TRF).  A group with
+ *     fewer than 3 distinct receivers is THR_POS_UNDERDETERMINED.  max_iter == 0 evaluates snr and dop at
+ *     x0 without moving.  first_two_rx is not read.
+ *  dims == 1: n_rx == 2 and one row per group; p = (rx[a] + rx[b] -+ tdoa c) / 2 with a, b =
+ *     first_two_rx[0], [1], minus where rx[a] > rx[b] -- the reference's three float64 operations.  x0 and
+ *     max_iter are not read.
+ * Per group, in group order: pos_out[g * dims ..], snr_out[g] = the mean of its rows' snr,
+ * dop_out[g] = sqrt(trace(inv(G'G))) at the position, G_i = (rx0_i - p) / |rx0_i - p| - (rx1_i - p) /
+ * |rx1_i - p| (-1 where G'G's determinant is 0 or not finite), iters_out[g] = trial points evaluated, and
+ * status_out[g]: THR_POS_OK; THR_POS_UNDERDETERMINED; THR_POS_UNCONVERGED (max_iter reached, the last
+ * iterate is written); THR_POS_AT_BOUND (converged on the box); THR_POS_NONFINITE (a NaN or Inf tdoa, or
+ * a point that coincides with a receiver).  Nothing is compacted: the caller drops what it does not want.
+ * An index out of range, a decreasing group_ptr, dims other than 1 or 2, n_rx > 64, a non-finite
+ * coordinate or x0, a 1-D group that does not hold one row, a bad device_id: THR_ERR_ARG before anything
+ * is launched.  n_groups == 0: THR_OK once the arguments and device_id have been checked.
+ */
+#define THR_POS_OK 0
+#define THR_POS_UNDERDETERMINED 1
+#define THR_POS_UNCONVERGED 2
+#define THR_POS_AT_BOUND 3
+#define THR_POS_NONFINITE 4
+int thr_pos(int device_id, size_t n_groups, const int64_t* group_ptr, const int32_t* row_rx0,
+            const int32_t* row_rx1, const double* row_tdoa, const double* row_snr, int n_rx, int dims,
+            const double* rx_coords, const int32_t* first_two_rx, const double* x0, int max_iter,
+            double* pos_out, double* dop_out, double* snr_out, int32_t* status_out, int32_t* iters_out);
+/* Milliseconds of the calling thread's last thr_pos: {copies in, kernels, copies out} (HIP events). */
+int thr_debug_pos_times(double* ms_out /* [3] */);
 
 #ifdef __cplusplus
 }

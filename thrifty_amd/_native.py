@@ -41,6 +41,7 @@ EXPORTS = [
     "thr_run_extract_card", "thr_run_extract_stream",
     "thr_match", "thr_debug_match_times",
     "thr_tdoa", "thr_debug_tdoa_times",
+    "thr_pos", "thr_debug_pos_times",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -257,6 +258,8 @@ def load_library():
     lib.thr_tdoa.argtypes = ([C.c_int, C.c_size_t] + [vp] * 5 + [C.c_size_t, vp, vp, vp, C.c_int, C.c_int, vp,
                              C.c_double, C.c_double, C.c_int, C.c_size_t, vp, vp, vp, szp, vp, vp, szp, vp, szp, vp, vp])
     lib.thr_debug_tdoa_times.argtypes = [C.POINTER(C.c_double)]
+    lib.thr_pos.argtypes = [C.c_int, C.c_size_t, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    lib.thr_debug_pos_times.argtypes = [C.POINTER(C.c_double)]
     _lib = lib
     return lib
 
@@ -1153,4 +1156,46 @@ def tdoa_times():
     lib = load_library()
     ms = (C.c_double * 3)()
     _check(lib, lib.thr_debug_tdoa_times(ms))
+    return tuple(ms)
+
+
+POS_GROUPS_PER_WORKGROUP = 32   # kTeams of csrc/pos.hip: one 8-lane team per group
+POS_REGISTER_ROWS = 4           # kRegRows: rows per lane held in registers; groups over 32 rows re-read theirs
+POS_MAX_RECEIVERS = 64          # kMaxReceivers
+POS_OK, POS_UNDERDETERMINED, POS_UNCONVERGED, POS_AT_BOUND, POS_NONFINITE = range(5)      # THR_POS_*
+
+
+def pos(group_ptr, row_rx0, row_rx1, row_tdoa, row_snr, rx_coords, first_two_rx=(0, 1), x0=(0.1, 0.1), max_iter=100,
+        device_id=0):
+    """thr_pos on TDOA rows in CSR form (group g: rows group_ptr[g]:group_ptr[g + 1]; row_rx0 / row_rx1:
+    dense indices into rx_coords[n_rx, dims]) -> dict of pos float64[g, dims], dop / snr float64[g],
+    status / iters int32[g], every group in order.  ValueError for what thr_pos refuses."""
+    lib = load_library()
+    ptr = np.ascontiguousarray(group_ptr, dtype=np.int64)
+    rx0, rx1 = np.ascontiguousarray(row_rx0, dtype=np.int32), np.ascontiguousarray(row_rx1, dtype=np.int32)
+    tdoa, snr = np.ascontiguousarray(row_tdoa, dtype=np.float64), np.ascontiguousarray(row_snr, dtype=np.float64)
+    xy = np.ascontiguousarray(rx_coords, dtype=np.float64)
+    if ptr.ndim != 1 or len(ptr) < 1 or xy.ndim != 2 or not (len(rx0) == len(rx1) == len(tdoa) == len(snr) == int(ptr[-1])):
+        raise ValueError("pos: group_ptr, the row columns or rx_coords have the wrong shape")
+    first = np.ascontiguousarray(first_two_rx, dtype=np.int32)
+    start = np.ascontiguousarray(x0, dtype=np.float64)
+    if first.shape != (2,) or start.shape != (2,):
+        raise ValueError("pos: first_two_rx and x0 hold two values each")
+    n, dims = len(ptr) - 1, xy.shape[1]
+    out = {"pos": np.zeros((n, dims), dtype=np.float64), "dop": np.zeros(n, dtype=np.float64),
+           "snr": np.zeros(n, dtype=np.float64), "status": np.zeros(n, dtype=np.int32), "iters": np.zeros(n, dtype=np.int32)}
+    rc = lib.thr_pos(int(device_id), n, ptr.ctypes.data, rx0.ctypes.data, rx1.ctypes.data, tdoa.ctypes.data,
+                     snr.ctypes.data, xy.shape[0], dims, xy.ctypes.data, first.ctypes.data, start.ctypes.data,
+                     int(max_iter), *[out[key].ctypes.data for key in ("pos", "dop", "snr", "status", "iters")])
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    return out
+
+
+def pos_times():
+    """{copies in, kernels, copies out} of this thread's last pos(), milliseconds (HIP events)."""
+    lib = load_library()
+    ms = (C.c_double * 3)()
+    _check(lib, lib.thr_debug_pos_times(ms))
     return tuple(ms)

@@ -1,0 +1,403 @@
+// pos on the device (reference thrifty/pos_est.py): the position of every mobile transmission from its
+// TDOA group.  One 8-lane team per group (the layout of k_fit, csrc/lmdif8.hpp): lane j owns rows
+// j, j + 8, ... of its group, the first four of them in registers; every sum over rows is a group8_sum,
+// bitwise identical in the team's eight lanes, and everything after the sums is computed redundantly by
+// all eight from identical inputs, so a team's control flow is uniform.
+//
+// 2-D: minimise sum (tdoa_i c - (|rx0_i - p| - |rx1_i - p|))^2 from x0 inside the reference's box
+// (min(rx) - 10 km .. max(rx) + 10 km).  Not SciPy's TRF: a Levenberg-Marquardt iteration of our own.
+//   * an evaluation at p gives six team sums: the cost F, the normal matrix A = G'G, the gradient g = G'r;
+//   * an axis on which p sits on the box while -g points out of it is held (the step solves the other axis);
+//   * the undamped (Gauss-Newton) step h_gn is looked at first.  Where it is shorter than
+//     kGaussNewtonGate (|p| + 1) the damping is at its floor, zero: the cost resolves the position only to
+//     about sqrt(eps) of its scale, so from here on the step is taken without asking the cost, and the
+//     iteration ends when such a step is shorter than kStepTol (|p| + 1).  The gate looks at the step,
+//     not at mu (Nielsen's mu is still far from any floor when the cost stops resolving), and it is
+//     decided afresh in every iteration: far from a minimum h_gn is long (or NaN) and the judged branch
+//     runs; an unjudged step moves p by kGaussNewtonGate (|p| + 1) at most;
+//   * otherwise the damped step (A + mu I) h = -g, projected into the box, is accepted when the cost
+//     decreases, and mu follows the gain ratio (Nielsen's rule).
+// Every comparison is written so that a NaN takes the branch that ends or does not accept; the loop runs
+// max_iter times at most.  All lanes of a wave execute every evaluation (a finished team's state is held
+// by selects), so the DPP sums never read a disabled lane.
+// 1-D (two receivers): the reference's three float64 operations in its order, no iteration.
+// dop = sqrt(trace(inv(G'G))) at the estimate, closed form; -1 where the determinant is 0 or not finite.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/thrifty_hip.h"
+#include "lmdif8.hpp"
+
+// the team's lanes must agree bit for bit and the 1-D result must equal numpy's: no a * b + c may become
+// an fma in this file (the build also passes -ffp-contract=off for it, thrifty_amd/build.py)
+#pragma clang fp contract(off)
+
+namespace thr {
+int fail_msg(int code, const char* fmt, ...);
+int on_exception(const char* who) noexcept;  // handle.hip
+}
+
+namespace {
+
+using thr::group8_sum;
+
+constexpr int kBlock = 256;                // workgroup size
+constexpr int kTeam = 8;                    // lanes per group
+constexpr int kTeams = kBlock / kTeam;      // groups per workgroup (_native.POS_GROUPS_PER_WORKGROUP)
+constexpr int kRegRows = 4;                 // rows per lane kept in registers: groups up to 32 rows (_native.POS_REGISTER_ROWS)
+constexpr int kMaxReceivers = 64;           // the distinct-receiver count is a popcount of a 64-bit mask
+constexpr double kSpeedOfLight = 2.997e8;   // the reference's constant (tdoa_est.py:25)
+constexpr double kMaxDist = 10e3;           // pos_est.py:24
+constexpr double kStepTol = 1e-13;          // the iteration ends on a step below kStepTol (|p| + 1)
+constexpr double kGaussNewtonGate = 1e-4;   // undamped steps below kGaussNewtonGate (|p| + 1) are taken unjudged
+constexpr double kMuStart = 1e-3;           // initial damping, relative to the larger diagonal entry of A
+constexpr double kMuMax = 1e100;            // (A + mu I)'s determinant stays finite
+
+enum Status : int { kOk = 0, kUnderdetermined = 1, kUnconverged = 2, kAtBound = 3, kNonfinite = 4 };
+
+struct Row {
+    double ax, ay, bx, by, tc;  // rx0, rx1 and tdoa * c
+};
+struct Sums {
+    double F, a00, a01, a11, g0, g1;
+};
+
+// one row's terms at (px, py), added to the lane's partial sums when `on`
+__device__ __forceinline__ void add_row(const Row& r, bool on, double px, double py, Sums& s) {
+    const double ax = r.ax - px, ay = r.ay - py, bx = r.bx - px, by = r.by - py;
+    const double da = sqrt(ax * ax + ay * ay), db = sqrt(bx * bx + by * by);
+    const double res = r.tc - (da - db);
+    const double gx = ax / da - bx / db, gy = ay / da - by / db;
+    s.F += on ? res * res : 0.0;
+    s.a00 += on ? gx * gx : 0.0;
+    s.a01 += on ? gx * gy : 0.0;
+    s.a11 += on ? gy * gy : 0.0;
+    s.g0 += on ? gx * res : 0.0;
+    s.g1 += on ? gy * res : 0.0;
+}
+
+__device__ __forceinline__ Row load_row(const int* __restrict__ rx0, const int* __restrict__ rx1,
+                                        const double* __restrict__ tdoa, const double* __restrict__ xy, long long i) {
+    const int a = rx0[i], b = rx1[i];
+    return Row{xy[2 * a], xy[2 * a + 1], xy[2 * b], xy[2 * b + 1], tdoa[i] * kSpeedOfLight};
+}
+
+__device__ __forceinline__ bool finite6(const Sums& s) {
+    return isfinite(s.F) && isfinite(s.a00) && isfinite(s.a01) && isfinite(s.a11) && isfinite(s.g0) && isfinite(s.g1);
+}
+
+__device__ __forceinline__ double clamp(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
+
+// group g = one team.  group_ptr, row_rx0 / row_rx1 (< n_rx) and the table were checked on the host.
+__global__ __launch_bounds__(kBlock) void k_pos2d(const long long* __restrict__ group_ptr, const int* __restrict__ rx0,
+                                                  const int* __restrict__ rx1, const double* __restrict__ tdoa,
+                                                  const double* __restrict__ snr, const double* __restrict__ xy,
+                                                  int n_groups, double x0, double y0, double lo0, double lo1, double hi0,
+                                                  double hi1, int max_iter, double* __restrict__ pos_out,
+                                                  double* __restrict__ dop_out, double* __restrict__ snr_out,
+                                                  int* __restrict__ status_out, int* __restrict__ iters_out) {
+    const int team = (blockIdx.x * kBlock + threadIdx.x) / kTeam, j = threadIdx.x & (kTeam - 1);
+    const bool live = team < n_groups;
+    const long long beg = live ? group_ptr[team] : 0;
+    const int m = live ? int(group_ptr[team + 1] - beg) : 0;
+
+    // ---- rows, the receivers' mask and the snr sum
+    Row reg[kRegRows];
+    unsigned long long mask = 0;
+    double snr_sum = 0.0;
+#pragma unroll
+    for (int k = 0; k < kRegRows; ++k) {
+        const int r = j + kTeam * k;
+        reg[k] = Row{1.0, 0.0, 0.0, 1.0, 0.0};
+        if (r < m) {
+            reg[k] = load_row(rx0, rx1, tdoa, xy, beg + r);
+            mask |= (1ull << rx0[beg + r]) | (1ull << rx1[beg + r]);
+            snr_sum += snr[beg + r];
+        }
+    }
+    for (int r = j + kTeam * kRegRows; r < m; r += kTeam) {
+        mask |= (1ull << rx0[beg + r]) | (1ull << rx1[beg + r]);
+        snr_sum += snr[beg + r];
+    }
+    unsigned mlo = unsigned(mask), mhi = unsigned(mask >> 32);
+#pragma unroll
+    for (int d = 1; d < kTeam; d <<= 1) {
+        mlo |= __shfl_xor(mlo, d, 64);
+        mhi |= __shfl_xor(mhi, d, 64);
+    }
+    const int n_distinct = __popc(mlo) + __popc(mhi);
+    const double snr_mean = group8_sum(snr_sum) / double(m);
+
+    auto evaluate = [&](double px, double py) {
+        Sums s{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < kRegRows; ++k) add_row(reg[k], j + kTeam * k < m, px, py, s);
+        for (int r = j + kTeam * kRegRows; r < m; r += kTeam)  // long groups re-read their rows
+            add_row(load_row(rx0, rx1, tdoa, xy, beg + r), true, px, py, s);
+        return Sums{group8_sum(s.F), group8_sum(s.a00), group8_sum(s.a01), group8_sum(s.a11), group8_sum(s.g0),
+                    group8_sum(s.g1)};
+    };
+
+    double p0 = x0, p1 = y0;
+    Sums cur = evaluate(p0, p1);
+    int status = kUnconverged, iters = 0;
+    bool active = live;
+    if (n_distinct < 3) {
+        status = kUnderdetermined;
+        active = false;
+    } else if (!finite6(cur)) {
+        status = kNonfinite;
+        active = false;
+    }
+    double mu = kMuStart * fmax(cur.a00, cur.a11), nu = 2.0;
+
+    for (int it = 0; it < max_iter; ++it) {
+        if (!__any(active)) break;
+        // ---- the step, from identical values in the team's eight lanes
+        const bool zero_grad = fmax(fabs(cur.g0), fabs(cur.g1)) == 0.0;
+        const bool hold0 = (p0 <= lo0 && cur.g0 > 0.0) || (p0 >= hi0 && cur.g0 < 0.0);
+        const bool hold1 = (p1 <= lo1 && cur.g1 > 0.0) || (p1 >= hi1 && cur.g1 < 0.0);
+        const double scale = sqrt(p0 * p0 + p1 * p1) + 1.0;
+        double h0, h1;
+        auto solve = [&](double damp) {
+            const double a = cur.a00 + damp, d = cur.a11 + damp;
+            if (hold0 || hold1) {
+                h0 = hold0 ? 0.0 : -cur.g0 / a;
+                h1 = hold1 ? 0.0 : -cur.g1 / d;
+            } else {
+                const double det = a * d - cur.a01 * cur.a01;
+                h0 = (cur.a01 * cur.g1 - d * cur.g0) / det;
+                h1 = (cur.a01 * cur.g0 - a * cur.g1) / det;
+            }
+            h0 = clamp(p0 + h0, lo0, hi0) - p0;
+            h1 = clamp(p1 + h1, lo1, hi1) - p1;
+            return sqrt(h0 * h0 + h1 * h1);
+        };
+        double len = solve(0.0);
+        const bool gauss_newton = len <= kGaussNewtonGate * scale;  // false for a NaN
+        if (!gauss_newton) len = solve(mu);
+        const double t0 = p0 + h0, t1 = p1 + h1;
+        const Sums trial = evaluate(t0, t1);  // every lane of the wave, finished teams too
+
+        if (active) {
+            iters = it + 1;
+            if (zero_grad || (hold0 && hold1)) {
+                status = kOk;
+                active = false;
+            } else if (!finite6(trial) || !isfinite(len)) {
+                status = kNonfinite;
+                active = false;
+            } else if (gauss_newton) {
+                p0 = t0, p1 = t1, cur = trial;
+                if (len <= kStepTol * scale) {
+                    status = kOk;
+                    active = false;
+                }
+            } else if (trial.F < cur.F) {
+                const double pred = -(2.0 * (h0 * cur.g0 + h1 * cur.g1) +
+                                      (h0 * (cur.a00 * h0 + cur.a01 * h1) + h1 * (cur.a01 * h0 + cur.a11 * h1)));
+                const double rho = (cur.F - trial.F) / pred, q = 2.0 * rho - 1.0;
+                mu *= fmin(fmax(1.0 / 3.0, 1.0 - q * q * q), 2.0);  // a NaN ratio: 1/3 (fmax drops the NaN)
+                nu = 2.0;
+                p0 = t0, p1 = t1, cur = trial;
+                if (len <= kStepTol * scale) {
+                    status = kOk;
+                    active = false;
+                }
+            } else {
+                mu = fmin(mu * nu, kMuMax);
+                nu = fmin(nu * 2.0, kMuMax);
+            }
+        }
+    }
+    if (status == kOk && (p0 <= lo0 || p0 >= hi0 || p1 <= lo1 || p1 >= hi1)) status = kAtBound;
+
+    const double det = cur.a00 * cur.a11 - cur.a01 * cur.a01;
+    const double dop = (det == 0.0 || !isfinite(det)) ? -1.0 : sqrt((cur.a00 + cur.a11) / det);
+    if (live && j == 0) {
+        pos_out[2 * team] = p0;
+        pos_out[2 * team + 1] = p1;
+        dop_out[team] = dop;
+        snr_out[team] = snr_mean;
+        status_out[team] = status;
+        iters_out[team] = iters;
+    }
+}
+
+// 1-D, two receivers, one row per group (checked on the host): pos_est.py:31-47, one lane per group
+__global__ __launch_bounds__(kBlock) void k_pos1d(const long long* __restrict__ group_ptr, const int* __restrict__ rx0,
+                                                  const int* __restrict__ rx1, const double* __restrict__ tdoa,
+                                                  const double* __restrict__ snr, const double* __restrict__ x,
+                                                  int n_groups, int first, int second, double* __restrict__ pos_out,
+                                                  double* __restrict__ dop_out, double* __restrict__ snr_out,
+                                                  int* __restrict__ status_out, int* __restrict__ iters_out) {
+    const int g = blockIdx.x * kBlock + threadIdx.x;
+    if (g >= n_groups) return;
+    const long long i = group_ptr[g];
+    const double tdoa_pos = tdoa[i] * kSpeedOfLight;
+    const double rx_dist = x[first] + x[second];
+    const double p = x[first] > x[second] ? (rx_dist - tdoa_pos) / 2.0 : (rx_dist + tdoa_pos) / 2.0;
+    const double a = x[rx0[i]] - p, b = x[rx1[i]] - p;
+    const double gg = a / fabs(a) - b / fabs(b), s = gg * gg;
+    pos_out[g] = p;
+    dop_out[g] = s == 0.0 ? -1.0 : sqrt(1.0 / s);
+    snr_out[g] = snr[i];
+    status_out[g] = (isfinite(p) && isfinite(s)) ? kOk : kNonfinite;
+    iters_out[g] = 0;
+}
+
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+    template <class T>
+    T* as() { return static_cast<T*>(p); }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+};
+
+#define P_TRY(expr)                                                                          \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess)                                                                \
+            return thr::fail_msg(THR_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+thread_local double g_times_ms[3] = {0, 0, 0};  // last thr_pos of this thread: copies in, kernels, copies out
+
+}  // namespace
+
+extern "C" int thr_pos(int device_id, size_t n_groups, const int64_t* group_ptr, const int32_t* row_rx0,
+                       const int32_t* row_rx1, const double* row_tdoa, const double* row_snr, int n_rx, int dims,
+                       const double* rx_coords, const int32_t* first_two_rx, const double* x0, int max_iter,
+                       double* pos_out, double* dop_out, double* snr_out, int32_t* status_out, int32_t* iters_out) try {
+    g_times_ms[0] = g_times_ms[1] = g_times_ms[2] = 0;
+    if (!group_ptr || !rx_coords) return thr::fail_msg(THR_ERR_ARG, "thr_pos: null argument");
+    if (dims != 1 && dims != 2) return thr::fail_msg(THR_ERR_ARG, "thr_pos: 1 or 2 dimensions, not %d", dims);
+    if (n_rx < 1 || n_rx > kMaxReceivers)
+        return thr::fail_msg(THR_ERR_ARG, "thr_pos: 1 to %d receivers, not %d", kMaxReceivers, n_rx);
+    if (max_iter < 0) return thr::fail_msg(THR_ERR_ARG, "thr_pos: max_iter must not be negative");
+    if (n_groups > size_t(1) << 28) return thr::fail_msg(THR_ERR_ARG, "thr_pos: too many groups");
+    if (n_groups && (!pos_out || !dop_out || !snr_out || !status_out || !iters_out))
+        return thr::fail_msg(THR_ERR_ARG, "thr_pos: null argument");
+
+    // ---- everything a kernel will index with is checked here, before anything is launched
+    if (group_ptr[0] != 0) return thr::fail_msg(THR_ERR_ARG, "thr_pos: group_ptr[0] must be 0");
+    for (size_t g = 0; g < n_groups; ++g) {
+        const int64_t len = group_ptr[g + 1] - group_ptr[g];
+        if (len < 0) return thr::fail_msg(THR_ERR_ARG, "thr_pos: group_ptr decreases at group %zu", g);
+        if (len > (int64_t(1) << 24)) return thr::fail_msg(THR_ERR_ARG, "thr_pos: group %zu is too long", g);
+        if (dims == 1 && len != 1)
+            return thr::fail_msg(THR_ERR_ARG, "thr_pos: a 1-D group holds one row, group %zu holds %lld", g, (long long)len);
+    }
+    const size_t n_rows = size_t(group_ptr[n_groups]);
+    if (n_rows > size_t(1) << 30) return thr::fail_msg(THR_ERR_ARG, "thr_pos: too many rows");
+    if (n_rows && (!row_rx0 || !row_rx1 || !row_tdoa || !row_snr))
+        return thr::fail_msg(THR_ERR_ARG, "thr_pos: null argument");
+    for (size_t i = 0; i < n_rows; ++i)
+        if (row_rx0[i] < 0 || row_rx0[i] >= n_rx || row_rx1[i] < 0 || row_rx1[i] >= n_rx)
+            return thr::fail_msg(THR_ERR_ARG, "thr_pos: row %zu names receivers %d and %d of %d", i, row_rx0[i], row_rx1[i], n_rx);
+    for (size_t i = 0; i < size_t(n_rx) * size_t(dims); ++i)
+        if (!std::isfinite(rx_coords[i])) return thr::fail_msg(THR_ERR_ARG, "thr_pos: receiver coordinate %zu is not finite", i);
+    double start[2] = {0, 0}, lo[2] = {0, 0}, hi[2] = {0, 0};
+    int first = 0, second = 0;
+    if (dims == 1) {
+        if (n_rx != 2) return thr::fail_msg(THR_ERR_ARG, "thr_pos: the 1-D solver takes two receivers, not %d", n_rx);
+        if (!first_two_rx || first_two_rx[0] < 0 || first_two_rx[0] >= n_rx || first_two_rx[1] < 0 || first_two_rx[1] >= n_rx)
+            return thr::fail_msg(THR_ERR_ARG, "thr_pos: first_two_rx must name two of the %d receivers", n_rx);
+        first = first_two_rx[0], second = first_two_rx[1];
+    } else {
+        if (!x0 || !std::isfinite(x0[0]) || !std::isfinite(x0[1])) return thr::fail_msg(THR_ERR_ARG, "thr_pos: x0 must be finite");
+        for (int k = 0; k < 2; ++k) {
+            start[k] = x0[k];
+            lo[k] = hi[k] = rx_coords[k];
+            for (int r = 1; r < n_rx; ++r) {
+                lo[k] = std::fmin(lo[k], rx_coords[2 * r + k]);
+                hi[k] = std::fmax(hi[k], rx_coords[2 * r + k]);
+            }
+            lo[k] -= kMaxDist;
+            hi[k] += kMaxDist;
+        }
+    }
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return thr::fail_msg(THR_ERR_DEVICE, "no HIP device available (this engine has no CPU fallback)");
+    if (device_id < 0 || device_id >= ndev) return thr::fail_msg(THR_ERR_ARG, "bad device_id %d", device_id);
+    if (n_groups == 0) return THR_OK;  // nothing to launch (the times stay zero)
+    P_TRY(hipSetDevice(device_id));
+    const int ng = int(n_groups);
+    hipStream_t s = nullptr;
+    Event ev[4];
+    for (Event& e : ev) P_TRY(hipEventCreate(&e.e));
+
+    DevBuf d_ptr, d_rx0, d_rx1, d_tdoa, d_snr, d_xy, d_pos, d_dop, d_snr_out, d_status, d_iters;
+    P_TRY(d_ptr.alloc((n_groups + 1) * 8));
+    P_TRY(d_rx0.alloc(n_rows * 4));
+    P_TRY(d_rx1.alloc(n_rows * 4));
+    P_TRY(d_tdoa.alloc(n_rows * 8));
+    P_TRY(d_snr.alloc(n_rows * 8));
+    P_TRY(d_xy.alloc(size_t(n_rx) * size_t(dims) * 8));
+    P_TRY(d_pos.alloc(n_groups * size_t(dims) * 8));
+    P_TRY(d_dop.alloc(n_groups * 8));
+    P_TRY(d_snr_out.alloc(n_groups * 8));
+    P_TRY(d_status.alloc(n_groups * 4));
+    P_TRY(d_iters.alloc(n_groups * 4));
+    P_TRY(hipEventRecord(ev[0].e, s));
+    P_TRY(hipMemcpy(d_ptr.p, group_ptr, (n_groups + 1) * 8, hipMemcpyHostToDevice));
+    if (n_rows) {
+        P_TRY(hipMemcpy(d_rx0.p, row_rx0, n_rows * 4, hipMemcpyHostToDevice));
+        P_TRY(hipMemcpy(d_rx1.p, row_rx1, n_rows * 4, hipMemcpyHostToDevice));
+        P_TRY(hipMemcpy(d_tdoa.p, row_tdoa, n_rows * 8, hipMemcpyHostToDevice));
+        P_TRY(hipMemcpy(d_snr.p, row_snr, n_rows * 8, hipMemcpyHostToDevice));
+    }
+    P_TRY(hipMemcpy(d_xy.p, rx_coords, size_t(n_rx) * size_t(dims) * 8, hipMemcpyHostToDevice));
+    P_TRY(hipEventRecord(ev[1].e, s));
+
+    if (dims == 1)
+        hipLaunchKernelGGL(k_pos1d, dim3(unsigned((n_groups + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                           d_ptr.as<long long>(), d_rx0.as<int>(), d_rx1.as<int>(), d_tdoa.as<double>(), d_snr.as<double>(),
+                           d_xy.as<double>(), ng, first, second, d_pos.as<double>(), d_dop.as<double>(),
+                           d_snr_out.as<double>(), d_status.as<int>(), d_iters.as<int>());
+    else
+        hipLaunchKernelGGL(k_pos2d, dim3(unsigned((n_groups + kTeams - 1) / kTeams)), dim3(kBlock), 0, s,
+                           d_ptr.as<long long>(), d_rx0.as<int>(), d_rx1.as<int>(), d_tdoa.as<double>(), d_snr.as<double>(),
+                           d_xy.as<double>(), ng, start[0], start[1], lo[0], lo[1], hi[0], hi[1], max_iter,
+                           d_pos.as<double>(), d_dop.as<double>(), d_snr_out.as<double>(), d_status.as<int>(),
+                           d_iters.as<int>());
+    P_TRY(hipGetLastError());
+    P_TRY(hipEventRecord(ev[2].e, s));
+
+    P_TRY(hipMemcpy(pos_out, d_pos.p, n_groups * size_t(dims) * 8, hipMemcpyDeviceToHost));
+    P_TRY(hipMemcpy(dop_out, d_dop.p, n_groups * 8, hipMemcpyDeviceToHost));
+    P_TRY(hipMemcpy(snr_out, d_snr_out.p, n_groups * 8, hipMemcpyDeviceToHost));
+    P_TRY(hipMemcpy(status_out, d_status.p, n_groups * 4, hipMemcpyDeviceToHost));
+    P_TRY(hipMemcpy(iters_out, d_iters.p, n_groups * 4, hipMemcpyDeviceToHost));
+    P_TRY(hipEventRecord(ev[3].e, s));
+    P_TRY(hipEventSynchronize(ev[3].e));
+    for (int k = 0; k < 3; ++k) {
+        float ms = 0;
+        P_TRY(hipEventElapsedTime(&ms, ev[k].e, ev[k + 1].e));
+        g_times_ms[k] = ms;
+    }
+    return THR_OK;
+} catch (...) {
+    return thr::on_exception("thr_pos");
+}
+
+extern "C" int thr_debug_pos_times(double* ms_out) try {
+    if (!ms_out) return thr::fail_msg(THR_ERR_ARG, "thr_debug_pos_times: null argument");
+    for (int k = 0; k < 3; ++k) ms_out[k] = g_times_ms[k];
+    return THR_OK;
+} catch (...) {
+    return thr::on_exception("thr_debug_pos_times");
+}
