@@ -64,7 +64,9 @@ extern "C" {
  *    within 11, a pure addition (no existing entry point or struct changes, the number stays):
  *    + thr_match / thr_debug_match_times -- the reference's `thrifty match` (matchmaker.py:17-79)
  *    + thr_tdoa / thr_debug_tdoa_times -- the reference's `thrifty tdoa` (tdoa_est.py:43-105, 234-303)
- *    + thr_pos / thr_debug_pos_times -- the reference's `thrifty pos` (pos_est.py:31-156) */
+ *    + thr_pos / thr_debug_pos_times -- the reference's `thrifty pos` (pos_est.py:31-156)
+ *    + thr_postdetect / thr_post_fetch / thr_post_free / thr_debug_post_times -- identify, match, tdoa and
+ *      pos in one call with device-resident intermediates (the reference's kitchen_sink.postdetect) */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -942,6 +944,85 @@ int thr_pos(int device_id, size_t n_groups, const int64_t* group_ptr, const int3
             double* pos_out, double* dop_out, double* snr_out, int32_t* status_out, int32_t* iters_out);
 /* Milliseconds of the calling thread's last thr_pos: {copies in, kernels, copies out} (HIP events). */
 int thr_debug_pos_times(double* ms_out /* [3] */);
+
+/* ---- the post-detect chain: identify -> match -> tdoa -> pos in ONE call (kitchen_sink.postdetect).
+ * The raw detection columns of all receivers go in once; the four stages run back to back on the device
+ * (the kernels of thr_identify, thr_match, thr_tdoa and thr_pos, in their order) and every intermediate
+ * stays there: between two stages only the scalar counts that size the next stage's buffers come back,
+ * plus thr_match's verdict on the timestamp order (and, in automatic mode, thr_identify's per-receiver
+ * histogram of carrier bins, a few thousand counters).  No column returns until thr_post_fetch.
+ *
+ * Index spaces: txid and keep are per INPUT detection; kept_order maps the toads order (the kept
+ * detections by timestamp) to input indices; everything else -- matches, misses, collisions, row_det,
+ * failures -- indexes the toads order, as the staged calls do when they are fed the kept detections.
+ * row_rx holds indices into rx_ids.  A stage that produces nothing (nothing kept, no match, no mobile
+ * detection pair, no row) leaves the later stages at their n == 0 case: nothing is launched for them.
+ *
+ * Errors (THR_ERR_ARG): a null pointer, rx_ids / beacon_ids not strictly ascending, n_rx outside 1..64,
+ * dims other than 1 or 2 (1-D takes two receivers), deg outside 1..3, a non-finite coordinate or x0, a
+ * negative window, n_beacons, min_match or max_iter -- all before the device is queried; timestamps that
+ * decrease or hold a NaN after the identify sort (thr_match's sentence); a detection of a match whose
+ * receiver rx_ids lacks ("... detection D is of receiver R ...").  */
+typedef struct thr_post_settings {
+    const thr_freq_range* map;   /* n_map rows in map order; n_map == 0: automatic windows */
+    size_t n_map;
+    double match_window;
+    int32_t min_match;
+    int32_t n_rx;
+    const int32_t* rx_ids;       /* [n_rx] strictly ascending */
+    int32_t dims;
+    int32_t n_beacons;
+    const double* rx_coords;     /* [n_rx][dims], rows in rx_ids order */
+    int32_t first_two_rx[2];     /* 1-D: indices into rx_ids of the receiver table's first two entries */
+    const int32_t* beacon_ids;   /* [n_beacons] strictly ascending */
+    const double* dist;          /* [n_rx][n_beacons] receiver-to-beacon distances */
+    double tdoa_window;
+    double sample_rate;
+    int32_t deg;
+    int32_t max_iter;
+    double x0[2];
+    int32_t tdoa_as_text;        /* nonzero: the position stage reads every tdoa as (tdoa * 1e9) / 1e9, the value a
+                                  * reader of the .tdoa text (nanoseconds) gets -- what `thrifty pos` works on */
+    int32_t reserved;            /* 0 */
+} thr_post_settings;
+typedef struct thr_post_counts {
+    size_t kept, matches, match_entries, misses, collisions, tasks, rows, groups, failures;
+} thr_post_counts;
+typedef struct thr_post thr_post;
+/* what thr_post_fetch copies: element type and count in terms of n (input detections) and thr_post_counts */
+#define THR_POST_TXID 0         /* int32[n] */
+#define THR_POST_KEEP 1         /* uint8[n] */
+#define THR_POST_KEPT_ORDER 2   /* int64[kept] */
+#define THR_POST_MATCH_PTR 3    /* int64[matches + 1] */
+#define THR_POST_MATCH_IDX 4    /* int64[match_entries] */
+#define THR_POST_MISSES 5       /* int64[misses] */
+#define THR_POST_COLLISIONS 6   /* int64[collisions][2] */
+#define THR_POST_ROW_RX 7       /* int32[rows][2], indices into rx_ids */
+#define THR_POST_ROW_DET 8      /* int64[rows][2] */
+#define THR_POST_ROW_VAL 9      /* float64[rows][3]: tdoa, snr, model_quality */
+#define THR_POST_GROUP_ID 10    /* int64[groups]: the match a group came from */
+#define THR_POST_GROUP_PTR 11   /* int64[groups + 1] */
+#define THR_POST_GROUP_TS 12    /* float64[groups]: timestamp of the match's first detection */
+#define THR_POST_GROUP_TX 13    /* int32[groups]: its txid */
+#define THR_POST_FAILURES 14    /* int64[failures][2] */
+#define THR_POST_N_WINDOW 15    /* int32[tasks] */
+#define THR_POST_N_KEPT 16      /* int32[tasks] */
+#define THR_POST_POS 17         /* float64[groups][dims] */
+#define THR_POST_DOP 18         /* float64[groups] */
+#define THR_POST_SNR 19         /* float64[groups] */
+#define THR_POST_STATUS 20      /* int32[groups], THR_POS_* */
+#define THR_POST_ITERS 21       /* int32[groups] */
+#define THR_POST_N_OUTPUTS 22
+int thr_postdetect(int device_id, size_t n, const int32_t* rxid, const int32_t* block, const double* timestamp,
+                   const int32_t* carrier_bin, const double* carrier_offset, const double* soa,
+                   const double* energy, const double* noise, const thr_post_settings* settings,
+                   thr_post** result_out, thr_post_counts* counts_out);
+/* Copies output `which` to dst; dst_bytes must be its exact size (THR_ERR_ARG otherwise). */
+int thr_post_fetch(thr_post* result, int which, void* dst, size_t dst_bytes);
+void thr_post_free(thr_post* result);
+/* Milliseconds of the calling thread's last thr_postdetect: {copies in, identify, match, tdoa, pos, copies
+ * out} (HIP events); the last slot adds up the thr_post_fetch calls made since. */
+int thr_debug_post_times(double* ms_out /* [6] */);
 
 #ifdef __cplusplus
 }

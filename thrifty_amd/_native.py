@@ -42,6 +42,7 @@ EXPORTS = [
     "thr_match", "thr_debug_match_times",
     "thr_tdoa", "thr_debug_tdoa_times",
     "thr_pos", "thr_debug_pos_times",
+    "thr_postdetect", "thr_post_fetch", "thr_post_free", "thr_debug_post_times",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -124,6 +125,21 @@ RECORD_DTYPE = np.dtype([
     ("corr_energy", "<f4"), ("corr_noise", "<f4"), ("reserved", "<u8"),
 ])
 assert RECORD_DTYPE.itemsize == 64
+
+
+class ThrPostSettings(C.Structure):       # thr_post_settings
+    _fields_ = [("map", C.c_void_p), ("n_map", C.c_size_t), ("match_window", C.c_double), ("min_match", C.c_int32),
+                ("n_rx", C.c_int32), ("rx_ids", C.c_void_p), ("dims", C.c_int32), ("n_beacons", C.c_int32),
+                ("rx_coords", C.c_void_p), ("first_two_rx", C.c_int32 * 2), ("beacon_ids", C.c_void_p),
+                ("dist", C.c_void_p), ("tdoa_window", C.c_double), ("sample_rate", C.c_double), ("deg", C.c_int32),
+                ("max_iter", C.c_int32), ("x0", C.c_double * 2), ("tdoa_as_text", C.c_int32), ("reserved", C.c_int32)]
+
+
+POST_COUNTS = ("kept", "matches", "match_entries", "misses", "collisions", "tasks", "rows", "groups", "failures")
+
+
+class ThrPostCounts(C.Structure):         # thr_post_counts
+    _fields_ = [(name, C.c_size_t) for name in POST_COUNTS]
 
 
 class NativeError(RuntimeError):
@@ -260,6 +276,12 @@ def load_library():
     lib.thr_debug_tdoa_times.argtypes = [C.POINTER(C.c_double)]
     lib.thr_pos.argtypes = [C.c_int, C.c_size_t, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     lib.thr_debug_pos_times.argtypes = [C.POINTER(C.c_double)]
+    lib.thr_postdetect.argtypes = ([C.c_int, C.c_size_t] + [vp] * 8 +
+                                   [C.POINTER(ThrPostSettings), C.POINTER(vp), C.POINTER(ThrPostCounts)])
+    lib.thr_post_fetch.argtypes = [vp, C.c_int, vp, C.c_size_t]
+    lib.thr_post_free.argtypes = [vp]
+    lib.thr_post_free.restype = None
+    lib.thr_debug_post_times.argtypes = [C.POINTER(C.c_double)]
     _lib = lib
     return lib
 
@@ -1198,4 +1220,97 @@ def pos_times():
     lib = load_library()
     ms = (C.c_double * 3)()
     _check(lib, lib.thr_debug_pos_times(ms))
+    return tuple(ms)
+
+
+POST_WORKGROUP = 256            # kBlock of csrc/postdetect.hip: the workgroup size of the chain's own kernels
+POST_MAX_RECEIVERS = 64         # kMaxReceivers of csrc/postdetect.hip (pos.hip's limit)
+# THR_POST_*: name -> (index, dtype, shape as a function of n, the counts and dims)
+POST_OUTPUTS = {
+    "txid": (0, np.int32, lambda n, c, d: (n,)),
+    "keep": (1, np.uint8, lambda n, c, d: (n,)),
+    "kept_order": (2, np.int64, lambda n, c, d: (c["kept"],)),
+    "match_ptr": (3, np.int64, lambda n, c, d: (c["matches"] + 1,)),
+    "match_idx": (4, np.int64, lambda n, c, d: (c["match_entries"],)),
+    "misses": (5, np.int64, lambda n, c, d: (c["misses"],)),
+    "collisions": (6, np.int64, lambda n, c, d: (c["collisions"], 2)),
+    "row_rx": (7, np.int32, lambda n, c, d: (c["rows"], 2)),
+    "row_det": (8, np.int64, lambda n, c, d: (c["rows"], 2)),
+    "row_val": (9, np.float64, lambda n, c, d: (c["rows"], 3)),
+    "group_id": (10, np.int64, lambda n, c, d: (c["groups"],)),
+    "group_ptr": (11, np.int64, lambda n, c, d: (c["groups"] + 1,)),
+    "group_timestamp": (12, np.float64, lambda n, c, d: (c["groups"],)),
+    "group_tx": (13, np.int32, lambda n, c, d: (c["groups"],)),
+    "failures": (14, np.int64, lambda n, c, d: (c["failures"], 2)),
+    "n_window": (15, np.int32, lambda n, c, d: (c["tasks"],)),
+    "n_kept": (16, np.int32, lambda n, c, d: (c["tasks"],)),
+    "pos": (17, np.float64, lambda n, c, d: (c["groups"], d)),
+    "dop": (18, np.float64, lambda n, c, d: (c["groups"],)),
+    "snr": (19, np.float64, lambda n, c, d: (c["groups"],)),
+    "status": (20, np.int32, lambda n, c, d: (c["groups"],)),
+    "iters": (21, np.int32, lambda n, c, d: (c["groups"],)),
+}
+
+
+def post_settings(freq_ranges, match_window, min_match, rx_ids, rx_coords, first_two_rx, beacon_ids, dist, tdoa_window,
+                  sample_rate, deg=2, x0=(0.1, 0.1), max_iter=100, tdoa_as_text=False):
+    """(ThrPostSettings, the arrays it points into -- keep them alive as long as the struct)."""
+    fmap = (np.zeros(0, dtype=FREQ_RANGE_DTYPE) if freq_ranges is None
+            else np.ascontiguousarray(np.asarray(freq_ranges, dtype=FREQ_RANGE_DTYPE)))
+    if freq_ranges is not None and len(fmap) == 0:
+        raise ValueError("empty frequency map")
+    ids = np.ascontiguousarray(rx_ids, dtype=np.int32)
+    xy = np.ascontiguousarray(rx_coords, dtype=np.float64)
+    beacons = np.ascontiguousarray(beacon_ids, dtype=np.int32)
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    if ids.ndim != 1 or xy.ndim != 2 or len(xy) != len(ids) or beacons.ndim != 1 or dist.shape != (len(ids), len(beacons)):
+        raise ValueError("postdetect: rx_ids, rx_coords, beacon_ids or dist have the wrong shape")
+    st = ThrPostSettings()
+    st.map, st.n_map = (fmap.ctypes.data if len(fmap) else None), len(fmap)
+    st.match_window, st.min_match = float(match_window), int(min_match)
+    st.n_rx, st.rx_ids, st.dims, st.rx_coords = len(ids), ids.ctypes.data, xy.shape[1], xy.ctypes.data
+    st.first_two_rx[0], st.first_two_rx[1] = int(first_two_rx[0]), int(first_two_rx[1])
+    st.n_beacons, st.beacon_ids, st.dist = len(beacons), beacons.ctypes.data, dist.ctypes.data
+    st.tdoa_window, st.sample_rate, st.deg, st.max_iter = float(tdoa_window), float(sample_rate), int(deg), int(max_iter)
+    st.x0[0], st.x0[1] = float(x0[0]), float(x0[1])
+    st.tdoa_as_text = 1 if tdoa_as_text else 0
+    return st, (fmap, ids, xy, beacons, dist)
+
+
+def postdetect(rxid, block, timestamp, carrier_bin, carrier_offset, soa, energy, noise, settings, outputs=None,
+               device_id=0):
+    """thr_postdetect on the raw detection columns of all receivers -> (counts dict, {name: array}) with
+    every output of POST_OUTPUTS (or those named in `outputs`) fetched.  `settings`: post_settings()'s
+    pair.  ValueError for what thr_postdetect refuses."""
+    lib = load_library()
+    st, _alive = settings
+    cols = [np.ascontiguousarray(col, dtype=kind) for col, kind in (
+        (rxid, np.int32), (block, np.int32), (timestamp, np.float64), (carrier_bin, np.int32),
+        (carrier_offset, np.float64), (soa, np.float64), (energy, np.float64), (noise, np.float64))]
+    n = len(cols[0])
+    if any(col.ndim != 1 or len(col) != n for col in cols):
+        raise ValueError("postdetect: the detection columns differ in length")
+    handle, counts = C.c_void_p(), ThrPostCounts()
+    rc = lib.thr_postdetect(int(device_id), n, *[col.ctypes.data for col in cols], C.byref(st), C.byref(handle),
+                            C.byref(counts))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    try:
+        c = {name: int(getattr(counts, name)) for name in POST_COUNTS}
+        out = {}
+        for name in (POST_OUTPUTS if outputs is None else outputs):
+            which, kind, shape = POST_OUTPUTS[name]
+            out[name] = np.zeros(shape(n, c, int(st.dims)), dtype=kind)
+            _check(lib, lib.thr_post_fetch(handle, which, out[name].ctypes.data, out[name].nbytes))
+    finally:
+        lib.thr_post_free(handle)
+    return c, out
+
+
+def post_times():
+    """{copies in, identify, match, tdoa, pos, copies out} of this thread's last postdetect(), milliseconds."""
+    lib = load_library()
+    ms = (C.c_double * 6)()
+    _check(lib, lib.thr_debug_post_times(ms))
     return tuple(ms)

@@ -12,8 +12,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libthriftyhip.so")
-SOURCES = ["handle.hip", "window.hip", "pipeline.hip", "entry.hip", "text.hip", "detect16k.hip", "detect16k_geom0.hip", "detect16k_geom1.hip", "detect16k_geom2.hip", "detect16k_carrier.hip", "detect16k_preshift.hip", "detect16k_sec.hip", "detect_seg.hip", "detect_long.hip", "detect_small.hip", "generic.hip", "card_ingest.hip", "identify.hip", "run_file.hip", "card_gate.hip", "run_gate.hip", "template_extract.hip", "run_extract.hip", "match.hip", "tdoa.hip", "pos.hip"]
-HEADERS = ["host_internal.hpp", "correlate16k.hpp", "correlate16k_geom.hpp", "detect_common.hpp", "fft_regs.hpp", "kernel_util.hpp", "lmdif8.hpp", "passes_w8.hpp", "card_gate.hpp", "template_extract.hpp", os.path.join("..", "..", "include", "thrifty_hip.h")]
+SOURCES = ["handle.hip", "window.hip", "pipeline.hip", "entry.hip", "text.hip", "detect16k.hip", "detect16k_geom0.hip", "detect16k_geom1.hip", "detect16k_geom2.hip", "detect16k_carrier.hip", "detect16k_preshift.hip", "detect16k_sec.hip", "detect_seg.hip", "detect_long.hip", "detect_small.hip", "generic.hip", "card_ingest.hip", "identify.hip", "run_file.hip", "card_gate.hip", "run_gate.hip", "template_extract.hip", "run_extract.hip", "match.hip", "tdoa.hip", "pos.hip", "postdetect.hip"]
+HEADERS = ["host_internal.hpp", "correlate16k.hpp", "correlate16k_geom.hpp", "detect_common.hpp", "fft_regs.hpp", "kernel_util.hpp", "lmdif8.hpp", "passes_w8.hpp", "card_gate.hpp", "template_extract.hpp", "post_stages.hpp", os.path.join("..", "..", "include", "thrifty_hip.h")]
 HOST_ONLY = ("handle.hip", "window.hip", "pipeline.hip", "entry.hip", "text.hip", "run_file.hip", "run_gate.hip", "run_extract.hip",
              "host_internal.hpp")     # no kernels: not part of csrc_hash()
 # kernels that none of the workloads of profiles/hbm_traffic.json launches (the carrier gate's verdict and
@@ -28,6 +28,8 @@ UNPROFILED_MATCH = ("match.hip",)
 UNPROFILED_TDOA = ("tdoa.hip",)
 # and for the position solver (thr_pos)
 UNPROFILED_POS = ("pos.hip",)
+# and for the post-detect chain (thr_postdetect) and the header its four stage cores are declared in
+UNPROFILED_POST = ("postdetect.hip", "post_stages.hpp")
 # per-file code-generation flags (measured on MI355X, see csrc/detect16k_carrier.hip)
 PER_FILE_FLAGS = {"detect16k_carrier.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                   # the work cursor's atomicAdd stays ONE lane's atomic whose result is waited for where it is
@@ -69,11 +71,11 @@ def _hipcc():
 
 def csrc_hash():
     """sha256 (first 16 hex digits) over the kernel sources and headers (everything but the host
-    side, HOST_ONLY, and the kernels no profiled workload launches, UNPROFILED / UNPROFILED_EXTRACT / UNPROFILED_MATCH / UNPROFILED_TDOA / UNPROFILED_POS): profiles/hbm_traffic.json records the hash its counter passes were taken on,
+    side, HOST_ONLY, and the kernels no profiled workload launches, UNPROFILED / UNPROFILED_EXTRACT / UNPROFILED_MATCH / UNPROFILED_TDOA / UNPROFILED_POS / UNPROFILED_POST): profiles/hbm_traffic.json records the hash its counter passes were taken on,
     bench.py flags a mismatch (`traffic_stale`)."""
     import hashlib
     h = hashlib.sha256()
-    skipped = UNPROFILED + UNPROFILED_EXTRACT + UNPROFILED_MATCH + UNPROFILED_TDOA + UNPROFILED_POS
+    skipped = UNPROFILED + UNPROFILED_EXTRACT + UNPROFILED_MATCH + UNPROFILED_TDOA + UNPROFILED_POS + UNPROFILED_POST
     for name in sorted([x for x in SOURCES if x not in HOST_ONLY + skipped] +
                        [x for x in HEADERS if not x.startswith("..") and x not in skipped]):
         h.update(name.encode())

@@ -16,13 +16,11 @@
 #include <vector>
 
 #include "../../include/thrifty_hip.h"
-
-namespace thr {
-int fail_msg(int code, const char* fmt, ...);
-int on_exception(const char* who) noexcept;  // handle.hip
-}
+#include "post_stages.hpp"
 
 namespace {
+
+using thr::DevBuf;
 
 // order-preserving maps to unsigned keys
 __device__ __forceinline__ unsigned key_i32(int v) { return unsigned(v) ^ 0x80000000u; }
@@ -111,22 +109,7 @@ __global__ void k_widen(const unsigned* __restrict__ in, int n, long long* __res
     if (i < n) out[i] = (long long)in[i];
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T>
-    T* as() { return static_cast<T*>(p); }
-};
-
-#define ID_TRY(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return thr::fail_msg(THR_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
+#define ID_TRY THR_HIP_TRY
 
 template <class K>
 hipError_t sort_pass(DevBuf& tmp, size_t& tmp_bytes, K* keys_in, K* keys_out, unsigned* val_in,
@@ -136,8 +119,6 @@ hipError_t sort_pass(DevBuf& tmp, size_t& tmp_bytes, K* keys_in, K* keys_out, un
                                                       val_out, n, 0, int(sizeof(K) * 8), s);
     if (e != hipSuccess) return e;
     if (need > tmp_bytes) {
-        if (tmp.p) (void)hipFree(tmp.p);
-        tmp.p = nullptr;
         if ((e = tmp.alloc(need)) != hipSuccess) return e;
         tmp_bytes = need;
     }
@@ -178,61 +159,34 @@ std::vector<double> window_edges(const unsigned* cnts, int n_bins, int first_bin
 
 }  // namespace
 
-extern "C" int thr_identify(int device_id, size_t n_in, const int32_t* rxid, const int32_t* block,
-                            const double* timestamp, const int32_t* carrier_bin,
-                            const double* carrier_offset, const double* energy,
-                            const thr_freq_range* map, size_t n_map, int32_t* txid_out,
-                            uint8_t* keep_out, int64_t* kept_order_out, size_t* n_kept_out) try {
-    if (n_kept_out) *n_kept_out = 0;
-    if (n_in == 0) return THR_OK;
-    if (!rxid || !block || !timestamp || !carrier_bin || !carrier_offset || !energy || !txid_out ||
-        !keep_out || !kept_order_out || !n_kept_out)
-        return thr::fail_msg(THR_ERR_ARG, "thr_identify: null argument");
-    if (n_in > size_t(1) << 28) return thr::fail_msg(THR_ERR_ARG, "thr_identify: too many detections");
-    if (n_map > 0 && !map) return thr::fail_msg(THR_ERR_ARG, "thr_identify: null frequency map");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return thr::fail_msg(THR_ERR_DEVICE, "no HIP device available (this engine has no CPU fallback)");
-    if (device_id < 0 || device_id >= ndev) return thr::fail_msg(THR_ERR_ARG, "bad device_id %d", device_id);
-    ID_TRY(hipSetDevice(device_id));
-    const int n = int(n_in);
+// The stage on device pointers (post_stages.hpp): every kernel of the identify step.  thr_identify below
+// is argument checks, copies in, this, copies out; thr_postdetect (postdetect.hip) calls it too.
+int thr::identify_core(int n, const int* d_rx, const int* d_blk, const double* d_ts, const int* d_bin,
+                       const double* d_off, const double* d_en, const int32_t* h_rxid, const int32_t* h_bin,
+                       const thr_freq_range* map, size_t n_map, hipStream_t s, IdentifyOut& out) {
     const dim3 blk(256), grid((n + 255) / 256);
-    hipStream_t s = nullptr;
-
-    DevBuf d_rx, d_blk, d_ts, d_bin, d_off, d_en, d_tx, d_keep, d_flag;
-    ID_TRY(d_rx.alloc(size_t(n) * 4));
-    ID_TRY(d_blk.alloc(size_t(n) * 4));
-    ID_TRY(d_ts.alloc(size_t(n) * 8));
-    ID_TRY(d_bin.alloc(size_t(n) * 4));
-    ID_TRY(d_off.alloc(size_t(n) * 8));
-    ID_TRY(d_en.alloc(size_t(n) * 8));
-    ID_TRY(d_tx.alloc(size_t(n) * 4));
-    ID_TRY(d_keep.alloc(n));
+    DevBuf d_flag;
+    ID_TRY(out.txid.alloc(size_t(n) * 4));
+    ID_TRY(out.keep.alloc(n));
     ID_TRY(d_flag.alloc(n));
-    ID_TRY(hipMemcpy(d_rx.p, rxid, size_t(n) * 4, hipMemcpyHostToDevice));
-    ID_TRY(hipMemcpy(d_blk.p, block, size_t(n) * 4, hipMemcpyHostToDevice));
-    ID_TRY(hipMemcpy(d_ts.p, timestamp, size_t(n) * 8, hipMemcpyHostToDevice));
-    ID_TRY(hipMemcpy(d_bin.p, carrier_bin, size_t(n) * 4, hipMemcpyHostToDevice));
-    ID_TRY(hipMemcpy(d_off.p, carrier_offset, size_t(n) * 8, hipMemcpyHostToDevice));
-    ID_TRY(hipMemcpy(d_en.p, energy, size_t(n) * 8, hipMemcpyHostToDevice));
 
     // ---- 1. transmitter ids
     if (n_map > 0) {
         DevBuf d_map;
         ID_TRY(d_map.alloc(n_map * sizeof(thr_freq_range)));
         ID_TRY(hipMemcpy(d_map.p, map, n_map * sizeof(thr_freq_range), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_classify_map, grid, blk, 0, s, d_rx.as<int>(), d_bin.as<int>(),
-                           d_off.as<double>(), n, d_map.as<thr_freq_range>(), int(n_map), d_tx.as<int>());
+        hipLaunchKernelGGL(k_classify_map, grid, blk, 0, s, d_rx, d_bin,
+                           d_off, n, d_map.as<thr_freq_range>(), int(n_map), out.txid.as<int>());
         ID_TRY(hipGetLastError());
         ID_TRY(hipDeviceSynchronize());  // d_map goes out of scope
     } else {
         // receivers and the overall bin range (host: two cheap passes over the caller's columns)
-        std::vector<int> rx_list(rxid, rxid + n);
+        std::vector<int> rx_list(h_rxid, h_rxid + n);
         std::sort(rx_list.begin(), rx_list.end());
         rx_list.erase(std::unique(rx_list.begin(), rx_list.end()), rx_list.end());
         const int n_rx = int(rx_list.size());
-        const int bin_lo = *std::min_element(carrier_bin, carrier_bin + n);
-        const int bin_hi = *std::max_element(carrier_bin, carrier_bin + n);
+        const int bin_lo = *std::min_element(h_bin, h_bin + n);
+        const int bin_hi = *std::max_element(h_bin, h_bin + n);
         const long long span = (long long)bin_hi - bin_lo + 1;
         if (span * n_rx > (1ll << 26))
             return thr::fail_msg(THR_ERR_ARG, "thr_identify: carrier bins span %lld x %d receivers", span, n_rx);
@@ -242,7 +196,7 @@ extern "C" int thr_identify(int device_id, size_t n_in, const int32_t* rxid, con
         ID_TRY(d_hist.alloc(size_t(n_rx) * n_bins * 4));
         ID_TRY(hipMemcpy(d_rxl.p, rx_list.data(), n_rx * 4, hipMemcpyHostToDevice));
         ID_TRY(hipMemset(d_hist.p, 0, size_t(n_rx) * n_bins * 4));
-        hipLaunchKernelGGL(k_histogram, grid, blk, 0, s, d_rx.as<int>(), d_bin.as<int>(), n,
+        hipLaunchKernelGGL(k_histogram, grid, blk, 0, s, d_rx, d_bin, n,
                            d_rxl.as<int>(), n_rx, bin_lo, n_bins, d_hist.as<unsigned>());
         ID_TRY(hipGetLastError());
         std::vector<unsigned> hist(size_t(n_rx) * n_bins);
@@ -263,8 +217,8 @@ extern "C" int thr_identify(int device_id, size_t n_in, const int32_t* rxid, con
         ID_TRY(d_eptr.alloc(eptr.size() * 4));
         ID_TRY(hipMemcpy(d_edges.p, edges.data(), edges.size() * 8, hipMemcpyHostToDevice));
         ID_TRY(hipMemcpy(d_eptr.p, eptr.data(), eptr.size() * 4, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_digitize, grid, blk, 0, s, d_rx.as<int>(), d_bin.as<int>(), n,
-                           d_rxl.as<int>(), n_rx, d_edges.as<double>(), d_eptr.as<int>(), d_tx.as<int>());
+        hipLaunchKernelGGL(k_digitize, grid, blk, 0, s, d_rx, d_bin, n,
+                           d_rxl.as<int>(), n_rx, d_edges.as<double>(), d_eptr.as<int>(), out.txid.as<int>());
         ID_TRY(hipGetLastError());
         ID_TRY(hipDeviceSynchronize());
     }
@@ -281,46 +235,85 @@ extern "C" int thr_identify(int device_id, size_t n_in, const int32_t* rxid, con
     ID_TRY(d_pts.alloc(size_t(n) * 4));
     unsigned *pa = d_pa.as<unsigned>(), *pb = d_pb.as<unsigned>();
     hipLaunchKernelGGL(k_iota, grid, blk, 0, s, pa, n);
-    hipLaunchKernelGGL(k_keys_f64, grid, blk, 0, s, d_ts.as<double>(), pa, n, d_k64a.as<unsigned long long>());
+    hipLaunchKernelGGL(k_keys_f64, grid, blk, 0, s, d_ts, pa, n, d_k64a.as<unsigned long long>());
     ID_TRY(sort_pass(d_tmp, tmp_bytes, d_k64a.as<unsigned long long>(), d_k64b.as<unsigned long long>(), pa, pb, n, s));
     ID_TRY(hipMemcpyAsync(d_pts.p, pb, size_t(n) * 4, hipMemcpyDeviceToDevice, s));  // order by timestamp alone
     std::swap(pa, pb);
-    for (const int* col : {d_blk.as<int>(), d_tx.as<int>(), d_rx.as<int>()}) {
+    for (const int* col : {d_blk, out.txid.as<const int>(), d_rx}) {
         hipLaunchKernelGGL(k_keys_i32, grid, blk, 0, s, col, pa, n, d_k32a.as<unsigned>());
         ID_TRY(sort_pass(d_tmp, tmp_bytes, d_k32a.as<unsigned>(), d_k32b.as<unsigned>(), pa, pb, n, s));
         std::swap(pa, pb);
     }
 
     // ---- 3. neighbour test in sorted order, 4. kept detections in timestamp order
-    hipLaunchKernelGGL(k_dup_mask, grid, blk, 0, s, pa, d_blk.as<int>(), d_en.as<double>(),
-                       d_tx.as<int>(), n, d_keep.as<unsigned char>());
-    hipLaunchKernelGGL(k_flags_in_order, grid, blk, 0, s, d_pts.as<unsigned>(), d_keep.as<unsigned char>(),
+    hipLaunchKernelGGL(k_dup_mask, grid, blk, 0, s, pa, d_blk, d_en,
+                       out.txid.as<int>(), n, out.keep.as<unsigned char>());
+    hipLaunchKernelGGL(k_flags_in_order, grid, blk, 0, s, d_pts.as<unsigned>(), out.keep.as<unsigned char>(),
                        n, d_flag.as<unsigned char>());
     ID_TRY(hipGetLastError());
-    DevBuf d_sel, d_nsel, d_wide;
+    DevBuf d_sel, d_nsel;
     ID_TRY(d_sel.alloc(size_t(n) * 4));
     ID_TRY(d_nsel.alloc(4));
-    ID_TRY(d_wide.alloc(size_t(n) * 8));
+    ID_TRY(out.kept_order.alloc(size_t(n) * 8));
     {
         size_t need = 0;
         ID_TRY(hipcub::DeviceSelect::Flagged(nullptr, need, d_pts.as<unsigned>(), d_flag.as<unsigned char>(),
                                              d_sel.as<unsigned>(), d_nsel.as<int>(), n, s));
         if (need > tmp_bytes) {
-            if (d_tmp.p) (void)hipFree(d_tmp.p);
-            d_tmp.p = nullptr;
             ID_TRY(d_tmp.alloc(need));
             tmp_bytes = need;
         }
         ID_TRY(hipcub::DeviceSelect::Flagged(d_tmp.p, need, d_pts.as<unsigned>(), d_flag.as<unsigned char>(),
                                              d_sel.as<unsigned>(), d_nsel.as<int>(), n, s));
     }
-    hipLaunchKernelGGL(k_widen, grid, blk, 0, s, d_sel.as<unsigned>(), n, d_wide.as<long long>());
+    hipLaunchKernelGGL(k_widen, grid, blk, 0, s, d_sel.as<unsigned>(), n, out.kept_order.as<long long>());
     ID_TRY(hipGetLastError());
-    int n_kept = 0;
-    ID_TRY(hipMemcpy(&n_kept, d_nsel.p, 4, hipMemcpyDeviceToHost));
-    ID_TRY(hipMemcpy(txid_out, d_tx.p, size_t(n) * 4, hipMemcpyDeviceToHost));
-    ID_TRY(hipMemcpy(keep_out, d_keep.p, n, hipMemcpyDeviceToHost));
-    ID_TRY(hipMemcpy(kept_order_out, d_wide.p, size_t(n_kept) * 8, hipMemcpyDeviceToHost));
+    ID_TRY(hipMemcpy(&out.n_kept, d_nsel.p, 4, hipMemcpyDeviceToHost));
+    return THR_OK;
+}
+
+extern "C" int thr_identify(int device_id, size_t n_in, const int32_t* rxid, const int32_t* block,
+                            const double* timestamp, const int32_t* carrier_bin,
+                            const double* carrier_offset, const double* energy,
+                            const thr_freq_range* map, size_t n_map, int32_t* txid_out,
+                            uint8_t* keep_out, int64_t* kept_order_out, size_t* n_kept_out) try {
+    if (n_kept_out) *n_kept_out = 0;
+    if (n_in == 0) return THR_OK;
+    if (!rxid || !block || !timestamp || !carrier_bin || !carrier_offset || !energy || !txid_out ||
+        !keep_out || !kept_order_out || !n_kept_out)
+        return thr::fail_msg(THR_ERR_ARG, "thr_identify: null argument");
+    if (n_in > size_t(1) << 28) return thr::fail_msg(THR_ERR_ARG, "thr_identify: too many detections");
+    if (n_map > 0 && !map) return thr::fail_msg(THR_ERR_ARG, "thr_identify: null frequency map");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return thr::fail_msg(THR_ERR_DEVICE, "no HIP device available (this engine has no CPU fallback)");
+    if (device_id < 0 || device_id >= ndev) return thr::fail_msg(THR_ERR_ARG, "bad device_id %d", device_id);
+    ID_TRY(hipSetDevice(device_id));
+    const int n = int(n_in);
+    hipStream_t s = nullptr;
+
+    DevBuf d_rx, d_blk, d_ts, d_bin, d_off, d_en;
+    ID_TRY(d_rx.alloc(size_t(n) * 4));
+    ID_TRY(d_blk.alloc(size_t(n) * 4));
+    ID_TRY(d_ts.alloc(size_t(n) * 8));
+    ID_TRY(d_bin.alloc(size_t(n) * 4));
+    ID_TRY(d_off.alloc(size_t(n) * 8));
+    ID_TRY(d_en.alloc(size_t(n) * 8));
+    ID_TRY(hipMemcpy(d_rx.p, rxid, size_t(n) * 4, hipMemcpyHostToDevice));
+    ID_TRY(hipMemcpy(d_blk.p, block, size_t(n) * 4, hipMemcpyHostToDevice));
+    ID_TRY(hipMemcpy(d_ts.p, timestamp, size_t(n) * 8, hipMemcpyHostToDevice));
+    ID_TRY(hipMemcpy(d_bin.p, carrier_bin, size_t(n) * 4, hipMemcpyHostToDevice));
+    ID_TRY(hipMemcpy(d_off.p, carrier_offset, size_t(n) * 8, hipMemcpyHostToDevice));
+    ID_TRY(hipMemcpy(d_en.p, energy, size_t(n) * 8, hipMemcpyHostToDevice));
+
+    thr::IdentifyOut out;
+    const int rc = thr::identify_core(n, d_rx.as<int>(), d_blk.as<int>(), d_ts.as<double>(), d_bin.as<int>(),
+                                      d_off.as<double>(), d_en.as<double>(), rxid, carrier_bin, map, n_map, s, out);
+    if (rc != THR_OK) return rc;
+    const int n_kept = out.n_kept;
+    ID_TRY(hipMemcpy(txid_out, out.txid.p, size_t(n) * 4, hipMemcpyDeviceToHost));
+    ID_TRY(hipMemcpy(keep_out, out.keep.p, n, hipMemcpyDeviceToHost));
+    ID_TRY(hipMemcpy(kept_order_out, out.kept_order.p, size_t(n_kept) * 8, hipMemcpyDeviceToHost));
     *n_kept_out = size_t(n_kept);
     return THR_OK;
 } catch (...) {

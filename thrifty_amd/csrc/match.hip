@@ -20,13 +20,13 @@
 #include <utility>
 
 #include "../../include/thrifty_hip.h"
-
-namespace thr {
-int fail_msg(int code, const char* fmt, ...);
-int on_exception(const char* who) noexcept;  // handle.hip
-}
+#include "post_stages.hpp"
 
 namespace {
+
+using thr::DevBuf;
+using thr::Event;
+using thr::with_temp;
 
 constexpr int kBlock = 256;  // workgroup size of every kernel here (tests/test_gpu_match_seams.py: W)
 constexpr unsigned kNone = 0xFFFFFFFFu;
@@ -221,47 +221,127 @@ __global__ void k_emit_members(const unsigned long long* __restrict__ keys, cons
     }
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T>
-    T* as() { return static_cast<T*>(p); }
-};
-struct Event {
-    hipEvent_t e = nullptr;
-    ~Event() {
-        if (e) (void)hipEventDestroy(e);
-    }
-};
-
-#define M_TRY(expr)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return thr::fail_msg(THR_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-// a hipCUB device algorithm: size query, grow the shared temporary, run
-template <class Call>
-hipError_t with_temp(DevBuf& tmp, size_t& tmp_bytes, Call call) {
-    size_t need = 0;
-    hipError_t e = call(nullptr, need);
-    if (e != hipSuccess) return e;
-    if (need > tmp_bytes) {
-        if (tmp.p) (void)hipFree(tmp.p);
-        tmp.p = nullptr;
-        if ((e = tmp.alloc(need)) != hipSuccess) return e;
-        tmp_bytes = need;
-    }
-    return call(tmp.p, need);
-}
+#define M_TRY THR_HIP_TRY
 
 thread_local double g_times_ms[3] = {0, 0, 0};  // last thr_match of this thread: copies in, kernels, copies out
 
 }  // namespace
+
+// The stage on device pointers (post_stages.hpp): every kernel of the match step and the totals.  Unsorted
+// or NaN timestamps come back as out.first_bad; the caller, who knows where the column lives, words them.
+int thr::match_core(int n, const int* d_rx, const int* d_tx, const double* d_ts, const double* d_en, double window,
+                    int min_match, hipStream_t s, MatchOut& out) {
+    const dim3 blk(kBlock), grid((n + kBlock - 1) / kBlock);
+    DevBuf d_bad;
+    M_TRY(d_bad.alloc(4));
+
+    // ---- 0. the input order
+    M_TRY(hipMemset(d_bad.p, 0xFF, 4));
+    hipLaunchKernelGGL(k_check_sorted, grid, blk, 0, s, d_ts, n, d_bad.as<unsigned>());
+    M_TRY(hipGetLastError());
+    unsigned bad = kNone;
+    M_TRY(hipMemcpy(&bad, d_bad.p, 4, hipMemcpyDeviceToHost));
+    out.first_bad = bad;
+    if (bad != kNone) return THR_OK;  // the caller words the refusal
+
+    // ---- 1. stable sort by txid: perm[p] = input index, increasing inside one txid
+    DevBuf d_k32a, d_k32b, d_iota, d_perm, d_tss, d_tmp;
+    size_t tmp_bytes = 0;
+    M_TRY(d_k32a.alloc(size_t(n) * 4));
+    M_TRY(d_k32b.alloc(size_t(n) * 4));
+    M_TRY(d_iota.alloc(size_t(n) * 4));
+    M_TRY(d_perm.alloc(size_t(n) * 4));
+    M_TRY(d_tss.alloc(size_t(n) * 8));
+    unsigned *key_s = d_k32b.as<unsigned>(), *iota = d_iota.as<unsigned>(), *perm = d_perm.as<unsigned>();
+    hipLaunchKernelGGL(k_iota, grid, blk, 0, s, iota, n);
+    hipLaunchKernelGGL(k_keys_tx, grid, blk, 0, s, d_tx, n, d_k32a.as<unsigned>());
+    M_TRY(hipGetLastError());
+    M_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
+        return hipcub::DeviceRadixSort::SortPairs(t, b, d_k32a.as<unsigned>(), key_s, iota, perm, n, 0, 32, s);
+    }));
+    hipLaunchKernelGGL(k_gather_ts, grid, blk, 0, s, d_ts, perm, n, d_tss.as<double>());
+
+    // ---- 2. next-leader pointers, leaders by pointer doubling, group numbers
+    DevBuf d_ja, d_jb, d_mark, d_gincl, d_lead;
+    M_TRY(d_ja.alloc(size_t(n) * 4));
+    M_TRY(d_jb.alloc(size_t(n) * 4));
+    M_TRY(d_mark.alloc(size_t(n) * 4));
+    M_TRY(d_gincl.alloc(size_t(n) * 4));
+    M_TRY(d_lead.alloc((size_t(n) + 1) * 4));
+    unsigned *ja = d_ja.as<unsigned>(), *jb = d_jb.as<unsigned>(), *mark = d_mark.as<unsigned>();
+    unsigned *gincl = d_gincl.as<unsigned>(), *lead_pos = d_lead.as<unsigned>();
+    hipLaunchKernelGGL(k_next_leader, grid, blk, 0, s, key_s, d_tss.as<double>(), n, window, ja, mark);
+    int log2n = 0;
+    while ((size_t(1) << log2n) < size_t(n)) ++log2n;
+    for (int round = 0; round < log2n + 1; ++round) {
+        hipLaunchKernelGGL(k_double, grid, blk, 0, s, ja, jb, mark, n);
+        std::swap(ja, jb);
+    }
+    M_TRY(hipGetLastError());
+    M_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
+        return hipcub::DeviceScan::InclusiveSum(t, b, mark, gincl, n, s);
+    }));
+    hipLaunchKernelGGL(k_group_starts, grid, blk, 0, s, mark, gincl, n, lead_pos);
+
+    // ---- 3. stable sort by (group, rxid); the running entry of every (group, rxid) run
+    DevBuf d_k64a, d_k64b, d_sp, d_win, d_wincl, d_first, d_fincl;
+    M_TRY(d_k64a.alloc(size_t(n) * 8));
+    M_TRY(d_k64b.alloc(size_t(n) * 8));
+    M_TRY(d_sp.alloc(size_t(n) * 4));
+    M_TRY(d_win.alloc(size_t(n) * sizeof(Winner)));
+    M_TRY(d_wincl.alloc(size_t(n) * sizeof(Winner)));
+    unsigned long long* keys = d_k64b.as<unsigned long long>();
+    unsigned* sp = d_sp.as<unsigned>();
+    unsigned *is_first = ja, *first_incl = jb;  // the jump tables are done with
+    hipLaunchKernelGGL(k_keys_group_rx, grid, blk, 0, s, gincl, perm, d_rx, n,
+                       d_k64a.as<unsigned long long>());
+    M_TRY(hipGetLastError());
+    M_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
+        return hipcub::DeviceRadixSort::SortPairs(t, b, d_k64a.as<unsigned long long>(), keys, iota, sp, n, 0,
+                                                  32 + log2n + 1, s);
+    }));
+    hipLaunchKernelGGL(k_winner_in, grid, blk, 0, s, keys, sp, perm, d_en, n, d_win.as<Winner>(),
+                       is_first);
+    M_TRY(hipGetLastError());
+    M_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
+        return hipcub::DeviceScan::InclusiveScan(t, b, d_win.as<Winner>(), d_wincl.as<Winner>(), WinnerOp(), n, s);
+    }));
+    M_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
+        return hipcub::DeviceScan::InclusiveSum(t, b, is_first, first_incl, n, s);
+    }));
+
+    // ---- 4. receivers per group against min_match; output slots in the order of the leaders' input index
+    DevBuf d_quad, d_qincl, d_ebase, d_cbase;
+    M_TRY(d_quad.alloc(size_t(n) * sizeof(Quad)));
+    M_TRY(d_qincl.alloc(size_t(n) * sizeof(Quad)));
+    M_TRY(d_ebase.alloc(size_t(n) * 4));
+    M_TRY(d_cbase.alloc(size_t(n) * 4));
+    M_TRY(out.ptr.alloc((size_t(n) + 1) * 8));
+    M_TRY(out.idx.alloc(size_t(n) * 8));
+    M_TRY(out.miss.alloc(size_t(n) * 8));
+    M_TRY(out.coll.alloc(size_t(n) * 16));
+    M_TRY(hipMemsetAsync(d_quad.p, 0, size_t(n) * sizeof(Quad), s));
+    hipLaunchKernelGGL(k_leader_counts, grid, blk, 0, s, mark, gincl, lead_pos, first_incl, perm, n, min_match,
+                       d_quad.as<Quad>());
+    M_TRY(hipGetLastError());
+    M_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
+        return hipcub::DeviceScan::InclusiveScan(t, b, d_quad.as<Quad>(), d_qincl.as<Quad>(), QuadSum(), n, s);
+    }));
+    hipLaunchKernelGGL(k_emit_leaders, grid, blk, 0, s, mark, gincl, perm, d_quad.as<Quad>(), d_qincl.as<Quad>(), n,
+                       d_ebase.as<unsigned>(), d_cbase.as<unsigned>(), out.ptr.as<long long>(),
+                       out.miss.as<long long>());
+    hipLaunchKernelGGL(k_emit_members, grid, blk, 0, s, keys, sp, perm, first_incl, lead_pos,
+                       d_ebase.as<unsigned>(), d_cbase.as<unsigned>(), d_wincl.as<Winner>(), n,
+                       out.idx.as<long long>(), out.coll.as<long long>());
+    M_TRY(hipGetLastError());
+    Quad total;
+    M_TRY(hipMemcpy(&total, d_qincl.as<Quad>() + (n - 1), sizeof(Quad), hipMemcpyDeviceToHost));
+    out.n_matches = total.match;
+    out.n_entries = total.entries;
+    out.n_misses = total.miss;
+    out.n_collisions = total.coll;
+    return THR_OK;
+}
 
 extern "C" int thr_match(int device_id, size_t n_in, const int32_t* rxid, const int32_t* txid,
                          const double* timestamp, const double* energy, double window, int min_match,
@@ -286,17 +366,15 @@ extern "C" int thr_match(int device_id, size_t n_in, const int32_t* rxid, const 
     if (device_id < 0 || device_id >= ndev) return thr::fail_msg(THR_ERR_ARG, "bad device_id %d", device_id);
     M_TRY(hipSetDevice(device_id));
     const int n = int(n_in);
-    const dim3 blk(kBlock), grid((n + kBlock - 1) / kBlock);
     hipStream_t s = nullptr;
     Event ev[4];
     for (Event& e : ev) M_TRY(hipEventCreate(&e.e));
 
-    DevBuf d_rx, d_tx, d_ts, d_en, d_bad;
+    DevBuf d_rx, d_tx, d_ts, d_en;
     M_TRY(d_rx.alloc(size_t(n) * 4));
     M_TRY(d_tx.alloc(size_t(n) * 4));
     M_TRY(d_ts.alloc(size_t(n) * 8));
     M_TRY(d_en.alloc(size_t(n) * 8));
-    M_TRY(d_bad.alloc(4));
     M_TRY(hipEventRecord(ev[0].e, s));
     M_TRY(hipMemcpy(d_rx.p, rxid, size_t(n) * 4, hipMemcpyHostToDevice));
     M_TRY(hipMemcpy(d_tx.p, txid, size_t(n) * 4, hipMemcpyHostToDevice));
@@ -304,116 +382,23 @@ extern "C" int thr_match(int device_id, size_t n_in, const int32_t* rxid, const 
     M_TRY(hipMemcpy(d_en.p, energy, size_t(n) * 8, hipMemcpyHostToDevice));
     M_TRY(hipEventRecord(ev[1].e, s));
 
-    // ---- 0. the input order
-    M_TRY(hipMemset(d_bad.p, 0xFF, 4));
-    hipLaunchKernelGGL(k_check_sorted, grid, blk, 0, s, d_ts.as<double>(), n, d_bad.as<unsigned>());
-    M_TRY(hipGetLastError());
-    unsigned bad = kNone;
-    M_TRY(hipMemcpy(&bad, d_bad.p, 4, hipMemcpyDeviceToHost));
-    if (bad != kNone)
+    thr::MatchOut out;
+    const int rc = thr::match_core(n, d_rx.as<int>(), d_tx.as<int>(), d_ts.as<double>(), d_en.as<double>(), window,
+                                   min_match, s, out);
+    if (rc != THR_OK) return rc;
+    if (out.first_bad != thr::kMatchSorted) {
+        const unsigned bad = out.first_bad;
         return thr::fail_msg(THR_ERR_ARG,
                              "thr_match: timestamps must be non-decreasing without NaN: detection %u is %s",
                              bad, timestamp[bad] != timestamp[bad] ? "NaN" : "earlier than the one before it");
-
-    // ---- 1. stable sort by txid: perm[p] = input index, increasing inside one txid
-    DevBuf d_k32a, d_k32b, d_iota, d_perm, d_tss, d_tmp;
-    size_t tmp_bytes = 0;
-    M_TRY(d_k32a.alloc(size_t(n) * 4));
-    M_TRY(d_k32b.alloc(size_t(n) * 4));
-    M_TRY(d_iota.alloc(size_t(n) * 4));
-    M_TRY(d_perm.alloc(size_t(n) * 4));
-    M_TRY(d_tss.alloc(size_t(n) * 8));
-    unsigned *key_s = d_k32b.as<unsigned>(), *iota = d_iota.as<unsigned>(), *perm = d_perm.as<unsigned>();
-    hipLaunchKernelGGL(k_iota, grid, blk, 0, s, iota, n);
-    hipLaunchKernelGGL(k_keys_tx, grid, blk, 0, s, d_tx.as<int>(), n, d_k32a.as<unsigned>());
-    M_TRY(hipGetLastError());
-    M_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
-        return hipcub::DeviceRadixSort::SortPairs(t, b, d_k32a.as<unsigned>(), key_s, iota, perm, n, 0, 32, s);
-    }));
-    hipLaunchKernelGGL(k_gather_ts, grid, blk, 0, s, d_ts.as<double>(), perm, n, d_tss.as<double>());
-
-    // ---- 2. next-leader pointers, leaders by pointer doubling, group numbers
-    DevBuf d_ja, d_jb, d_mark, d_gincl, d_lead;
-    M_TRY(d_ja.alloc(size_t(n) * 4));
-    M_TRY(d_jb.alloc(size_t(n) * 4));
-    M_TRY(d_mark.alloc(size_t(n) * 4));
-    M_TRY(d_gincl.alloc(size_t(n) * 4));
-    M_TRY(d_lead.alloc((size_t(n) + 1) * 4));
-    unsigned *ja = d_ja.as<unsigned>(), *jb = d_jb.as<unsigned>(), *mark = d_mark.as<unsigned>();
-    unsigned *gincl = d_gincl.as<unsigned>(), *lead_pos = d_lead.as<unsigned>();
-    hipLaunchKernelGGL(k_next_leader, grid, blk, 0, s, key_s, d_tss.as<double>(), n, window, ja, mark);
-    int log2n = 0;
-    while ((size_t(1) << log2n) < n_in) ++log2n;
-    for (int round = 0; round < log2n + 1; ++round) {
-        hipLaunchKernelGGL(k_double, grid, blk, 0, s, ja, jb, mark, n);
-        std::swap(ja, jb);
     }
-    M_TRY(hipGetLastError());
-    M_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
-        return hipcub::DeviceScan::InclusiveSum(t, b, mark, gincl, n, s);
-    }));
-    hipLaunchKernelGGL(k_group_starts, grid, blk, 0, s, mark, gincl, n, lead_pos);
-
-    // ---- 3. stable sort by (group, rxid); the running entry of every (group, rxid) run
-    DevBuf d_k64a, d_k64b, d_sp, d_win, d_wincl, d_first, d_fincl;
-    M_TRY(d_k64a.alloc(size_t(n) * 8));
-    M_TRY(d_k64b.alloc(size_t(n) * 8));
-    M_TRY(d_sp.alloc(size_t(n) * 4));
-    M_TRY(d_win.alloc(size_t(n) * sizeof(Winner)));
-    M_TRY(d_wincl.alloc(size_t(n) * sizeof(Winner)));
-    unsigned long long* keys = d_k64b.as<unsigned long long>();
-    unsigned* sp = d_sp.as<unsigned>();
-    unsigned *is_first = ja, *first_incl = jb;  // the jump tables are done with
-    hipLaunchKernelGGL(k_keys_group_rx, grid, blk, 0, s, gincl, perm, d_rx.as<int>(), n,
-                       d_k64a.as<unsigned long long>());
-    M_TRY(hipGetLastError());
-    M_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
-        return hipcub::DeviceRadixSort::SortPairs(t, b, d_k64a.as<unsigned long long>(), keys, iota, sp, n, 0,
-                                                  32 + log2n + 1, s);
-    }));
-    hipLaunchKernelGGL(k_winner_in, grid, blk, 0, s, keys, sp, perm, d_en.as<double>(), n, d_win.as<Winner>(),
-                       is_first);
-    M_TRY(hipGetLastError());
-    M_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
-        return hipcub::DeviceScan::InclusiveScan(t, b, d_win.as<Winner>(), d_wincl.as<Winner>(), WinnerOp(), n, s);
-    }));
-    M_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
-        return hipcub::DeviceScan::InclusiveSum(t, b, is_first, first_incl, n, s);
-    }));
-
-    // ---- 4. receivers per group against min_match; output slots in the order of the leaders' input index
-    DevBuf d_quad, d_qincl, d_ebase, d_cbase, d_mptr, d_midx, d_miss, d_coll;
-    M_TRY(d_quad.alloc(size_t(n) * sizeof(Quad)));
-    M_TRY(d_qincl.alloc(size_t(n) * sizeof(Quad)));
-    M_TRY(d_ebase.alloc(size_t(n) * 4));
-    M_TRY(d_cbase.alloc(size_t(n) * 4));
-    M_TRY(d_mptr.alloc(size_t(n) * 8));
-    M_TRY(d_midx.alloc(size_t(n) * 8));
-    M_TRY(d_miss.alloc(size_t(n) * 8));
-    M_TRY(d_coll.alloc(size_t(n) * 16));
-    M_TRY(hipMemsetAsync(d_quad.p, 0, size_t(n) * sizeof(Quad), s));
-    hipLaunchKernelGGL(k_leader_counts, grid, blk, 0, s, mark, gincl, lead_pos, first_incl, perm, n, min_match,
-                       d_quad.as<Quad>());
-    M_TRY(hipGetLastError());
-    M_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
-        return hipcub::DeviceScan::InclusiveScan(t, b, d_quad.as<Quad>(), d_qincl.as<Quad>(), QuadSum(), n, s);
-    }));
-    hipLaunchKernelGGL(k_emit_leaders, grid, blk, 0, s, mark, gincl, perm, d_quad.as<Quad>(), d_qincl.as<Quad>(), n,
-                       d_ebase.as<unsigned>(), d_cbase.as<unsigned>(), d_mptr.as<long long>(),
-                       d_miss.as<long long>());
-    hipLaunchKernelGGL(k_emit_members, grid, blk, 0, s, keys, sp, perm, first_incl, lead_pos,
-                       d_ebase.as<unsigned>(), d_cbase.as<unsigned>(), d_wincl.as<Winner>(), n,
-                       d_midx.as<long long>(), d_coll.as<long long>());
-    M_TRY(hipGetLastError());
     M_TRY(hipEventRecord(ev[2].e, s));
 
-    Quad total;
-    M_TRY(hipMemcpy(&total, d_qincl.as<Quad>() + (n - 1), sizeof(Quad), hipMemcpyDeviceToHost));
-    M_TRY(hipMemcpy(match_ptr_out, d_mptr.p, size_t(total.match) * 8, hipMemcpyDeviceToHost));
-    match_ptr_out[total.match] = int64_t(total.entries);
-    M_TRY(hipMemcpy(match_idx_out, d_midx.p, size_t(total.entries) * 8, hipMemcpyDeviceToHost));
-    M_TRY(hipMemcpy(miss_out, d_miss.p, size_t(total.miss) * 8, hipMemcpyDeviceToHost));
-    M_TRY(hipMemcpy(collision_out, d_coll.p, size_t(total.coll) * 16, hipMemcpyDeviceToHost));
+    M_TRY(hipMemcpy(match_ptr_out, out.ptr.p, out.n_matches * 8, hipMemcpyDeviceToHost));
+    match_ptr_out[out.n_matches] = int64_t(out.n_entries);
+    M_TRY(hipMemcpy(match_idx_out, out.idx.p, out.n_entries * 8, hipMemcpyDeviceToHost));
+    M_TRY(hipMemcpy(miss_out, out.miss.p, out.n_misses * 8, hipMemcpyDeviceToHost));
+    M_TRY(hipMemcpy(collision_out, out.coll.p, out.n_collisions * 16, hipMemcpyDeviceToHost));
     M_TRY(hipEventRecord(ev[3].e, s));
     M_TRY(hipEventSynchronize(ev[3].e));
     for (int k = 0; k < 3; ++k) {
@@ -421,9 +406,9 @@ extern "C" int thr_match(int device_id, size_t n_in, const int32_t* rxid, const 
         M_TRY(hipEventElapsedTime(&ms, ev[k].e, ev[k + 1].e));
         g_times_ms[k] = ms;
     }
-    *n_matches_out = total.match;
-    *n_misses_out = total.miss;
-    *n_collisions_out = total.coll;
+    *n_matches_out = out.n_matches;
+    *n_misses_out = out.n_misses;
+    *n_collisions_out = out.n_collisions;
     return THR_OK;
 } catch (...) {
     return thr::on_exception("thr_match");

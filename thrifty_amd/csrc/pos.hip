@@ -30,18 +30,16 @@
 
 #include "../../include/thrifty_hip.h"
 #include "lmdif8.hpp"
+#include "post_stages.hpp"
 
 // the team's lanes must agree bit for bit and the 1-D result must equal numpy's: no a * b + c may become
 // an fma in this file (the build also passes -ffp-contract=off for it, thrifty_amd/build.py)
 #pragma clang fp contract(off)
 
-namespace thr {
-int fail_msg(int code, const char* fmt, ...);
-int on_exception(const char* who) noexcept;  // handle.hip
-}
-
 namespace {
 
+using thr::DevBuf;
+using thr::Event;
 using thr::group8_sum;
 
 constexpr int kBlock = 256;                // workgroup size
@@ -249,32 +247,67 @@ __global__ __launch_bounds__(kBlock) void k_pos1d(const long long* __restrict__ 
     iters_out[g] = 0;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T>
-    T* as() { return static_cast<T*>(p); }
-};
-struct Event {
-    hipEvent_t e = nullptr;
-    ~Event() {
-        if (e) (void)hipEventDestroy(e);
-    }
-};
-
-#define P_TRY(expr)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return thr::fail_msg(THR_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
+#define P_TRY THR_HIP_TRY
 
 thread_local double g_times_ms[3] = {0, 0, 0};  // last thr_pos of this thread: copies in, kernels, copies out
 
 }  // namespace
+
+// What the host derives from the receiver table, with its checks (thr_pos and thr_postdetect share them).
+int thr::pos_plan(const char* who, int n_rx, int dims, const double* rx_coords, const int32_t* first_two_rx,
+                  const double* x0, PosPlan& plan) {
+    if (!rx_coords) return thr::fail_msg(THR_ERR_ARG, "%s: null argument", who);
+    if (dims != 1 && dims != 2) return thr::fail_msg(THR_ERR_ARG, "%s: 1 or 2 dimensions, not %d", who, dims);
+    if (n_rx < 1 || n_rx > kMaxReceivers)
+        return thr::fail_msg(THR_ERR_ARG, "%s: 1 to %d receivers, not %d", who, kMaxReceivers, n_rx);
+    for (size_t i = 0; i < size_t(n_rx) * size_t(dims); ++i)
+        if (!std::isfinite(rx_coords[i])) return thr::fail_msg(THR_ERR_ARG, "%s: receiver coordinate %zu is not finite", who, i);
+    if (dims == 1) {
+        if (n_rx != 2) return thr::fail_msg(THR_ERR_ARG, "%s: the 1-D solver takes two receivers, not %d", who, n_rx);
+        if (!first_two_rx || first_two_rx[0] < 0 || first_two_rx[0] >= n_rx || first_two_rx[1] < 0 || first_two_rx[1] >= n_rx)
+            return thr::fail_msg(THR_ERR_ARG, "%s: first_two_rx must name two of the %d receivers", who, n_rx);
+        plan.first = first_two_rx[0], plan.second = first_two_rx[1];
+    } else {
+        if (!x0 || !std::isfinite(x0[0]) || !std::isfinite(x0[1])) return thr::fail_msg(THR_ERR_ARG, "%s: x0 must be finite", who);
+        for (int k = 0; k < 2; ++k) {
+            plan.start[k] = x0[k];
+            plan.lo[k] = plan.hi[k] = rx_coords[k];
+            for (int r = 1; r < n_rx; ++r) {
+                plan.lo[k] = std::fmin(plan.lo[k], rx_coords[2 * r + k]);
+                plan.hi[k] = std::fmax(plan.hi[k], rx_coords[2 * r + k]);
+            }
+            plan.lo[k] -= kMaxDist;
+            plan.hi[k] += kMaxDist;
+        }
+    }
+    return THR_OK;
+}
+
+// The stage on device pointers (post_stages.hpp): one launch.  group_ptr and the row receivers are the
+// caller's responsibility (thr_pos checks them on the host, thr_postdetect makes them itself).
+int thr::pos_core(int ng, const long long* d_ptr, const int* d_rx0, const int* d_rx1, const double* d_tdoa,
+                  const double* d_snr, const double* d_xy, int dims, const PosPlan& plan, int max_iter, hipStream_t s,
+                  PosOut& out) {
+    const size_t n_groups = size_t(ng);
+    P_TRY(out.pos.alloc(n_groups * size_t(dims) * 8));
+    P_TRY(out.dop.alloc(n_groups * 8));
+    P_TRY(out.snr.alloc(n_groups * 8));
+    P_TRY(out.status.alloc(n_groups * 4));
+    P_TRY(out.iters.alloc(n_groups * 4));
+    if (dims == 1)
+        hipLaunchKernelGGL(k_pos1d, dim3(unsigned((n_groups + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                           d_ptr, d_rx0, d_rx1, d_tdoa, d_snr,
+                           d_xy, ng, plan.first, plan.second, out.pos.as<double>(), out.dop.as<double>(),
+                           out.snr.as<double>(), out.status.as<int>(), out.iters.as<int>());
+    else
+        hipLaunchKernelGGL(k_pos2d, dim3(unsigned((n_groups + kTeams - 1) / kTeams)), dim3(kBlock), 0, s,
+                           d_ptr, d_rx0, d_rx1, d_tdoa, d_snr,
+                           d_xy, ng, plan.start[0], plan.start[1], plan.lo[0], plan.lo[1], plan.hi[0], plan.hi[1], max_iter,
+                           out.pos.as<double>(), out.dop.as<double>(), out.snr.as<double>(), out.status.as<int>(),
+                           out.iters.as<int>());
+    P_TRY(hipGetLastError());
+    return THR_OK;
+}
 
 extern "C" int thr_pos(int device_id, size_t n_groups, const int64_t* group_ptr, const int32_t* row_rx0,
                        const int32_t* row_rx1, const double* row_tdoa, const double* row_snr, int n_rx, int dims,
@@ -306,28 +339,8 @@ extern "C" int thr_pos(int device_id, size_t n_groups, const int64_t* group_ptr,
     for (size_t i = 0; i < n_rows; ++i)
         if (row_rx0[i] < 0 || row_rx0[i] >= n_rx || row_rx1[i] < 0 || row_rx1[i] >= n_rx)
             return thr::fail_msg(THR_ERR_ARG, "thr_pos: row %zu names receivers %d and %d of %d", i, row_rx0[i], row_rx1[i], n_rx);
-    for (size_t i = 0; i < size_t(n_rx) * size_t(dims); ++i)
-        if (!std::isfinite(rx_coords[i])) return thr::fail_msg(THR_ERR_ARG, "thr_pos: receiver coordinate %zu is not finite", i);
-    double start[2] = {0, 0}, lo[2] = {0, 0}, hi[2] = {0, 0};
-    int first = 0, second = 0;
-    if (dims == 1) {
-        if (n_rx != 2) return thr::fail_msg(THR_ERR_ARG, "thr_pos: the 1-D solver takes two receivers, not %d", n_rx);
-        if (!first_two_rx || first_two_rx[0] < 0 || first_two_rx[0] >= n_rx || first_two_rx[1] < 0 || first_two_rx[1] >= n_rx)
-            return thr::fail_msg(THR_ERR_ARG, "thr_pos: first_two_rx must name two of the %d receivers", n_rx);
-        first = first_two_rx[0], second = first_two_rx[1];
-    } else {
-        if (!x0 || !std::isfinite(x0[0]) || !std::isfinite(x0[1])) return thr::fail_msg(THR_ERR_ARG, "thr_pos: x0 must be finite");
-        for (int k = 0; k < 2; ++k) {
-            start[k] = x0[k];
-            lo[k] = hi[k] = rx_coords[k];
-            for (int r = 1; r < n_rx; ++r) {
-                lo[k] = std::fmin(lo[k], rx_coords[2 * r + k]);
-                hi[k] = std::fmax(hi[k], rx_coords[2 * r + k]);
-            }
-            lo[k] -= kMaxDist;
-            hi[k] += kMaxDist;
-        }
-    }
+    thr::PosPlan plan;
+    if (const int rc = thr::pos_plan("thr_pos", n_rx, dims, rx_coords, first_two_rx, x0, plan)) return rc;
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -340,18 +353,13 @@ extern "C" int thr_pos(int device_id, size_t n_groups, const int64_t* group_ptr,
     Event ev[4];
     for (Event& e : ev) P_TRY(hipEventCreate(&e.e));
 
-    DevBuf d_ptr, d_rx0, d_rx1, d_tdoa, d_snr, d_xy, d_pos, d_dop, d_snr_out, d_status, d_iters;
+    DevBuf d_ptr, d_rx0, d_rx1, d_tdoa, d_snr, d_xy;
     P_TRY(d_ptr.alloc((n_groups + 1) * 8));
     P_TRY(d_rx0.alloc(n_rows * 4));
     P_TRY(d_rx1.alloc(n_rows * 4));
     P_TRY(d_tdoa.alloc(n_rows * 8));
     P_TRY(d_snr.alloc(n_rows * 8));
     P_TRY(d_xy.alloc(size_t(n_rx) * size_t(dims) * 8));
-    P_TRY(d_pos.alloc(n_groups * size_t(dims) * 8));
-    P_TRY(d_dop.alloc(n_groups * 8));
-    P_TRY(d_snr_out.alloc(n_groups * 8));
-    P_TRY(d_status.alloc(n_groups * 4));
-    P_TRY(d_iters.alloc(n_groups * 4));
     P_TRY(hipEventRecord(ev[0].e, s));
     P_TRY(hipMemcpy(d_ptr.p, group_ptr, (n_groups + 1) * 8, hipMemcpyHostToDevice));
     if (n_rows) {
@@ -363,25 +371,17 @@ extern "C" int thr_pos(int device_id, size_t n_groups, const int64_t* group_ptr,
     P_TRY(hipMemcpy(d_xy.p, rx_coords, size_t(n_rx) * size_t(dims) * 8, hipMemcpyHostToDevice));
     P_TRY(hipEventRecord(ev[1].e, s));
 
-    if (dims == 1)
-        hipLaunchKernelGGL(k_pos1d, dim3(unsigned((n_groups + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                           d_ptr.as<long long>(), d_rx0.as<int>(), d_rx1.as<int>(), d_tdoa.as<double>(), d_snr.as<double>(),
-                           d_xy.as<double>(), ng, first, second, d_pos.as<double>(), d_dop.as<double>(),
-                           d_snr_out.as<double>(), d_status.as<int>(), d_iters.as<int>());
-    else
-        hipLaunchKernelGGL(k_pos2d, dim3(unsigned((n_groups + kTeams - 1) / kTeams)), dim3(kBlock), 0, s,
-                           d_ptr.as<long long>(), d_rx0.as<int>(), d_rx1.as<int>(), d_tdoa.as<double>(), d_snr.as<double>(),
-                           d_xy.as<double>(), ng, start[0], start[1], lo[0], lo[1], hi[0], hi[1], max_iter,
-                           d_pos.as<double>(), d_dop.as<double>(), d_snr_out.as<double>(), d_status.as<int>(),
-                           d_iters.as<int>());
-    P_TRY(hipGetLastError());
+    thr::PosOut out;
+    if (const int rc = thr::pos_core(ng, d_ptr.as<long long>(), d_rx0.as<int>(), d_rx1.as<int>(), d_tdoa.as<double>(),
+                                     d_snr.as<double>(), d_xy.as<double>(), dims, plan, max_iter, s, out))
+        return rc;
     P_TRY(hipEventRecord(ev[2].e, s));
 
-    P_TRY(hipMemcpy(pos_out, d_pos.p, n_groups * size_t(dims) * 8, hipMemcpyDeviceToHost));
-    P_TRY(hipMemcpy(dop_out, d_dop.p, n_groups * 8, hipMemcpyDeviceToHost));
-    P_TRY(hipMemcpy(snr_out, d_snr_out.p, n_groups * 8, hipMemcpyDeviceToHost));
-    P_TRY(hipMemcpy(status_out, d_status.p, n_groups * 4, hipMemcpyDeviceToHost));
-    P_TRY(hipMemcpy(iters_out, d_iters.p, n_groups * 4, hipMemcpyDeviceToHost));
+    P_TRY(hipMemcpy(pos_out, out.pos.p, n_groups * size_t(dims) * 8, hipMemcpyDeviceToHost));
+    P_TRY(hipMemcpy(dop_out, out.dop.p, n_groups * 8, hipMemcpyDeviceToHost));
+    P_TRY(hipMemcpy(snr_out, out.snr.p, n_groups * 8, hipMemcpyDeviceToHost));
+    P_TRY(hipMemcpy(status_out, out.status.p, n_groups * 4, hipMemcpyDeviceToHost));
+    P_TRY(hipMemcpy(iters_out, out.iters.p, n_groups * 4, hipMemcpyDeviceToHost));
     P_TRY(hipEventRecord(ev[3].e, s));
     P_TRY(hipEventSynchronize(ev[3].e));
     for (int k = 0; k < 3; ++k) {

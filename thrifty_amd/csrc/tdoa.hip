@@ -19,17 +19,16 @@
 #include <vector>
 
 #include "../../include/thrifty_hip.h"
+#include "post_stages.hpp"
 
 // the outlier mask must equal numpy's bit for bit: no a * b + c may become an fma in this file (the
 // build also passes -ffp-contract=off for it, thrifty_amd/build.py: PER_FILE_FLAGS)
 #pragma clang fp contract(off)
 
-namespace thr {
-int fail_msg(int code, const char* fmt, ...);
-int on_exception(const char* who) noexcept;  // handle.hip
-}
-
 namespace {
+
+using thr::DevBuf;
+using thr::Event;
 
 constexpr int kBlock = 256;               // workgroup size of every kernel here
 constexpr int kWave = 64;                 // one task per wavefront
@@ -443,28 +442,7 @@ __global__ void k_emit_groups(const unsigned* __restrict__ flag, const unsigned*
     group_ptr[flag_excl[m]] = (long long)ok_excl[task_base[m]];
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T>
-    T* as() { return static_cast<T*>(p); }
-};
-struct Event {
-    hipEvent_t e = nullptr;
-    ~Event() {
-        if (e) (void)hipEventDestroy(e);
-    }
-};
-
-#define T_TRY(expr)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return thr::fail_msg(THR_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
+#define T_TRY THR_HIP_TRY
 
 // exclusive sum of n unsigned values (n >= 1), the shared temporary grown on demand
 hipError_t exclusive_sum(DevBuf& tmp, size_t& tmp_bytes, const unsigned* in, unsigned* out, int n, hipStream_t s) {
@@ -472,8 +450,6 @@ hipError_t exclusive_sum(DevBuf& tmp, size_t& tmp_bytes, const unsigned* in, uns
     hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, in, out, n, s);
     if (e != hipSuccess) return e;
     if (need > tmp_bytes) {
-        if (tmp.p) (void)hipFree(tmp.p);
-        tmp.p = nullptr;
         if ((e = tmp.alloc(need)) != hipSuccess) return e;
         tmp_bytes = need;
     }
@@ -485,6 +461,155 @@ inline dim3 grid_for(size_t n) { return dim3(unsigned((n + kBlock - 1) / kBlock)
 thread_local double g_times_ms[3] = {0, 0, 0};  // last thr_tdoa of this thread: copies in, kernels, copies out
 
 }  // namespace
+
+// The stage on device pointers (post_stages.hpp).  thr_tdoa has walked the matches on the host and passes
+// the task and pair totals; thr_postdetect passes -1 and the totals are read off the two scans.  Nothing
+// here validates the CSR: see the callers for why they may hand it over.
+int thr::tdoa_core(int n, const int* d_rx, const double* d_ts, const double* d_soa, const double* d_en,
+                   const double* d_no, int nm, const long long* d_ptr, const long long* d_idx, const int* d_beacon,
+                   int n_rx, int n_beacons, const double* d_dist, double window, double sample_rate, int deg,
+                   long long n_tasks, long long n_pairs, hipStream_t s, TdoaOut& out) {
+    const int n_keys = n_rx * n_rx;
+    const dim3 blk(kBlock);
+
+    // ---- 1. pairs per match, their slots, the expansion
+    DevBuf d_q, d_cnt_b, d_cnt_t, d_base_b, d_base_t, d_tmp;
+    DevBuf d_key, d_pd0, d_pd1, d_pb, d_td0, d_td1;
+    size_t tmp_bytes = 0;
+    T_TRY(d_q.alloc(size_t(n) * 8));
+    T_TRY(d_cnt_b.alloc((size_t(nm) + 1) * 4));
+    T_TRY(d_cnt_t.alloc((size_t(nm) + 1) * 4));
+    T_TRY(d_base_b.alloc((size_t(nm) + 1) * 4));
+    T_TRY(d_base_t.alloc((size_t(nm) + 1) * 4));
+    hipLaunchKernelGGL(k_quality, grid_for(n), blk, 0, s, d_en, d_no, n, d_q.as<double>());
+    hipLaunchKernelGGL(k_pair_counts, grid_for(size_t(nm) + 1), blk, 0, s, d_ptr, d_beacon, nm,
+                       d_cnt_b.as<unsigned>(), d_cnt_t.as<unsigned>());
+    T_TRY(hipGetLastError());
+    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_cnt_b.as<unsigned>(), d_base_b.as<unsigned>(), nm + 1, s));
+    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_cnt_t.as<unsigned>(), d_base_t.as<unsigned>(), nm + 1, s));
+    if (n_tasks < 0 || n_pairs < 0) {  // not claimed by the caller: the scans' totals
+        unsigned totals[2] = {0, 0};
+        T_TRY(hipMemcpy(&totals[0], d_base_t.as<unsigned>() + nm, 4, hipMemcpyDeviceToHost));
+        T_TRY(hipMemcpy(&totals[1], d_base_b.as<unsigned>() + nm, 4, hipMemcpyDeviceToHost));
+        n_tasks = totals[0];
+        n_pairs = totals[1];
+    }
+    const int nt = int(n_tasks), np = int(n_pairs);
+    out.n_tasks = size_t(nt);
+    out.n_pairs = size_t(np);
+    if (nt == 0) return THR_OK;  // no mobile detection pair: nothing more to launch
+    T_TRY(d_key.alloc(size_t(np) * 4));
+    T_TRY(d_pd0.alloc(size_t(np) * 4));
+    T_TRY(d_pd1.alloc(size_t(np) * 4));
+    T_TRY(d_pb.alloc(size_t(np) * 4));
+    T_TRY(d_td0.alloc(size_t(nt) * 4));
+    T_TRY(d_td1.alloc(size_t(nt) * 4));
+    hipLaunchKernelGGL(k_expand, grid_for(nm), blk, 0, s, d_ptr, d_idx,
+                       d_beacon, d_rx, nm, n_rx, d_base_b.as<unsigned>(), d_base_t.as<unsigned>(),
+                       d_key.as<unsigned>(), d_pd0.as<int>(), d_pd1.as<int>(), d_pb.as<int>(), d_td0.as<int>(),
+                       d_td1.as<int>());
+    T_TRY(hipGetLastError());
+
+    // ---- 2. the beacon pairs into their receiver pair's list, match order kept
+    DevBuf d_key_s, d_iota, d_perm, d_bucket, d_bts, d_bs0, d_bs1, d_bq0, d_bq1, d_bb;
+    T_TRY(d_bucket.alloc((size_t(n_keys) + 2) * 4));
+    T_TRY(d_bts.alloc(size_t(np) * 8));
+    T_TRY(d_bs0.alloc(size_t(np) * 8));
+    T_TRY(d_bs1.alloc(size_t(np) * 8));
+    T_TRY(d_bq0.alloc(size_t(np) * 8));
+    T_TRY(d_bq1.alloc(size_t(np) * 8));
+    T_TRY(d_bb.alloc(size_t(np) * 4));
+    if (np > 0) {
+        T_TRY(d_key_s.alloc(size_t(np) * 4));
+        T_TRY(d_iota.alloc(size_t(np) * 4));
+        T_TRY(d_perm.alloc(size_t(np) * 4));
+        hipLaunchKernelGGL(k_iota, grid_for(np), blk, 0, s, d_iota.as<unsigned>(), np);
+        T_TRY(hipGetLastError());
+        int key_bits = 1;
+        while ((1 << key_bits) < n_keys) ++key_bits;
+        size_t need = 0;
+        T_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, d_key.as<unsigned>(), d_key_s.as<unsigned>(),
+                                                 d_iota.as<unsigned>(), d_perm.as<unsigned>(), np, 0, key_bits, s));
+        if (need > tmp_bytes) {
+            T_TRY(d_tmp.alloc(need));
+            tmp_bytes = need;
+        }
+        T_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, need, d_key.as<unsigned>(), d_key_s.as<unsigned>(),
+                                                 d_iota.as<unsigned>(), d_perm.as<unsigned>(), np, 0, key_bits, s));
+        hipLaunchKernelGGL(k_gather_pairs, grid_for(np), blk, 0, s, d_perm.as<unsigned>(), d_pd0.as<int>(),
+                           d_pd1.as<int>(), d_pb.as<int>(), d_ts, d_soa, d_q.as<double>(), np,
+                           d_bts.as<double>(), d_bs0.as<double>(), d_bs1.as<double>(), d_bq0.as<double>(),
+                           d_bq1.as<double>(), d_bb.as<int>());
+        hipLaunchKernelGGL(k_bucket_bounds, grid_for(size_t(n_keys) + 1), blk, 0, s, d_key_s.as<unsigned>(), np, n_keys,
+                           d_bucket.as<unsigned>());
+        T_TRY(hipGetLastError());
+    } else {
+        T_TRY(hipMemsetAsync(d_bucket.p, 0, (size_t(n_keys) + 2) * 4, s));  // no beacon match: every list is empty
+    }
+
+    // ---- 3. one wavefront per task
+    DevBuf d_ok, d_val;
+    T_TRY(d_ok.alloc((size_t(nt) + 1) * 4));
+    T_TRY(d_val.alloc(size_t(nt) * 24));
+    T_TRY(out.n_window.alloc(size_t(nt) * 4));
+    T_TRY(out.n_kept.alloc(size_t(nt) * 4));
+    T_TRY(hipMemsetAsync(d_ok.p, 0, (size_t(nt) + 1) * 4, s));
+    const dim3 est_grid(unsigned((nt + kWaves - 1) / kWaves));
+#define LAUNCH_ESTIMATE(DEG)                                                                                        \
+    hipLaunchKernelGGL(k_estimate<DEG>, est_grid, blk, 0, s, d_td0.as<int>(), d_td1.as<int>(), d_rx,        \
+                       d_ts, d_soa, d_q.as<double>(), d_bucket.as<unsigned>(), n_rx,        \
+                       n_beacons, d_bts.as<double>(), d_bs0.as<double>(), d_bs1.as<double>(), d_bq0.as<double>(),     \
+                       d_bq1.as<double>(), d_bb.as<int>(), d_dist, window, sample_rate, nt,              \
+                       d_ok.as<unsigned>(), d_val.as<double>(), out.n_window.as<int>(), out.n_kept.as<int>())
+    if (deg == 1)
+        LAUNCH_ESTIMATE(1);
+    else if (deg == 2)
+        LAUNCH_ESTIMATE(2);
+    else
+        LAUNCH_ESTIMATE(3);
+#undef LAUNCH_ESTIMATE
+    T_TRY(hipGetLastError());
+
+    // ---- 4. rows, failures and groups in the reference's orders
+    DevBuf d_ok_ex, d_fail, d_fail_ex, d_gflag, d_gflag_ex;
+    T_TRY(d_ok_ex.alloc((size_t(nt) + 1) * 4));
+    T_TRY(d_fail.alloc((size_t(nt) + 1) * 4));
+    T_TRY(d_fail_ex.alloc((size_t(nt) + 1) * 4));
+    T_TRY(d_gflag.alloc((size_t(nm) + 1) * 4));
+    T_TRY(d_gflag_ex.alloc((size_t(nm) + 1) * 4));
+    T_TRY(out.row_rx.alloc(size_t(nt) * 8));
+    T_TRY(out.row_det.alloc(size_t(nt) * 16));
+    T_TRY(out.row_val.alloc(size_t(nt) * 24));
+    T_TRY(out.fail.alloc(size_t(nt) * 16));
+    T_TRY(out.group_id.alloc(size_t(nm) * 8));
+    T_TRY(out.group_ptr.alloc((size_t(nm) + 1) * 8));
+    hipLaunchKernelGGL(k_fail_flags, grid_for(size_t(nt) + 1), blk, 0, s, d_ok.as<unsigned>(), nt, d_fail.as<unsigned>());
+    T_TRY(hipGetLastError());
+    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_ok.as<unsigned>(), d_ok_ex.as<unsigned>(), nt + 1, s));
+    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_fail.as<unsigned>(), d_fail_ex.as<unsigned>(), nt + 1, s));
+    hipLaunchKernelGGL(k_emit_rows, grid_for(nt), blk, 0, s, d_ok.as<unsigned>(), d_ok_ex.as<unsigned>(),
+                       d_fail_ex.as<unsigned>(), d_td0.as<int>(), d_td1.as<int>(), d_rx, d_val.as<double>(), nt,
+                       out.row_rx.as<int>(), out.row_det.as<long long>(), out.row_val.as<double>(),
+                       out.fail.as<long long>());
+    hipLaunchKernelGGL(k_group_flags, grid_for(size_t(nm) + 1), blk, 0, s, d_beacon, d_base_t.as<unsigned>(),
+                       d_ok_ex.as<unsigned>(), nm, d_gflag.as<unsigned>());
+    T_TRY(hipGetLastError());
+    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_gflag.as<unsigned>(), d_gflag_ex.as<unsigned>(), nm + 1, s));
+    hipLaunchKernelGGL(k_emit_groups, grid_for(nm), blk, 0, s, d_gflag.as<unsigned>(), d_gflag_ex.as<unsigned>(),
+                       d_base_t.as<unsigned>(), d_ok_ex.as<unsigned>(), nm, out.group_id.as<long long>(),
+                       out.group_ptr.as<long long>());
+    T_TRY(hipGetLastError());
+    unsigned n_rows = 0, n_fail = 0, n_groups = 0;
+    T_TRY(hipMemcpy(&n_rows, d_ok_ex.as<unsigned>() + nt, 4, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(&n_fail, d_fail_ex.as<unsigned>() + nt, 4, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(&n_groups, d_gflag_ex.as<unsigned>() + nm, 4, hipMemcpyDeviceToHost));
+    if (size_t(n_rows) + size_t(n_fail) != size_t(nt) || n_groups > n_rows)
+        return thr::fail_msg(THR_ERR_DEVICE, "thr_tdoa: %u rows and %u failures for %d tasks", n_rows, n_fail, nt);
+    out.n_rows = n_rows;
+    out.n_fail = n_fail;
+    out.n_groups = n_groups;
+    return THR_OK;
+}
 
 extern "C" int thr_tdoa(int device_id, size_t n_det, const int32_t* rx, const double* timestamp, const double* soa,
                         const double* energy, const double* noise, size_t n_matches, const int64_t* match_ptr,
@@ -546,10 +671,8 @@ extern "C" int thr_tdoa(int device_id, size_t n_det, const int32_t* rx, const do
     group_ptr_out[0] = 0;
     if (n_tasks == 0) return THR_OK;  // no mobile detection pair: nothing to launch (the times stay zero)
     T_TRY(hipSetDevice(device_id));
-    const int n = int(n_det), nm = int(n_matches), nt = int(n_tasks), np = int(total_pairs);
-    const int n_keys = n_rx * n_rx;
+    const int n = int(n_det), nm = int(n_matches), nt = int(n_tasks);
     const size_t n_idx = size_t(match_ptr[n_matches]);
-    const dim3 blk(kBlock);
     hipStream_t s = nullptr;
     Event ev[4];
     for (Event& e : ev) T_TRY(hipEventCreate(&e.e));
@@ -576,141 +699,24 @@ extern "C" int thr_tdoa(int device_id, size_t n_det, const int32_t* rx, const do
     if (n_beacons) T_TRY(hipMemcpy(d_dist.p, dist, size_t(n_rx) * size_t(n_beacons) * 8, hipMemcpyHostToDevice));
     T_TRY(hipEventRecord(ev[1].e, s));
 
-    // ---- 1. pairs per match, their slots, the expansion
-    DevBuf d_q, d_cnt_b, d_cnt_t, d_base_b, d_base_t, d_tmp;
-    DevBuf d_key, d_pd0, d_pd1, d_pb, d_td0, d_td1;
-    size_t tmp_bytes = 0;
-    T_TRY(d_q.alloc(size_t(n) * 8));
-    T_TRY(d_cnt_b.alloc((size_t(nm) + 1) * 4));
-    T_TRY(d_cnt_t.alloc((size_t(nm) + 1) * 4));
-    T_TRY(d_base_b.alloc((size_t(nm) + 1) * 4));
-    T_TRY(d_base_t.alloc((size_t(nm) + 1) * 4));
-    T_TRY(d_key.alloc(size_t(np) * 4));
-    T_TRY(d_pd0.alloc(size_t(np) * 4));
-    T_TRY(d_pd1.alloc(size_t(np) * 4));
-    T_TRY(d_pb.alloc(size_t(np) * 4));
-    T_TRY(d_td0.alloc(size_t(nt) * 4));
-    T_TRY(d_td1.alloc(size_t(nt) * 4));
-    hipLaunchKernelGGL(k_quality, grid_for(n), blk, 0, s, d_en.as<double>(), d_no.as<double>(), n, d_q.as<double>());
-    hipLaunchKernelGGL(k_pair_counts, grid_for(size_t(nm) + 1), blk, 0, s, d_ptr.as<long long>(), d_beacon.as<int>(), nm,
-                       d_cnt_b.as<unsigned>(), d_cnt_t.as<unsigned>());
-    T_TRY(hipGetLastError());
-    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_cnt_b.as<unsigned>(), d_base_b.as<unsigned>(), nm + 1, s));
-    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_cnt_t.as<unsigned>(), d_base_t.as<unsigned>(), nm + 1, s));
-    hipLaunchKernelGGL(k_expand, grid_for(nm), blk, 0, s, d_ptr.as<long long>(), d_idx.as<long long>(),
-                       d_beacon.as<int>(), d_rx.as<int>(), nm, n_rx, d_base_b.as<unsigned>(), d_base_t.as<unsigned>(),
-                       d_key.as<unsigned>(), d_pd0.as<int>(), d_pd1.as<int>(), d_pb.as<int>(), d_td0.as<int>(),
-                       d_td1.as<int>());
-    T_TRY(hipGetLastError());
-
-    // ---- 2. the beacon pairs into their receiver pair's list, match order kept
-    DevBuf d_key_s, d_iota, d_perm, d_bucket, d_bts, d_bs0, d_bs1, d_bq0, d_bq1, d_bb;
-    T_TRY(d_bucket.alloc((size_t(n_keys) + 2) * 4));
-    T_TRY(d_bts.alloc(size_t(np) * 8));
-    T_TRY(d_bs0.alloc(size_t(np) * 8));
-    T_TRY(d_bs1.alloc(size_t(np) * 8));
-    T_TRY(d_bq0.alloc(size_t(np) * 8));
-    T_TRY(d_bq1.alloc(size_t(np) * 8));
-    T_TRY(d_bb.alloc(size_t(np) * 4));
-    if (np > 0) {
-        T_TRY(d_key_s.alloc(size_t(np) * 4));
-        T_TRY(d_iota.alloc(size_t(np) * 4));
-        T_TRY(d_perm.alloc(size_t(np) * 4));
-        hipLaunchKernelGGL(k_iota, grid_for(np), blk, 0, s, d_iota.as<unsigned>(), np);
-        T_TRY(hipGetLastError());
-        int key_bits = 1;
-        while ((1 << key_bits) < n_keys) ++key_bits;
-        size_t need = 0;
-        T_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, d_key.as<unsigned>(), d_key_s.as<unsigned>(),
-                                                 d_iota.as<unsigned>(), d_perm.as<unsigned>(), np, 0, key_bits, s));
-        if (need > tmp_bytes) {
-            if (d_tmp.p) (void)hipFree(d_tmp.p);
-            d_tmp.p = nullptr;
-            T_TRY(d_tmp.alloc(need));
-            tmp_bytes = need;
-        }
-        T_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, need, d_key.as<unsigned>(), d_key_s.as<unsigned>(),
-                                                 d_iota.as<unsigned>(), d_perm.as<unsigned>(), np, 0, key_bits, s));
-        hipLaunchKernelGGL(k_gather_pairs, grid_for(np), blk, 0, s, d_perm.as<unsigned>(), d_pd0.as<int>(),
-                           d_pd1.as<int>(), d_pb.as<int>(), d_ts.as<double>(), d_soa.as<double>(), d_q.as<double>(), np,
-                           d_bts.as<double>(), d_bs0.as<double>(), d_bs1.as<double>(), d_bq0.as<double>(),
-                           d_bq1.as<double>(), d_bb.as<int>());
-        hipLaunchKernelGGL(k_bucket_bounds, grid_for(size_t(n_keys) + 1), blk, 0, s, d_key_s.as<unsigned>(), np, n_keys,
-                           d_bucket.as<unsigned>());
-        T_TRY(hipGetLastError());
-    } else {
-        T_TRY(hipMemsetAsync(d_bucket.p, 0, (size_t(n_keys) + 2) * 4, s));  // no beacon match: every list is empty
-    }
-
-    // ---- 3. one wavefront per task
-    DevBuf d_ok, d_val, d_nwin, d_nkept;
-    T_TRY(d_ok.alloc((size_t(nt) + 1) * 4));
-    T_TRY(d_val.alloc(size_t(nt) * 24));
-    T_TRY(d_nwin.alloc(size_t(nt) * 4));
-    T_TRY(d_nkept.alloc(size_t(nt) * 4));
-    T_TRY(hipMemsetAsync(d_ok.p, 0, (size_t(nt) + 1) * 4, s));
-    const dim3 est_grid(unsigned((nt + kWaves - 1) / kWaves));
-#define LAUNCH_ESTIMATE(DEG)                                                                                        \
-    hipLaunchKernelGGL(k_estimate<DEG>, est_grid, blk, 0, s, d_td0.as<int>(), d_td1.as<int>(), d_rx.as<int>(),        \
-                       d_ts.as<double>(), d_soa.as<double>(), d_q.as<double>(), d_bucket.as<unsigned>(), n_rx,        \
-                       n_beacons, d_bts.as<double>(), d_bs0.as<double>(), d_bs1.as<double>(), d_bq0.as<double>(),     \
-                       d_bq1.as<double>(), d_bb.as<int>(), d_dist.as<double>(), window, sample_rate, nt,              \
-                       d_ok.as<unsigned>(), d_val.as<double>(), d_nwin.as<int>(), d_nkept.as<int>())
-    if (deg == 1)
-        LAUNCH_ESTIMATE(1);
-    else if (deg == 2)
-        LAUNCH_ESTIMATE(2);
-    else
-        LAUNCH_ESTIMATE(3);
-#undef LAUNCH_ESTIMATE
-    T_TRY(hipGetLastError());
-
-    // ---- 4. rows, failures and groups in the reference's orders
-    DevBuf d_ok_ex, d_fail, d_fail_ex, d_gflag, d_gflag_ex, d_row_rx, d_row_det, d_row_val, d_fail_out, d_gid, d_gptr;
-    T_TRY(d_ok_ex.alloc((size_t(nt) + 1) * 4));
-    T_TRY(d_fail.alloc((size_t(nt) + 1) * 4));
-    T_TRY(d_fail_ex.alloc((size_t(nt) + 1) * 4));
-    T_TRY(d_gflag.alloc((size_t(nm) + 1) * 4));
-    T_TRY(d_gflag_ex.alloc((size_t(nm) + 1) * 4));
-    T_TRY(d_row_rx.alloc(size_t(nt) * 8));
-    T_TRY(d_row_det.alloc(size_t(nt) * 16));
-    T_TRY(d_row_val.alloc(size_t(nt) * 24));
-    T_TRY(d_fail_out.alloc(size_t(nt) * 16));
-    T_TRY(d_gid.alloc(size_t(nm) * 8));
-    T_TRY(d_gptr.alloc(size_t(nm) * 8));
-    hipLaunchKernelGGL(k_fail_flags, grid_for(size_t(nt) + 1), blk, 0, s, d_ok.as<unsigned>(), nt, d_fail.as<unsigned>());
-    T_TRY(hipGetLastError());
-    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_ok.as<unsigned>(), d_ok_ex.as<unsigned>(), nt + 1, s));
-    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_fail.as<unsigned>(), d_fail_ex.as<unsigned>(), nt + 1, s));
-    hipLaunchKernelGGL(k_emit_rows, grid_for(nt), blk, 0, s, d_ok.as<unsigned>(), d_ok_ex.as<unsigned>(),
-                       d_fail_ex.as<unsigned>(), d_td0.as<int>(), d_td1.as<int>(), d_rx.as<int>(), d_val.as<double>(), nt,
-                       d_row_rx.as<int>(), d_row_det.as<long long>(), d_row_val.as<double>(),
-                       d_fail_out.as<long long>());
-    hipLaunchKernelGGL(k_group_flags, grid_for(size_t(nm) + 1), blk, 0, s, d_beacon.as<int>(), d_base_t.as<unsigned>(),
-                       d_ok_ex.as<unsigned>(), nm, d_gflag.as<unsigned>());
-    T_TRY(hipGetLastError());
-    T_TRY(exclusive_sum(d_tmp, tmp_bytes, d_gflag.as<unsigned>(), d_gflag_ex.as<unsigned>(), nm + 1, s));
-    hipLaunchKernelGGL(k_emit_groups, grid_for(nm), blk, 0, s, d_gflag.as<unsigned>(), d_gflag_ex.as<unsigned>(),
-                       d_base_t.as<unsigned>(), d_ok_ex.as<unsigned>(), nm, d_gid.as<long long>(),
-                       d_gptr.as<long long>());
-    T_TRY(hipGetLastError());
+    thr::TdoaOut out;
+    const int rc = thr::tdoa_core(n, d_rx.as<int>(), d_ts.as<double>(), d_soa.as<double>(), d_en.as<double>(),
+                                  d_no.as<double>(), nm, d_ptr.as<long long>(), d_idx.as<long long>(), d_beacon.as<int>(),
+                                  n_rx, n_beacons, d_dist.as<double>(), window, sample_rate, deg, (long long)n_tasks,
+                                  (long long)total_pairs, s, out);
+    if (rc != THR_OK) return rc;
+    const size_t n_rows = out.n_rows, n_fail = out.n_fail, n_groups = out.n_groups;
     T_TRY(hipEventRecord(ev[2].e, s));
 
-    unsigned n_rows = 0, n_fail = 0, n_groups = 0;
-    T_TRY(hipMemcpy(&n_rows, d_ok_ex.as<unsigned>() + nt, 4, hipMemcpyDeviceToHost));
-    T_TRY(hipMemcpy(&n_fail, d_fail_ex.as<unsigned>() + nt, 4, hipMemcpyDeviceToHost));
-    T_TRY(hipMemcpy(&n_groups, d_gflag_ex.as<unsigned>() + nm, 4, hipMemcpyDeviceToHost));
-    if (size_t(n_rows) + size_t(n_fail) != n_tasks || n_groups > n_rows)
-        return thr::fail_msg(THR_ERR_DEVICE, "thr_tdoa: %u rows and %u failures for %zu tasks", n_rows, n_fail, n_tasks);
-    T_TRY(hipMemcpy(row_rx_out, d_row_rx.p, size_t(n_rows) * 8, hipMemcpyDeviceToHost));
-    T_TRY(hipMemcpy(row_det_out, d_row_det.p, size_t(n_rows) * 16, hipMemcpyDeviceToHost));
-    T_TRY(hipMemcpy(row_val_out, d_row_val.p, size_t(n_rows) * 24, hipMemcpyDeviceToHost));
-    T_TRY(hipMemcpy(fail_out, d_fail_out.p, size_t(n_fail) * 16, hipMemcpyDeviceToHost));
-    T_TRY(hipMemcpy(group_id_out, d_gid.p, size_t(n_groups) * 8, hipMemcpyDeviceToHost));
-    T_TRY(hipMemcpy(group_ptr_out, d_gptr.p, size_t(n_groups) * 8, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(row_rx_out, out.row_rx.p, n_rows * 8, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(row_det_out, out.row_det.p, n_rows * 16, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(row_val_out, out.row_val.p, n_rows * 24, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(fail_out, out.fail.p, n_fail * 16, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(group_id_out, out.group_id.p, n_groups * 8, hipMemcpyDeviceToHost));
+    T_TRY(hipMemcpy(group_ptr_out, out.group_ptr.p, n_groups * 8, hipMemcpyDeviceToHost));
     group_ptr_out[n_groups] = int64_t(n_rows);
-    if (n_window_out) T_TRY(hipMemcpy(n_window_out, d_nwin.p, size_t(nt) * 4, hipMemcpyDeviceToHost));
-    if (n_kept_out) T_TRY(hipMemcpy(n_kept_out, d_nkept.p, size_t(nt) * 4, hipMemcpyDeviceToHost));
+    if (n_window_out) T_TRY(hipMemcpy(n_window_out, out.n_window.p, size_t(nt) * 4, hipMemcpyDeviceToHost));
+    if (n_kept_out) T_TRY(hipMemcpy(n_kept_out, out.n_kept.p, size_t(nt) * 4, hipMemcpyDeviceToHost));
     T_TRY(hipEventRecord(ev[3].e, s));
     T_TRY(hipEventSynchronize(ev[3].e));
     for (int k = 0; k < 3; ++k) {

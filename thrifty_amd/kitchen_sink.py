@@ -1,0 +1,234 @@
+#!/usr/bin/env python
+"""
+From the receivers' captures to positions in one step.
+
+GPU counterpart of reference thrifty/kitchen_sink.py: `detect_all` runs a detector over every
+receiver's capture, `postdetect` takes the detections of all receivers through identify, match, TDOA
+estimation and position estimation.  With the four default stages `postdetect` is ONE device call
+(`thr_postdetect`, csrc/postdetect.hip): the detection columns go to the device once, the four stages run
+back to back on device-resident intermediates, and the results come back at the end.
+With any stage replaced, the given callables are chained the way the reference chains them.
+
+`postdetect_columns` is the same chain on columns, without result objects -- next to
+`identify.integrate_columns`, `matchmaker.match_columns`, `tdoa_est.tdoa_columns` and
+`pos_est.pos_columns`, whose results it reproduces bit for bit.
+
+`locate` (this module's command line, `python -m thrifty_amd.cli locate`) writes data.toads, data.match,
+data.tdoa and data.pos from one fused call; the four files are byte-identical to running `identify`,
+`match`, `tdoa` and `pos` in turn.
+
+Deviation from the reference: the fused path needs the receivers of every match in `rx_pos` (KeyError
+otherwise, as `tdoa_est.estimate_tdoas` raises it) and at most 64 receivers (`pos_est`'s limit).
+"""
+from __future__ import print_function
+
+import argparse
+import collections
+import logging
+import re
+
+import numpy as np
+
+from thrifty_amd import _native, identify, matchmaker, pos_est, tdoa_est, toads_data
+
+PostdetectSettings = collections.namedtuple(
+    "PostdetectSettings", ["tx_freqs", "match_window", "tdoa_est_window", "rx_pos", "beacon_pos", "sample_rate"])
+PostdetectResult = collections.namedtuple("PostdetectResult", ["toads", "matches", "tdoas", "pos"])
+
+COLUMNS = ("rxid", "block", "timestamp", "carrier_bin", "carrier_offset", "soa", "energy", "noise")
+_UNKNOWN_RX = re.compile(r"detection (-?\d+) is of receiver (-?\d+), which rx_ids lacks")
+
+
+def _default_detector(*args, **kwargs):
+    from thrifty_amd.detect import Detector       # (imported late: detect pulls in the whole engine)
+    return Detector(*args, **kwargs)
+
+
+def patch_module(module, **override):
+    """`module` with some of its keyword arguments fixed: the returned callable passes its own
+    arguments on, with `override` laid over the keywords."""
+    return lambda *args, **kwargs: module(*args, **dict(kwargs, **override))
+
+
+def _detections_of(rxid, name, settings, detector):
+    from thrifty_amd.block_data import card_reader
+    logging.info(" * Detect: RX #%d (%s)", rxid, name)
+    with open(name, "r") as capture:
+        for hit, result in detector(settings, card_reader(capture), rxid=rxid):
+            if hit:
+                yield result
+
+
+def detect_all(cards, settings, detector=_default_detector):
+    """Detections of every receiver's .card capture, receiver after receiver in the order of `cards`
+    ({rxid: file name})."""
+    return [result for rxid, name in cards.items() for result in _detections_of(rxid, name, settings, detector)]
+
+
+def _native_settings(settings, min_match, deg, x0, max_iter, tdoa_as_text):
+    """PostdetectSettings -> (_native.post_settings pair, receiver ids ascending)."""
+    rx_pos = {rx: np.asarray(p, dtype=np.float64) for rx, p in settings.rx_pos.items()}
+    beacon_pos = {tx: np.asarray(p, dtype=np.float64) for tx, p in settings.beacon_pos.items()}
+    ids, table = pos_est._receiver_table(rx_pos)          # insertion order; ValueError for what no solver takes
+    order = np.argsort(np.asarray(ids, dtype=np.int64), kind="stable")
+    rx_ids = np.asarray(ids, dtype=np.int64)[order]
+    where = {int(rx): k for k, rx in enumerate(rx_ids.tolist())}
+    first_two = (where[ids[0]], where[ids[1]]) if len(ids) > 1 else (0, 0)
+    beacons = sorted(beacon_pos)
+    dist = np.array([[tdoa_est._distance(rx_pos[rx], beacon_pos[b]) for b in beacons] for rx in rx_ids.tolist()],
+                    dtype=np.float64).reshape(len(rx_ids), len(beacons))
+    native = _native.post_settings(identify._flatten(settings.tx_freqs), settings.match_window, min_match, rx_ids,
+                                   table[order], first_two, beacons, dist, settings.tdoa_est_window,
+                                   settings.sample_rate, deg, x0, max_iter, tdoa_as_text)
+    return native, rx_ids
+
+
+def postdetect_columns(cols, settings, device_id=0, min_match=2, deg=2, x0=(0.1, 0.1), max_iter=100,
+                       tdoa_as_text=False):
+    """The whole chain on the raw detection columns of all receivers (COLUMNS) in one device call ->
+    dict: `txid` / `keep` per input detection and `kept_order` (identify.integrate_columns); `match_ptr`,
+    `match_idx`, `misses`, `collisions` (matchmaker.match_columns, indices into the kept order);
+    `tdoas`, `group_id`, `group_ptr`, `timestamp`, `tx`, `failures`, `n_window`, `n_kept`
+    (tdoa_est.tdoa_columns); `pos`, `dop`, `snr`, `status`, `iters` over ALL groups (pos_est.pos_columns);
+    `counts`.  KeyError for a receiver of a match that `settings.rx_pos` lacks."""
+    native, rx_ids = _native_settings(settings, min_match, deg, x0, max_iter, tdoa_as_text)
+    try:
+        counts, out = _native.postdetect(*[cols[name] for name in COLUMNS], settings=native, device_id=device_id)
+    except ValueError as err:
+        unknown = _UNKNOWN_RX.search(str(err))
+        if unknown:
+            raise KeyError(int(unknown.group(2)))
+        raise
+    rows = np.zeros(counts["rows"], dtype=tdoa_est.TDOA_DTYPE)
+    if len(rows):
+        rows["rx0"], rows["rx1"] = rx_ids[out["row_rx"][:, 0]], rx_ids[out["row_rx"][:, 1]]
+        rows["det0_idx"], rows["det1_idx"] = out["row_det"][:, 0], out["row_det"][:, 1]
+        rows["tdoa"], rows["snr"], rows["model_quality"] = out["row_val"].T
+    res = {name: out[name] for name in ("txid", "kept_order", "match_ptr", "match_idx", "misses", "collisions",
+                                        "group_id", "group_ptr", "failures", "n_window", "n_kept", "pos", "dop",
+                                        "snr", "status", "iters")}
+    res.update(keep=out["keep"].astype(bool), tdoas=rows, timestamp=out["group_timestamp"], tx=out["group_tx"],
+               counts=counts)
+    return res
+
+
+def _positions(res, dims):
+    """The solved groups as pos_est.solve's structured array; the dropped ones are announced."""
+    dropped = np.isin(res["status"], list(pos_est._DROPPED))
+    for g in np.flatnonzero(dropped).tolist():
+        print("Failed to estimate group #{}: {}".format(int(res["group_id"][g]), pos_est._DROPPED[int(res["status"][g])]))
+    keep = ~dropped
+    results = np.zeros(int(keep.sum()), dtype=pos_est._result_dtype(dims))
+    results["group_id"], results["timestamp"], results["tx"] = res["group_id"][keep], res["timestamp"][keep], res["tx"][keep]
+    results["dop"], results["snr"] = res["dop"][keep], res["snr"][keep]
+    for axis, name in enumerate(("x", "y")[:dims]):
+        results[name] = res["pos"][keep, axis]
+    return results
+
+
+def _columns(detections):
+    n = len(detections)
+    kinds = {"rxid": np.int32, "block": np.int32, "carrier_bin": np.int32}
+    cols = {name: np.empty(n, kinds.get(name, np.float64)) for name in COLUMNS}
+    for i, d in enumerate(detections):
+        cols["rxid"][i] = -1 if d.rxid is None else d.rxid
+        cols["block"][i], cols["timestamp"][i], cols["soa"][i] = d.block, d.timestamp, d.soa
+        cols["carrier_bin"][i], cols["carrier_offset"][i] = d.carrier_info.bin, d.carrier_info.offset
+        cols["energy"][i], cols["noise"][i] = d.corr_info.energy, d.corr_info.noise
+    return cols
+
+
+def _fused(toad, settings, **options):
+    """(PostdetectResult, the column result) of one thr_postdetect call on result objects."""
+    res = postdetect_columns(_columns(toad), settings, **options)
+    for det, tx in zip(toad, res["txid"].tolist()):
+        det.txid = tx
+    ptr, idx = res["match_ptr"].tolist(), res["match_idx"].tolist()
+    dims = res["pos"].shape[1]
+    return PostdetectResult(toads=[toad[i] for i in res["kept_order"].tolist()],
+                            matches=[idx[a:b] for a, b in zip(ptr[:-1], ptr[1:])],
+                            tdoas=tdoa_est._groups(res), pos=_positions(res, dims)), res
+
+
+def postdetect(toad, settings, integrator=identify.integrate, matcher=matchmaker.match_toads,
+               tdoa_estimator=tdoa_est.estimate_tdoas, pos_estimator=pos_est.solve):
+    """Identify, match, estimate TDOAs, estimate positions -> PostdetectResult.  `.txid` of the detections
+    is set in place."""
+    stages = (integrator, matcher, tdoa_estimator, pos_estimator)
+    if stages == (identify.integrate, matchmaker.match_toads, tdoa_est.estimate_tdoas, pos_est.solve):
+        return _fused(list(toad), settings)[0]
+    as_arrays = lambda table: {key: np.array(value) for key, value in table.items()}  # noqa: E731
+    rx_pos = as_arrays(settings.rx_pos)
+    logging.info(" * Integrate")
+    toads = integrator(toad, freqmap=settings.tx_freqs)
+    logging.info(" * Match")
+    matches = matcher(toads, settings.match_window)[0]
+    logging.info(" * TDOA estimate")
+    tdoas = tdoa_estimator(detections=toads, matches=matches, window_size=settings.tdoa_est_window,
+                           beacon_pos=as_arrays(settings.beacon_pos), rx_pos=rx_pos,
+                           sample_rate=settings.sample_rate)[0]
+    logging.info(" * Positions estimate")
+    return PostdetectResult(toads=toads, matches=matches, tdoas=tdoas, pos=pos_estimator(tdoas, rx_pos))
+
+
+_CLI = (
+    (("toad_file",), dict(type=str, nargs="*", default=["*.toad"], help="toad file(s) from receivers [default: *.toad]")),
+    (("-m", "--map"), dict(type=argparse.FileType("r"),
+                           help="schema for mapping DFT index to transmitter ID [default: auto-detect]")),
+    (("-r", "--rx-coordinates"), dict(dest="rx_pos", type=argparse.FileType("r"), default="pos-rx.cfg",
+                                      help="path to config file that contains the coordinates of the receivers")),
+    (("-b", "--beacon-coordinates"), dict(dest="beacon_pos", type=argparse.FileType("r"), default="pos-beacon.cfg",
+                                          help="path to config file that contains the coordinates of the beacon "
+                                               "transmitters")),
+    (("-w", "--window"), dict(dest="window", type=float, default=0.2, help="size of the match window in seconds")),
+    (("-n", "--num-matches"), dict(dest="num_matches", type=int, default=2,
+                                   help="minimum number of receivers that should detect a transmission")),
+    (("--tdoa-window",), dict(dest="tdoa_window", type=float, default=8,
+                              help="maximum difference in timestamp between a beacon transmission and a mobile "
+                                   "unit transmission for the former to be used for the latter's TDOA")),
+    (("-s", "--sample-rate"), dict(dest="sample_rate", type=float, default=2.4e6,
+                                   help="nominal sample rate of receivers")),
+    (("--prefix",), dict(default="data", help="the outputs are PREFIX.toads, .match, .tdoa and .pos [default: data]")),
+)
+
+
+def _parser():
+    parser = argparse.ArgumentParser(prog="locate", description=__doc__,
+                                     formatter_class=argparse.RawDescriptionHelpFormatter)
+    for flags, options in _CLI:
+        parser.add_argument(*flags, **options)
+    return parser
+
+
+def _main(argv=None):
+    """`locate`: .toad files of all receivers -> PREFIX.toads, .match, .tdoa, .pos from one fused call."""
+    args = _parser().parse_args(argv)
+    try:
+        freqmap = identify.load_freqmap(args.map)
+        rx_pos, beacon_pos = tdoa_est.load_pos_config(args.rx_pos), tdoa_est.load_pos_config(args.beacon_pos)
+    finally:
+        for stream in (args.map, args.rx_pos, args.beacon_pos):
+            if stream is not None:
+                stream.close()
+    detections, filenames = identify.load_toad_files(args.toad_file)
+    settings = PostdetectSettings(tx_freqs=freqmap, match_window=args.window, tdoa_est_window=args.tdoa_window,
+                                  rx_pos=rx_pos, beacon_pos=beacon_pos, sample_rate=args.sample_rate)
+    # (tdoa_as_text: `pos` reads its TDOAs from the .tdoa text, nanoseconds; so does the fused call)
+    result, res = _fused(detections, settings, min_match=args.num_matches, tdoa_as_text=True)
+    with open(args.prefix + ".toads", "w") as out:
+        out.write("".join(["# source_files: [%s]\n" % " ".join(filenames)] + [d.serialize() + "\n" for d in result.toads]))
+    with open(args.prefix + ".match", "w") as out:
+        matchmaker.save_matches(result.matches, out)
+    tdoa_est.save_tdoa_groups(args.prefix + ".tdoa", result.tdoas)
+    pos_est.save_positions(args.prefix + ".pos", result.pos)
+    print(identify._REMOVED.format(len(detections) - len(result.toads), len(detections)))
+    print("Number of matches:", len(result.matches))
+    print("Number of misses:", len(res["misses"]))
+    print("Number of collisions:", len(res["collisions"]))
+    print("Number of TDOA estimations:", len(result.tdoas))
+    print("Number of TDOA estimation failures:", len(res["failures"]))
+    print("Number of positions:", len(result.pos))
+
+
+if __name__ == "__main__":
+    _main()
