@@ -151,6 +151,9 @@ def test_extraction_kernels_do_not_touch_the_profiled_hash():
     assert "template_extract.hip" in build.SOURCES and "run_extract.hip" in build.SOURCES
     assert "template_extract.hpp" in build.HEADERS and "run_extract.hip" in build.HOST_ONLY
     assert set(build.UNPROFILED_EXTRACT) == {"template_extract.hip", "template_extract.hpp"}
+    # the host header the file loops share: listed, host only, and named so that csrc_hash() skips it
+    assert "run_loop.hpp" in build.HEADERS and "run_loop.hpp" in build.HOST_ONLY
+    assert set(build.UNPROFILED_RUN) == {"run_loop.hpp"}
 
 
 def test_native_exports_and_abi_of_the_extraction():

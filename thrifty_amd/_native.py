@@ -850,30 +850,30 @@ class Engine(object):
                               rc, out)
         return out
 
+    def _run(self, data, call):
+        """One whole-input call: `call(pointer, n_bytes, stats)` -> rc, over the bytes-like `data` -> _run_done."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        st = ThrRunStats()
+        rc = call(buf.ctypes.data if buf.size else None, buf.size, C.byref(st))
+        del buf
+        return self._run_done(rc, st)
+
     def run_card(self, text, out_fd=None, rxid=None, with_txid=False, carrier_offset_mode=0,
                  batch_blocks=0, rec_out=None):
         """thr_run_card: frame, detect and format the .card text `text` (bytes-like: the mapped
         file) inside the library; the .toad text goes to the descriptor `out_fd`, the detected
         records (timestamp bits in `reserved`) into `rec_out` (a RECORD_DTYPE array) if given.
         -> stats dict (blocks, detections, seconds per stage, `index_error` ...)."""
-        buf = np.frombuffer(text, dtype=np.uint8)
         o = self._run_opts(out_fd, rxid, with_txid, carrier_offset_mode, batch_blocks, rec_out)
-        st = ThrRunStats()
-        rc = self._lib.thr_run_card(self._h, buf.ctypes.data, buf.size, C.byref(o), C.byref(st))
-        del buf
-        return self._run_done(rc, st)
+        return self._run(text, lambda ptr, n, st: self._lib.thr_run_card(self._h, ptr, n, C.byref(o), st))
 
     def run_stream(self, stream, first_block_idx=0, out_fd=None, rxid=None, with_txid=False,
                    carrier_offset_mode=0, batch_blocks=0, rec_out=None, timestamp=None):
         """thr_run_stream: the same for a raw u8 I/Q stream whose first 2 * block_len bytes are
         block `first_block_idx` (overlap framing on the device)."""
-        buf = np.frombuffer(stream, dtype=np.uint8)
         o = self._run_opts(out_fd, rxid, with_txid, carrier_offset_mode, batch_blocks, rec_out, timestamp)
-        st = ThrRunStats()
-        rc = self._lib.thr_run_stream(self._h, buf.ctypes.data, buf.size, int(first_block_idx), C.byref(o),
-                                      C.byref(st))
-        del buf
-        return self._run_done(rc, st)
+        return self._run(stream, lambda ptr, n, st: self._lib.thr_run_stream(self._h, ptr, n, int(first_block_idx),
+                                                                             C.byref(o), st))
 
     def debug_window(self):
         """thr_debug_window -> (released_below, locked_lo, locked_hi, segment_bytes), byte offsets
@@ -1101,17 +1101,12 @@ class Extraction(object):
         the library.  -> the statistics as a dict (`index_error`: the run ended at the reference's
         IndexError block)."""
         eng = self._eng
-        buf = np.frombuffer(data, dtype=np.uint8)
         o = eng._run_opts(out_fd, rxid, False, 0, batch_blocks, rec_out, timestamp)
-        st = ThrRunStats()
-        ptr = buf.ctypes.data if buf.size else None
         if card:
-            rc = self._lib.thr_run_extract_card(eng._h, ptr, buf.size, C.byref(o), self._x, C.byref(st))
-        else:
-            rc = self._lib.thr_run_extract_stream(eng._h, ptr, buf.size, int(first_block_idx), C.byref(o), self._x,
-                                                  C.byref(st))
-        del buf
-        return eng._run_done(rc, st)
+            return eng._run(data, lambda ptr, n, st: self._lib.thr_run_extract_card(eng._h, ptr, n, C.byref(o),
+                                                                                    self._x, st))
+        return eng._run(data, lambda ptr, n, st: self._lib.thr_run_extract_stream(
+            eng._h, ptr, n, int(first_block_idx), C.byref(o), self._x, st))
 
     def result(self, template_len):
         """thr_extract_result -> (record, timestamp, template float64[template_len], n_qualifying).
