@@ -66,7 +66,8 @@ extern "C" {
  *    + thr_tdoa / thr_debug_tdoa_times -- the reference's `thrifty tdoa` (tdoa_est.py:43-105, 234-303)
  *    + thr_pos / thr_debug_pos_times -- the reference's `thrifty pos` (pos_est.py:31-156)
  *    + thr_postdetect / thr_post_fetch / thr_post_free / thr_debug_post_times -- identify, match, tdoa and
- *      pos in one call with device-resident intermediates (the reference's kitchen_sink.postdetect) */
+ *      pos in one call with device-resident intermediates (the reference's kitchen_sink.postdetect)
+ *    + thr_debug_live_resources -- what the process holds of the HIP runtime (the handles own it) */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -796,6 +797,11 @@ int thr_debug_window_times(thr_handle* h, double out[6]);
  *   the main stream, out[7] filling the index array (sample chunks); out[8 + k] = the longest single
  *   occurrence of phase k. */
 int thr_debug_pipe_times(thr_handle* h, double out[16]);
+/* thr_debug_live_resources: what the library holds of the HIP runtime in this process, now: out[0] device
+ *   buffers, out[1] pinned host buffers, out[2] streams, out[3] events -- of every handle, extraction and
+ *   post-detect result together.  Everything a handle took is given back by its thr_destroy (thr_extract_destroy,
+ *   thr_post_free): the four counts are then what they were before it was created.  Needs no device. */
+int thr_debug_live_resources(int64_t out[4]);
 int thr_debug_fft(thr_handle* h, const void* samples, int format, size_t n_blocks,
                   float* spectra_out /* [n_blocks][block_len][2] */);
 int thr_debug_stage(thr_handle* h, const void* samples, int format, size_t n_blocks,

@@ -588,3 +588,24 @@ def test_a_flag_change_rebuild_leaves_no_object_of_the_old_flags_behind(tmp_path
         build.build_native()
     assert seen == {"objects": [], "lib": False, "stamp": False}
     assert build.needs_build()                                    # the next build starts from scratch again
+
+
+# ---------------------------------------------------------------- who owns the device resources
+def test_nothing_allocates_behind_the_owners_back():
+    """The engine's host files take nothing from the HIP runtime and give nothing back on their own: buffers,
+    pinned buffers, streams and events are hip_own.hpp's types, which count them (thr_debug_live_resources)."""
+    from thrifty_amd import build
+    raw = ("hipMalloc(", "hipHostMalloc(", "hipFree(", "hipHostFree(", "hipEventCreate", "hipEventDestroy",
+           "hipStreamCreate", "hipStreamDestroy")
+    for name in ("handle.hip", "pipeline.hip", "entry.hip", "window.hip", "card_gate.hip", "template_extract.hip",
+                 "host_internal.hpp", "card_gate.hpp", "template_extract.hpp"):
+        text = open(os.path.join(build.CSRC, name)).read()
+        assert [call for call in raw if call in text] == [], name
+    post = open(os.path.join(build.CSRC, "post_stages.hpp")).read()
+    assert not re.search(r"struct\s+(DevBuf|Event)\b", post) and '#include "hip_own.hpp"' in post
+    own = open(os.path.join(build.CSRC, "hip_own.hpp")).read()
+    for call in ("hipFree(", "hipHostFree(", "hipStreamDestroy(", "hipEventDestroy("):      # one place each
+        assert own.count(call) == 1, call
+    assert "thr_debug_live_resources" in _native.EXPORTS and callable(_native.live_resources)
+    header = open(os.path.join(ROOT, "include", "thrifty_hip.h")).read()
+    assert "int thr_debug_live_resources(int64_t out[4]);" in header

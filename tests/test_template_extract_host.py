@@ -151,9 +151,18 @@ def test_extraction_kernels_do_not_touch_the_profiled_hash():
     assert "template_extract.hip" in build.SOURCES and "run_extract.hip" in build.SOURCES
     assert "template_extract.hpp" in build.HEADERS and "run_extract.hip" in build.HOST_ONLY
     assert set(build.UNPROFILED_EXTRACT) == {"template_extract.hip", "template_extract.hpp"}
-    # the host header the file loops share: listed, host only, and named so that csrc_hash() skips it
-    assert "run_loop.hpp" in build.HEADERS and "run_loop.hpp" in build.HOST_ONLY
-    assert set(build.UNPROFILED_RUN) == {"run_loop.hpp"}
+
+
+@pytest.mark.parametrize("header", ["run_loop.hpp", "host_internal.hpp"])
+def test_csrc_hash_does_not_see_a_host_only_header(monkeypatch, header):
+    # the host headers: listed (a change rebuilds), host only, and for that reason alone outside csrc_hash()
+    assert header in build.HEADERS and header in build.HOST_ONLY
+    with_header = build.csrc_hash()
+    monkeypatch.setattr(build, "HEADERS", [h for h in build.HEADERS if h != header])
+    assert build.csrc_hash() == with_header
+    monkeypatch.undo()
+    monkeypatch.setattr(build, "HOST_ONLY", tuple(h for h in build.HOST_ONLY if h != header))
+    assert build.csrc_hash() != with_header
 
 
 def test_native_exports_and_abi_of_the_extraction():

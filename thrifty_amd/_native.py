@@ -43,6 +43,7 @@ EXPORTS = [
     "thr_tdoa", "thr_debug_tdoa_times",
     "thr_pos", "thr_debug_pos_times",
     "thr_postdetect", "thr_post_fetch", "thr_post_free", "thr_debug_post_times",
+    "thr_debug_live_resources",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -282,6 +283,7 @@ def load_library():
     lib.thr_post_free.argtypes = [vp]
     lib.thr_post_free.restype = None
     lib.thr_debug_post_times.argtypes = [C.POINTER(C.c_double)]
+    lib.thr_debug_live_resources.argtypes = [C.POINTER(C.c_int64)]
     _lib = lib
     return lib
 
@@ -1309,3 +1311,11 @@ def post_times():
     ms = (C.c_double * 6)()
     _check(lib, lib.thr_debug_post_times(ms))
     return tuple(ms)
+
+
+def live_resources():
+    """thr_debug_live_resources -> (device buffers, pinned host buffers, streams, events) the library holds now."""
+    lib = load_library()
+    out = (C.c_int64 * 4)()
+    _check(lib, lib.thr_debug_live_resources(out))
+    return tuple(int(v) for v in out)

@@ -13,10 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libthriftyhip.so")
 SOURCES = ["handle.hip", "window.hip", "pipeline.hip", "entry.hip", "text.hip", "detect16k.hip", "detect16k_geom0.hip", "detect16k_geom1.hip", "detect16k_geom2.hip", "detect16k_carrier.hip", "detect16k_preshift.hip", "detect16k_sec.hip", "detect_seg.hip", "detect_long.hip", "detect_small.hip", "generic.hip", "card_ingest.hip", "identify.hip", "run_file.hip", "card_gate.hip", "run_gate.hip", "template_extract.hip", "run_extract.hip", "match.hip", "tdoa.hip", "pos.hip", "postdetect.hip"]
-HEADERS = ["host_internal.hpp", "correlate16k.hpp", "correlate16k_geom.hpp", "detect_common.hpp", "fft_regs.hpp", "kernel_util.hpp", "lmdif8.hpp", "passes_w8.hpp", "card_gate.hpp", "template_extract.hpp", "post_stages.hpp", "run_loop.hpp", os.path.join("..", "..", "include", "thrifty_hip.h")]
+HEADERS = ["host_internal.hpp", "correlate16k.hpp", "correlate16k_geom.hpp", "detect_common.hpp", "fft_regs.hpp", "kernel_util.hpp", "lmdif8.hpp", "passes_w8.hpp", "card_gate.hpp", "template_extract.hpp", "post_stages.hpp", "run_loop.hpp", "hip_own.hpp", "input_window.hpp", os.path.join("..", "..", "include", "thrifty_hip.h")]
 HOST_ONLY = ("handle.hip", "window.hip", "pipeline.hip", "entry.hip", "text.hip", "run_file.hip", "run_gate.hip", "run_extract.hip",
-             "host_internal.hpp", "run_loop.hpp")     # no kernels.  csrc_hash() leaves the SOURCES among these out; a header
-# is hashed unless an UNPROFILED_* tuple names it (host_internal.hpp always was: the recorded counters carry that hash)
+             "host_internal.hpp", "run_loop.hpp", "hip_own.hpp", "input_window.hpp")     # no kernels: csrc_hash() leaves these out
 # kernels that none of the workloads of profiles/hbm_traffic.json launches (the carrier gate's verdict and
 # base64 encode): editing them cannot make the recorded counters stale, so csrc_hash() skips them too
 UNPROFILED = ("card_gate.hip", "card_gate.hpp")
@@ -31,8 +30,6 @@ UNPROFILED_TDOA = ("tdoa.hip",)
 UNPROFILED_POS = ("pos.hip",)
 # and for the post-detect chain (thr_postdetect) and the header its four stage cores are declared in
 UNPROFILED_POST = ("postdetect.hip", "post_stages.hpp")
-# and for the file loops' shared host header (see HOST_ONLY: a header stays out of the hash only by being named here)
-UNPROFILED_RUN = ("run_loop.hpp",)
 # per-file code-generation flags (measured on MI355X, see csrc/detect16k_carrier.hip)
 PER_FILE_FLAGS = {"detect16k_carrier.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                   # the work cursor's atomicAdd stays ONE lane's atomic whose result is waited for where it is
@@ -72,15 +69,20 @@ def _hipcc():
     return exe
 
 
+def compile_cmd(src, path, obj, extra=()):
+    """The compile line of one entry of SOURCES (scripts/device_code_digest.py runs the same line)."""
+    return [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
+            "-fno-slp-vectorize"] + PER_FILE_FLAGS.get(src, []) + list(extra) + ["-c", path, "-o", obj]
+
+
 def csrc_hash():
     """sha256 (first 16 hex digits) over the kernel sources and headers (everything but the host
-    side, HOST_ONLY, and the kernels no profiled workload launches, UNPROFILED / UNPROFILED_EXTRACT / UNPROFILED_MATCH / UNPROFILED_TDOA / UNPROFILED_POS / UNPROFILED_POST / UNPROFILED_RUN): profiles/hbm_traffic.json records the hash its counter passes were taken on,
+    side, HOST_ONLY, and the kernels no profiled workload launches, UNPROFILED / UNPROFILED_EXTRACT / UNPROFILED_MATCH / UNPROFILED_TDOA / UNPROFILED_POS / UNPROFILED_POST): profiles/hbm_traffic.json records the hash its counter passes were taken on,
     bench.py flags a mismatch (`traffic_stale`)."""
     import hashlib
     h = hashlib.sha256()
-    skipped = UNPROFILED + UNPROFILED_EXTRACT + UNPROFILED_MATCH + UNPROFILED_TDOA + UNPROFILED_POS + UNPROFILED_POST + UNPROFILED_RUN
-    for name in sorted([x for x in SOURCES if x not in HOST_ONLY + skipped] +
-                       [x for x in HEADERS if not x.startswith("..") and x not in skipped]):
+    skipped = HOST_ONLY + UNPROFILED + UNPROFILED_EXTRACT + UNPROFILED_MATCH + UNPROFILED_TDOA + UNPROFILED_POS + UNPROFILED_POST
+    for name in sorted(x for x in SOURCES + HEADERS if not x.startswith("..") and x not in skipped):
         h.update(name.encode())
         with open(os.path.join(CSRC, name), "rb") as f:
             h.update(f.read())
@@ -136,9 +138,7 @@ def build_native(force=False, verbose=False):
         if (not force and os.path.exists(obj) and
                 os.path.getmtime(obj) > max(newest_common, os.path.getmtime(os.path.join(CSRC, src)))):
             continue
-        cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-               "-fno-slp-vectorize"] + PER_FILE_FLAGS.get(src, []) + extra + [
-                   "-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = compile_cmd(src, os.path.join(CSRC, src), obj, extra)
         if verbose:
             print(" ".join(cmd))
         jobs.append((subprocess.Popen(cmd), cmd, obj))   # the translation units build in parallel

@@ -180,27 +180,19 @@ int gate_chunk(GateRun& g, const void* d_in, size_t stride, const int64_t* block
                size_t nb, size_t done, bool card) {
     thr_gate_handle* h = g.h;
     const int n = h->cfg.block_len;
-    int rc;
-    if ((rc = pipe_grow(&h->d_gate_slots, &h->gate_slots_bytes, nb * g.slot_stride)) != THR_OK) return rc;
-    if (h->h_gate_slots_bytes < nb * g.slot_stride) {
-        if (h->h_gate_slots) (void)hipHostFree(h->h_gate_slots);
-        h->h_gate_slots = nullptr;
-        h->h_gate_slots_bytes = 0;
-        HIP_TRY(hipHostMalloc(&h->h_gate_slots, nb * g.slot_stride, hipHostMallocDefault));
-        h->h_gate_slots_bytes = nb * g.slot_stride;
-    }
+    const size_t slots_bytes = nb * g.slot_stride;
+    HIP_TRY(h->d_gate_slots.grow(slots_bytes, slots_bytes >> 3));
+    HIP_TRY(h->h_gate_slots.grow(slots_bytes));
     const long long* d_idx = nullptr;
     if (block_idx) {
         HIP_TRY(hipMemcpyAsync(h->d_gate_off, block_idx, nb * sizeof(long long), hipMemcpyHostToDevice, h->stream));
         d_idx = h->d_gate_off;
     }
-    rc = run_batch(h, d_in, THR_IN_U8, nullptr, int(nb), nullptr, nullptr, nullptr, nullptr, 0, true, stride);
-    if (rc != THR_OK) return rc;
+    THR_TRY(run_batch(h, d_in, THR_IN_U8, nullptr, int(nb), nullptr, nullptr, nullptr, nullptr, 0, true, stride));
     HIP_TRY(thr::launch_gate_verdict(h->d_stats, int(nb), n, h->gate_c, h->gate_s, d_idx, first_idx, h->d_gate_rec,
                                      h->d_gate_pos, h->d_gate_count, h->stream));
     HIP_TRY(thr::launch_b64_encode(static_cast<const unsigned char*>(d_in), h->dev.blk_stride, n, h->d_gate_pos,
-                                   h->d_gate_count, int(nb), static_cast<unsigned char*>(h->d_gate_slots),
-                                   h->stream));
+                                   h->d_gate_count, int(nb), h->d_gate_slots, h->stream));
     HIP_TRY(hipMemcpyAsync(h->h_gate_count, h->d_gate_count, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(g.out + done, h->d_gate_rec, nb * sizeof(thr_record), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -216,7 +208,7 @@ int gate_chunk(GateRun& g, const void* d_in, size_t stride, const int64_t* block
         // (only what the encoder wrote: the bytes behind a slot's newline are the caller's)
         for (size_t s = 0; s < count; ++s)
             std::memcpy(g.slots + (g.passed + s) * g.slot_stride,
-                        static_cast<const char*>(h->h_gate_slots) + s * g.slot_stride, g.payload_chars + 1);
+                        h->h_gate_slots + s * g.slot_stride, g.payload_chars + 1);
     }
     g.passed += count;
     return THR_OK;
@@ -259,8 +251,13 @@ int gate_decode(thr_gate_handle* h, const long long* rel, size_t nb, size_t blk)
     long long* d_rel = h->d_gate_off + h->cfg.max_batch;
     HIP_TRY(hipMemcpyAsync(d_rel, rel, nb * sizeof(long long), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemsetAsync(h->d_gate_count, 0, 2 * sizeof(int), h->stream));
-    HIP_TRY(thr::launch_b64_decode(static_cast<const unsigned char*>(h->d_gate_text), d_rel, int(nb), int(blk),
-                                   static_cast<unsigned char*>(h->d_in), h->d_gate_count + 1, h->stream));
+    HIP_TRY(thr::launch_b64_decode(h->d_gate_text, d_rel, int(nb), int(blk), h->d_in, h->d_gate_count + 1,
+                                   h->stream));
+    return THR_OK;
+}
+
+int gate_grow(thr::Dev<unsigned char>& buf, size_t need) {      // (an eighth of slack, as the detect pipeline's staging)
+    HIP_TRY(buf.grow(need, need >> 3));
     return THR_OK;
 }
 
@@ -293,7 +290,7 @@ int thr_gate(thr_handle* h, const uint8_t* samples, const int64_t* block_idx, si
     GateRun g{thr_gate_of(h), out, slots, 0, thr::gate_slot_stride(h->cfg.block_len), thr::gate_payload_chars(h->cfg.block_len)};
     for (size_t done = 0; done < n_blocks && rc == THR_OK;) {
         const size_t nb = std::min(n_blocks - done, gate_chunk_blocks(h, blk));
-        if ((rc = pipe_grow(&h->d_in, &h->d_in_bytes, nb * blk)) != THR_OK) break;
+        if ((rc = gate_grow(h->d_in, nb * blk)) != THR_OK) break;
         if ((rc = gate_h2d(h, h->d_in, samples + done * blk, nb * blk, samples + (done + nb) * blk)) != THR_OK) break;
         rc = gate_chunk(g, h->d_in, 0, block_idx ? block_idx + done : nullptr, int64_t(done), nb, done, false);
         done += nb;
@@ -324,7 +321,7 @@ int thr_gate_stream(thr_handle* h, const uint8_t* stream, size_t n_bytes, int64_
     for (size_t done = 0; done < n_blocks && rc == THR_OK;) {
         const size_t nb = std::min(n_blocks - done, gate_chunk_blocks(h, stride));
         const size_t bytes = (nb - 1) * stride + blk;
-        if ((rc = pipe_grow(&h->d_in, &h->d_in_bytes, bytes)) != THR_OK) break;
+        if ((rc = gate_grow(h->d_in, bytes)) != THR_OK) break;
         if ((rc = gate_h2d(h, h->d_in, stream + done * stride, bytes, stream + (done + nb) * stride)) != THR_OK) break;
         rc = gate_chunk(g, h->d_in, stride, nullptr, first_block_idx + int64_t(done), nb, done, false);
         done += nb;
@@ -366,8 +363,8 @@ int thr_gate_card(thr_handle* h, const char* text, size_t text_len, const int64_
         const size_t span = size_t(hi - lo) + chars;
         rel.resize(nb);
         for (size_t i = 0; i < nb; ++i) rel[i] = payload_off[done + i] - lo;
-        if ((rc = pipe_grow(&gh->d_gate_text, &gh->gate_text_bytes, span)) != THR_OK) break;
-        if ((rc = pipe_grow(&h->d_in, &h->d_in_bytes, nb * blk)) != THR_OK) break;
+        if ((rc = gate_grow(gh->d_gate_text, span)) != THR_OK) break;
+        if ((rc = gate_grow(h->d_in, nb * blk)) != THR_OK) break;
         if ((rc = gate_h2d(h, gh->d_gate_text, text + lo, span, text + hi + chars)) != THR_OK) break;
         if ((rc = gate_decode(gh, rel.data(), nb, blk)) != THR_OK) break;
         rc = gate_chunk(g, h->d_in, 0, block_idx ? block_idx + done : nullptr, int64_t(done), nb, done, true);

@@ -5,23 +5,19 @@
 #pragma once
 #include "host_internal.hpp"
 
-// A gate handle (thr_create_ex, THR_VARIANT_GATE) is a thr_handle with the gate's state behind it
-// (host_internal.hpp is part of the profiled source hash, so the state cannot live in thr_handle).
-// The tag is explicit: create_body writes THR_VARIANT_GATE into dev.variant of the handles it allocates
-// as thr_gate_handle and of no other (the carrier kernels never read that field).
+// A gate handle (thr_create_ex, THR_VARIANT_GATE) is a thr_handle with the gate's state behind it.  The tag
+// is dev.variant: create_body writes THR_VARIANT_GATE there for the handles it allocates as thr_gate_handle
+// and for no other (the carrier kernels never read that field).
 struct thr_gate_handle : thr_handle {
     float gate_c = 0, gate_s = 0;             // pass when max > c + s * noise (power domain, float32 like cardet's)
-    int* d_gate_pos = nullptr;                // [max_batch] positions of the passed blocks, input order
-    int* d_gate_count = nullptr;              // [2]: passed blocks of the chunk, invalid base64 payloads
-    int* h_gate_count = nullptr;              // pinned twin
-    thr_record* d_gate_rec = nullptr;         // [max_batch]
-    void* d_gate_slots = nullptr;             // [chunk][slot_stride] base64 of the passed blocks
-    size_t gate_slots_bytes = 0;
-    void* h_gate_slots = nullptr;             // pinned twin: the device-to-host copy is count * slot_stride bytes
-    size_t h_gate_slots_bytes = 0;
-    void* d_gate_text = nullptr;              // .card input: the chunk's text
-    size_t gate_text_bytes = 0;
-    long long* d_gate_off = nullptr;          // [2 * max_batch]: block indices, payload offsets
+    Dev<int> d_gate_pos;                      // [max_batch] positions of the passed blocks, input order
+    Dev<int> d_gate_count;                    // [2]: passed blocks of the chunk, invalid base64 payloads
+    Pinned<int> h_gate_count;                 // pinned twin
+    Dev<thr_record> d_gate_rec;               // [max_batch]
+    Dev<unsigned char> d_gate_slots;          // [chunk][slot_stride] base64 of the passed blocks
+    Pinned<char> h_gate_slots;                // pinned twin: the device-to-host copy is count * slot_stride bytes
+    Dev<unsigned char> d_gate_text;           // .card input: the chunk's text
+    Dev<long long> d_gate_off;                // [2 * max_batch]: block indices, payload offsets
 };
 inline bool thr_is_gate(const thr_handle* h) { return h->dev.variant == THR_VARIANT_GATE; }
 inline thr_gate_handle* thr_gate_of(thr_handle* h) {

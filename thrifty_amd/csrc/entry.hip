@@ -3,6 +3,22 @@
 
 #include "card_gate.hpp"
 
+namespace {
+// h->forced belongs to ONE batch: it is null again however the entry point that set it is left
+struct ForcedReset {
+    thr_handle* h;
+    ~ForcedReset() { h->forced = nullptr; }
+};
+// an entry point left before its batch was waited for: nothing of it stays enqueued behind the caller's arrays
+struct DrainUnlessDone {
+    thr_handle* h;
+    bool done = false;
+    ~DrainUnlessDone() {
+        if (!done) (void)hipStreamSynchronize(h->stream);
+    }
+};
+}  // namespace
+
 extern "C" {
 
 int thr_detect_device(thr_handle* h, const void* d_samples, int format,
@@ -136,10 +152,9 @@ static int submit_enter(thr_handle* h, const char* who, size_t n_blocks, uint64_
     HIP_TRY(hipSetDevice(h->device));
     const int rc = ensure_pipe(h);
     if (rc != THR_OK) return rc;
-    auto& p = h->hp;
     for (int k = 0; k < thr_handle::kPipeDepth; ++k) {
-        const int b = int((p.next_ticket + uint64_t(k)) % thr_handle::kPipeDepth);
-        if (p.pend_n[b] == 0 && p.slot_ticket[b] == 0) {
+        const int b = int((h->hp.next_ticket + uint64_t(k)) % thr_handle::kPipeDepth);
+        if (h->hp.slot[b].pend_n == 0 && h->hp.slot[b].ticket == 0) {
             *slot = b;
             return THR_OK;
         }
@@ -151,16 +166,17 @@ static int submit_enter(thr_handle* h, const char* who, size_t n_blocks, uint64_
 // a failed submit must not leave a half-enqueued chunk behind: wait for the streams, clear the slot
 static int submit_leave(thr_handle* h, int b, int rc, uint64_t* ticket) {
     auto& p = h->hp;
+    auto& s = p.slot[b];
     if (rc != THR_OK) {
-        (void)hipStreamSynchronize(p.copy);
+        (void)hipStreamSynchronize(h->copy_stream);
         (void)hipStreamSynchronize(h->stream);
-        p.pend_n[b] = 0;
-        p.slot_ticket[b] = 0;
+        s.pend_n = 0;
+        s.ticket = 0;
         return rc;
     }
-    p.slot_ticket[b] = p.next_ticket++;
+    s.ticket = p.next_ticket++;
     p.async_open += 1;
-    *ticket = p.slot_ticket[b];
+    *ticket = s.ticket;
     return THR_OK;
 }
 
@@ -217,17 +233,17 @@ int thr_submit_stream(thr_handle* h, const uint8_t* stream, size_t n_bytes, int6
 int thr_collect(thr_handle* h, uint64_t ticket) try {
     if (!h) return fail(THR_ERR_ARG, "thr_collect: null handle");
     if (ticket == 0) return THR_OK;   // the ticket of an empty batch
-    auto& p = h->hp;
     for (int b = 0; b < thr_handle::kPipeDepth; ++b) {
-        if (p.slot_ticket[b] != ticket) continue;
+        auto& s = h->hp.slot[b];
+        if (s.ticket != ticket) continue;
         HIP_TRY(hipSetDevice(h->device));
         int rc = pipe_drain(h, b);
-        if (rc != THR_OK && p.pend_n[b] != 0) {   // the wait itself failed: nothing may stay pending
+        if (rc != THR_OK && s.pend_n != 0) {   // the wait itself failed: nothing may stay pending
             (void)hipStreamSynchronize(h->stream);
-            p.pend_n[b] = 0;
+            s.pend_n = 0;
         }
-        p.slot_ticket[b] = 0;
-        p.async_open -= 1;
+        s.ticket = 0;
+        h->hp.async_open -= 1;
         return rc;
     }
     return fail(THR_ERR_STATE, "thr_collect: ticket %llu is not open (never issued, or collected already)",
@@ -239,11 +255,10 @@ int thr_collect(thr_handle* h, uint64_t ticket) try {
 int thr_inputs_consumed(thr_handle* h, uint64_t ticket) try {
     if (!h) return fail(THR_ERR_ARG, "thr_inputs_consumed: null handle");
     if (ticket == 0) return THR_OK;
-    auto& p = h->hp;
     for (int b = 0; b < thr_handle::kPipeDepth; ++b) {
-        if (p.slot_ticket[b] != ticket) continue;
+        if (h->hp.slot[b].ticket != ticket) continue;
         HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(hipEventSynchronize(p.ev_h2d[b]));   // recorded behind the chunk's last H2D copy
+        HIP_TRY(hipEventSynchronize(h->hp.slot[b].ev_h2d));   // recorded behind the chunk's last H2D copy
         pipe_inputs_done(h, b);
         return THR_OK;
     }
@@ -256,10 +271,9 @@ int thr_poll(thr_handle* h, uint64_t ticket, int* done) try {
     if (!h || !done) return fail(THR_ERR_ARG, "thr_poll: null argument");
     *done = 1;
     if (ticket == 0) return THR_OK;
-    auto& p = h->hp;
-    for (int b = 0; b < thr_handle::kPipeDepth; ++b) {
-        if (p.slot_ticket[b] != ticket) continue;
-        const hipError_t e = hipEventQuery(p.ev_done[b]);
+    for (const auto& s : h->hp.slot) {
+        if (s.ticket != ticket) continue;
+        const hipError_t e = hipEventQuery(s.ev_done);
         if (e == hipErrorNotReady) {
             *done = 0;
             return THR_OK;
@@ -278,14 +292,7 @@ int thr_compact_device(thr_handle* h, const thr_record* d_in, size_t n_records, 
     if (!h || !d_in || !d_out || !n_kept) return fail(THR_ERR_ARG, "thr_compact_device: null argument");
     HIP_TRY(hipSetDevice(h->device));
     if (n_records > size_t(1) << 30) return fail(THR_ERR_ARG, "too many records");
-    const int tiles = thr::compact_tiles(int(n_records));
-    if (tiles > h->compact_tiles_cap) {
-        if (h->d_compact_tiles) (void)hipFree(h->d_compact_tiles);
-        h->d_compact_tiles = nullptr;
-        h->compact_tiles_cap = 0;
-        HIP_TRY(hipMalloc(&h->d_compact_tiles, size_t(tiles) * sizeof(int)));
-        h->compact_tiles_cap = tiles;
-    }
+    HIP_TRY(h->d_compact_tiles.grow(size_t(thr::compact_tiles(int(n_records))) * sizeof(int)));
     HIP_TRY(thr::launch_compact(d_in, int(n_records), d_out, h->d_ncompact, h->d_compact_tiles,
                                 h->stream));
     int n = 0;
@@ -308,27 +315,16 @@ int thr_debug_fft(thr_handle* h, const void* samples, int format, size_t n_block
     if (rc != THR_OK) return rc;
     const size_t n = size_t(h->cfg.block_len);
     const size_t blk_bytes = n * (format == THR_IN_U8 ? 2 : 8);
-    float2* d_dump = nullptr;
-    HIP_TRY(hipMalloc(&d_dump, n_blocks * n * sizeof(float2)));
-    rc = THR_OK;
-    do {
-        if (hipMemcpyAsync(h->d_in, samples, n_blocks * blk_bytes, hipMemcpyHostToDevice, h->stream) !=
-            hipSuccess) {
-            rc = fail(THR_ERR_DEVICE, "H2D copy failed");
-            break;
-        }
-        rc = run_batch(h, h->d_in, format, nullptr, int(n_blocks), h->d_rec, d_dump, nullptr, nullptr,
-                       0, true);
-        if (rc != THR_OK) break;
-        if (hipMemcpyAsync(spectra_out, d_dump, n_blocks * n * sizeof(float2), hipMemcpyDeviceToHost,
-                           h->stream) != hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess) {
-            rc = fail(THR_ERR_DEVICE, "D2H copy failed: %s", hipGetErrorString(hipGetLastError()));
-            break;
-        }
-    } while (0);
-    (void)hipFree(d_dump);
-    return rc;
+    Dev<float2> d_dump;
+    HIP_TRY(d_dump.alloc(n_blocks * n * sizeof(float2)));
+    if (hipMemcpyAsync(h->d_in, samples, n_blocks * blk_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+        return fail(THR_ERR_DEVICE, "H2D copy failed");
+    THR_TRY(run_batch(h, h->d_in, format, nullptr, int(n_blocks), h->d_rec, d_dump, nullptr, nullptr, 0, true));
+    if (hipMemcpyAsync(spectra_out, d_dump, n_blocks * n * sizeof(float2), hipMemcpyDeviceToHost, h->stream) !=
+            hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess)
+        return fail(THR_ERR_DEVICE, "D2H copy failed: %s", hipGetErrorString(hipGetLastError()));
+    return THR_OK;
 } catch (...) {
     return thr::on_exception("thr_debug_fft");
 }
@@ -350,37 +346,28 @@ int thr_detect_offsets(thr_handle* h, const void* samples, int format, const int
     HIP_TRY(hipSetDevice(h->device));
     if (h->hp.async_open != 0)
         return fail(THR_ERR_STATE, "thr_detect_offsets: %d submitted batch(es) not collected yet", h->hp.async_open);
-    int rc = ensure_staging(h, format);
-    if (rc != THR_OK) return rc;
-    if (!h->d_forced) HIP_TRY(hipMalloc(&h->d_forced, size_t(h->cfg.max_batch) * sizeof(double)));
+    THR_TRY(ensure_staging(h, format));
+    if (!h->d_forced) HIP_TRY(h->d_forced.alloc(size_t(h->cfg.max_batch) * sizeof(double)));
     const size_t blk_bytes = size_t(h->cfg.block_len) * (format == THR_IN_U8 ? 2 : 8);
     const size_t nt = size_t(h->cfg.n_templates);
     std::vector<long long> idx(n_blocks);
     for (size_t i = 0; i < n_blocks; ++i) idx[i] = block_idx ? (long long)block_idx[i] : (long long)i;
-    rc = THR_OK;
-    do {
-        if (hipMemcpyAsync(h->d_in, samples, n_blocks * blk_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-            hipMemcpyAsync(h->d_idx, idx.data(), n_blocks * sizeof(long long), hipMemcpyHostToDevice, h->stream) !=
-                hipSuccess ||
-            hipMemcpyAsync(h->d_forced, carrier_offset, n_blocks * sizeof(double), hipMemcpyHostToDevice,
-                           h->stream) != hipSuccess) {
-            rc = fail(THR_ERR_DEVICE, "staging failed: %s", hipGetErrorString(hipGetLastError()));
-            break;
-        }
-        h->forced = h->d_forced;
-        rc = run_batch(h, h->d_in, format, h->d_idx, int(n_blocks), h->d_rec, nullptr, nullptr, nullptr, 0, false);
-        h->forced = nullptr;
-        if (rc != THR_OK) break;
-        if (hipMemcpyAsync(out, h->d_rec, n_blocks * nt * sizeof(thr_record), hipMemcpyDeviceToHost, h->stream) !=
-                hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess) {
-            rc = fail(THR_ERR_DEVICE, "D2H copy failed: %s", hipGetErrorString(hipGetLastError()));
-            break;
-        }
-    } while (0);
-    h->forced = nullptr;
-    if (rc != THR_OK) (void)hipStreamSynchronize(h->stream);
-    return rc;
+    DrainUnlessDone drain{h};       // (`idx` and the caller's arrays outlive the copies of a failed batch)
+    if (hipMemcpyAsync(h->d_in, samples, n_blocks * blk_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipMemcpyAsync(h->d_idx, idx.data(), n_blocks * sizeof(long long), hipMemcpyHostToDevice, h->stream) !=
+            hipSuccess ||
+        hipMemcpyAsync(h->d_forced, carrier_offset, n_blocks * sizeof(double), hipMemcpyHostToDevice, h->stream) !=
+            hipSuccess)
+        return fail(THR_ERR_DEVICE, "staging failed: %s", hipGetErrorString(hipGetLastError()));
+    ForcedReset reset{h};
+    h->forced = h->d_forced;
+    THR_TRY(run_batch(h, h->d_in, format, h->d_idx, int(n_blocks), h->d_rec, nullptr, nullptr, nullptr, 0, false));
+    if (hipMemcpyAsync(out, h->d_rec, n_blocks * nt * sizeof(thr_record), hipMemcpyDeviceToHost, h->stream) !=
+            hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess)
+        return fail(THR_ERR_DEVICE, "D2H copy failed: %s", hipGetErrorString(hipGetLastError()));
+    drain.done = true;
+    return THR_OK;
 } catch (...) {
     return thr::on_exception("thr_detect_offsets");
 }
@@ -406,55 +393,31 @@ int thr_debug_stage_offsets(thr_handle* h, const void* samples, int format, size
     const size_t n = size_t(h->cfg.block_len);
     const size_t blk_bytes = n * (format == THR_IN_U8 ? 2 : 8);
     const size_t dump_bytes = n_blocks * n * sizeof(float2);
-    float2 *d_x = nullptr, *d_c = nullptr;
-    HIP_TRY(hipMalloc(&d_x, dump_bytes));
-    if (hipMalloc(&d_c, dump_bytes) != hipSuccess) {
-        (void)hipFree(d_x);
-        return fail(THR_ERR_DEVICE, "hipMalloc failed");
+    Dev<float2> d_x, d_c;
+    HIP_TRY(d_x.alloc(dump_bytes));
+    if (d_c.alloc(dump_bytes) != hipSuccess) return fail(THR_ERR_DEVICE, "hipMalloc failed");
+    if (hipMemsetAsync(d_x, 0, dump_bytes, h->stream) != hipSuccess ||
+        hipMemsetAsync(d_c, 0, dump_bytes, h->stream) != hipSuccess ||
+        hipMemcpyAsync(h->d_in, samples, n_blocks * blk_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+        return fail(THR_ERR_DEVICE, "staging failed");
+    ForcedReset reset{h};
+    if (carrier_offset) {
+        if (!h->d_forced && h->d_forced.alloc(size_t(h->cfg.max_batch) * sizeof(double)) != hipSuccess)
+            return fail(THR_ERR_DEVICE, "hipMalloc failed");
+        if (hipMemcpyAsync(h->d_forced, carrier_offset, n_blocks * sizeof(double), hipMemcpyHostToDevice,
+                           h->stream) != hipSuccess)
+            return fail(THR_ERR_DEVICE, "staging failed");
+        h->forced = h->d_forced;
     }
-    rc = THR_OK;
-    do {
-        if (hipMemsetAsync(d_x, 0, dump_bytes, h->stream) != hipSuccess ||
-            hipMemsetAsync(d_c, 0, dump_bytes, h->stream) != hipSuccess ||
-            hipMemcpyAsync(h->d_in, samples, n_blocks * blk_bytes, hipMemcpyHostToDevice, h->stream) !=
-                hipSuccess) {
-            rc = fail(THR_ERR_DEVICE, "staging failed");
-            break;
-        }
-        if (carrier_offset) {
-            if (!h->d_forced && hipMalloc(&h->d_forced, size_t(h->cfg.max_batch) * sizeof(double)) != hipSuccess) {
-                rc = fail(THR_ERR_DEVICE, "hipMalloc failed");
-                break;
-            }
-            if (hipMemcpyAsync(h->d_forced, carrier_offset, n_blocks * sizeof(double), hipMemcpyHostToDevice,
-                               h->stream) != hipSuccess) {
-                rc = fail(THR_ERR_DEVICE, "staging failed");
-                break;
-            }
-            h->forced = h->d_forced;
-        }
-        rc = run_batch(h, h->d_in, format, nullptr, int(n_blocks), h->d_rec, nullptr, d_x, d_c,
-                       template_id, false);
-        h->forced = nullptr;
-        if (rc != THR_OK) break;
-        if (shifted_fft_out &&
-            hipMemcpyAsync(shifted_fft_out, d_x, dump_bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
-            rc = fail(THR_ERR_DEVICE, "D2H copy failed");
-            break;
-        }
-        if (corr_out &&
-            hipMemcpyAsync(corr_out, d_c, dump_bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
-            rc = fail(THR_ERR_DEVICE, "D2H copy failed");
-            break;
-        }
-        if (hipStreamSynchronize(h->stream) != hipSuccess) {
-            rc = fail(THR_ERR_DEVICE, "sync failed: %s", hipGetErrorString(hipGetLastError()));
-            break;
-        }
-    } while (0);
-    (void)hipFree(d_x);
-    (void)hipFree(d_c);
-    return rc;
+    THR_TRY(run_batch(h, h->d_in, format, nullptr, int(n_blocks), h->d_rec, nullptr, d_x, d_c, template_id, false));
+    if (shifted_fft_out &&
+        hipMemcpyAsync(shifted_fft_out, d_x, dump_bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+        return fail(THR_ERR_DEVICE, "D2H copy failed");
+    if (corr_out && hipMemcpyAsync(corr_out, d_c, dump_bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+        return fail(THR_ERR_DEVICE, "D2H copy failed");
+    if (hipStreamSynchronize(h->stream) != hipSuccess)
+        return fail(THR_ERR_DEVICE, "sync failed: %s", hipGetErrorString(hipGetLastError()));
+    return THR_OK;
 } catch (...) {
     return thr::on_exception("thr_debug_stage_offsets");
 }

@@ -176,6 +176,53 @@ bool plan_sections_4k(thr::DevCfg& d, int template_len) {
     return g > 0;
 }
 
+namespace {
+
+// a host array into a device array of its own
+template <class T, class U>
+int upload(Dev<T>& owner, const std::vector<U>& v) {
+    HIP_TRY(owner.alloc(v.size() * sizeof(U)));
+    HIP_TRY(hipMemcpy(owner, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice));
+    return THR_OK;
+}
+
+using Spectrum = std::vector<std::complex<double>>;
+
+Spectrum template_fft(const thr_handle* h, int t, int len) {     // FFT(template t zero-padded to len)
+    const int w = h->cfg.template_len;
+    Spectrum buf(len, 0.0);
+    for (int i = 0; i < w; ++i) buf[i] = h->cfg.templates[size_t(t) * w + i];
+    host_fft(buf);
+    return buf;
+}
+
+float2 conj_over(const std::complex<double>& v, int n) {
+    const std::complex<double> c = std::conj(v) / double(n);
+    return float2{float(c.real()), float(c.imag())};
+}
+
+// conj(spec[first + step * k]) / n for the 16384 bins k, in the digit-reversed, lane-coalesced order
+// k_correlate consumes: thread tid holds k = (tid >> 5) + 16 (tid & 31) + 512 k3
+void permute_16k(float2* out, const Spectrum& spec, int first, int step, int n) {
+    for (int tid = 0; tid < 512; ++tid)
+        for (int k3 = 0; k3 < 32; ++k3) {
+            const int k = (tid >> 5) + 16 * (tid & 31) + 512 * k3;
+            out[((k3 >> 1) * 512 + tid) * 2 + (k3 & 1)] = conj_over(spec[first + step * k], n);
+        }
+}
+
+// the short-block layout: thread column c = k1 * 32 + k2 (k1 < r1) holds bins k1 + r1 k2 + tb k3, tb = 32 r1;
+// float4 j of the column = k3 in {2j, 2j + 1}, stored [j][c] for coalescing
+void permute_short(float2* out, const Spectrum& spec, int r1, int tb, int n) {
+    for (int c = 0; c < tb; ++c)
+        for (int k3 = 0; k3 < 32; ++k3) {
+            const int k = (c >> 5) + r1 * (c & 31) + tb * k3;
+            out[((k3 >> 1) * tb + c) * 2 + (k3 & 1)] = conj_over(spec[k], n);
+        }
+}
+
+}  // namespace
+
 int build_constants(thr_handle* h) {
     const int n = h->cfg.block_len;
     // --- LDS twiddle tables (forward sign): C[32][32], A[16][32], Bt[16][32]  (fast path)
@@ -187,8 +234,7 @@ int build_constants(thr_handle* h) {
     for (int k1 = 0; k1 < 16; ++k1)
         for (int mp = 0; mp < 32; ++mp)
             tab[1536 + k1 * 32 + mp] = unit_root((long long)k1 * mp, h->lng ? 16384 : n);
-    HIP_TRY(hipMalloc(&h->d_tables, tab.size() * sizeof(float2)));
-    HIP_TRY(hipMemcpy(h->d_tables, tab.data(), tab.size() * sizeof(float2), hipMemcpyHostToDevice));
+    THR_TRY(upload(h->d_tables, tab));
     // --- pass-1 / pass-B twiddles W_16384^(k1 q) of k_correlate and of the
     //     short-block kernels as one L2-resident table in global memory
     h->dev.gtw = nullptr;
@@ -205,105 +251,52 @@ int build_constants(thr_handle* h) {
                     for (int e = 0; e < 2; ++e)
                         g[16 * 1024 + ((k1 * 16 + j) * 32 + n3) * 2 + e] =
                             unit_root((long long)k1 * (32 * (2 * j + e) + n3), 16384);
-        HIP_TRY(hipMalloc(&h->d_gtw, g.size() * sizeof(float2)));
-        HIP_TRY(hipMemcpy(h->d_gtw, g.data(), g.size() * sizeof(float2), hipMemcpyHostToDevice));
+        THR_TRY(upload(h->d_gtw, g));
         h->dev.gtw = h->d_gtw;
     }
     // --- full-length root table for the shift phasor
     std::vector<float2> tw(n);
     for (int j = 0; j < n; ++j) tw[j] = unit_root(j, n);
-    HIP_TRY(hipMalloc(&h->d_twn, tw.size() * sizeof(float2)));
-    HIP_TRY(hipMemcpy(h->d_twn, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
-    // --- template spectra: conj(FFT(zero-padded template)) / N, in the
-    //     digit-reversed, lane-coalesced order k_correlate consumes
+    THR_TRY(upload(h->d_twn, tw));
+    // --- template spectra: conj(FFT(zero-padded template)) / N, in the order the path's correlate
+    //     kernel consumes
     const int w = h->cfg.template_len, nt = h->cfg.n_templates;
     std::vector<float2> spec(size_t(nt) * n);
     for (int t = 0; t < nt; ++t) {
-        std::vector<std::complex<double>> buf(n, 0.0);
         double energy = 0;
         for (int i = 0; i < w; ++i) {
             const double v = h->cfg.templates[size_t(t) * w + i];
-            buf[i] = v;
             energy += v * v;
         }
         h->dev.tmpl_energy[t] = float(energy);
-        host_fft(buf);
+        const Spectrum buf = template_fft(h, t, n);
         float2* out = spec.data() + size_t(t) * n;
         if (h->lng) {
             // sub-transform k0 holds bins k0 + R0*q; within it the 16384 kernels' permutation
             const int r0 = n / 16384;
-            for (int k0 = 0; k0 < r0; ++k0)
-                for (int tid = 0; tid < 512; ++tid)
-                    for (int k3 = 0; k3 < 32; ++k3) {
-                        const int q = (tid >> 5) + 16 * (tid & 31) + 512 * k3;
-                        const std::complex<double> c = std::conj(buf[k0 + r0 * q]) / double(n);
-                        out[size_t(k0) * 16384 + ((k3 >> 1) * 512 + tid) * 2 + (k3 & 1)] =
-                            float2{float(c.real()), float(c.imag())};
-                    }
+            for (int k0 = 0; k0 < r0; ++k0) permute_16k(out + size_t(k0) * 16384, buf, k0, r0, n);
         } else if (h->small) {
-            // thread column c = k1 * 32 + k2 (k1 < R1) holds bins k1 + R1 k2 + 32 R1 k3;
-            // float4 j of the column = k3 in {2j, 2j + 1}, stored [j][c] for coalescing
-            const int r1 = n / 1024, tb = 32 * r1;
-            for (int c = 0; c < tb; ++c)
-                for (int k3 = 0; k3 < 32; ++k3) {
-                    const int k = (c >> 5) + r1 * (c & 31) + tb * k3;
-                    const std::complex<double> cc = std::conj(buf[k]) / double(n);
-                    out[((k3 >> 1) * tb + c) * 2 + (k3 & 1)] = float2{float(cc.real()), float(cc.imag())};
-                }
+            permute_short(out, buf, n / 1024, 32 * (n / 1024), n);
         } else if (h->fast) {
-            for (int tid = 0; tid < 512; ++tid)
-                for (int k3 = 0; k3 < 32; ++k3) {
-                    const int k = (tid >> 5) + 16 * (tid & 31) + 512 * k3;
-                    const std::complex<double> c = std::conj(buf[k]) / double(n);
-                    out[((k3 >> 1) * 512 + tid) * 2 + (k3 & 1)] =
-                        float2{float(c.real()), float(c.imag())};
-                }
+            permute_16k(out, buf, 0, 1, n);
         } else {
-            for (int k = 0; k < n; ++k) {
-                const std::complex<double> c = std::conj(buf[k]) / double(n);
-                out[k] = float2{float(c.real()), float(c.imag())};
-            }
+            for (int k = 0; k < n; ++k) out[k] = conj_over(buf[k], n);
         }
     }
     if (h->seg) {
-        // sectioned correlate stage: conj(FFT(template zero-padded to 16384)) / 16384 in the
-        // digit-reversed, lane-coalesced order k_correlate consumes (same as block_len 16384)
+        // sectioned correlate stage: the template zero-padded to 16384, as for block_len 16384
         const int m = 16384;
         std::vector<float2> s16(size_t(nt) * m);
-        for (int t = 0; t < nt; ++t) {
-            std::vector<std::complex<double>> buf(m, 0.0);
-            for (int i = 0; i < w; ++i) buf[i] = h->cfg.templates[size_t(t) * w + i];
-            host_fft(buf);
-            float2* out = s16.data() + size_t(t) * m;
-            for (int tid = 0; tid < 512; ++tid)
-                for (int k3 = 0; k3 < 32; ++k3) {
-                    const int k = (tid >> 5) + 16 * (tid & 31) + 512 * k3;
-                    const std::complex<double> c = std::conj(buf[k]) / double(m);
-                    out[((k3 >> 1) * 512 + tid) * 2 + (k3 & 1)] = float2{float(c.real()), float(c.imag())};
-                }
-        }
-        HIP_TRY(hipMalloc(&h->d_tspec16k, s16.size() * sizeof(float2)));
-        HIP_TRY(hipMemcpy(h->d_tspec16k, s16.data(), s16.size() * sizeof(float2), hipMemcpyHostToDevice));
+        for (int t = 0; t < nt; ++t) permute_16k(s16.data() + size_t(t) * m, template_fft(h, t, m), 0, 1, m);
+        THR_TRY(upload(h->d_tspec16k, s16));
     }
     if (h->sec4k) {
-        // 4096-sample sections of a 16384-sample block: conj(FFT(template zero-padded to 4096)) / 4096,
-        // thread column c = row * 32 + k2 holds bins row + 4 k2 + 128 k3 (the short-block layout, R1 = 4)
-        const int m = 4096, r1 = 4, tb = 128;
+        // 4096-sample sections of a 16384-sample block: the template zero-padded to 4096, thread column
+        // c = row * 32 + k2 holds bins row + 4 k2 + 128 k3 (the short-block layout, R1 = 4)
+        const int m = 4096;
         std::vector<float2> s4(size_t(nt) * m);
-        for (int t = 0; t < nt; ++t) {
-            std::vector<std::complex<double>> buf(m, 0.0);
-            for (int i = 0; i < w; ++i) buf[i] = h->cfg.templates[size_t(t) * w + i];
-            host_fft(buf);
-            float2* out = s4.data() + size_t(t) * m;
-            for (int c = 0; c < tb; ++c)
-                for (int k3 = 0; k3 < 32; ++k3) {
-                    const int k = (c >> 5) + r1 * (c & 31) + tb * k3;
-                    const std::complex<double> cc = std::conj(buf[k]) / double(m);
-                    out[((k3 >> 1) * tb + c) * 2 + (k3 & 1)] = float2{float(cc.real()), float(cc.imag())};
-                }
-        }
-        HIP_TRY(hipMalloc(&h->d_tspec4k, s4.size() * sizeof(float2)));
-        HIP_TRY(hipMemcpy(h->d_tspec4k, s4.data(), s4.size() * sizeof(float2), hipMemcpyHostToDevice));
+        for (int t = 0; t < nt; ++t) permute_short(s4.data() + size_t(t) * m, template_fft(h, t, m), 4, 128, m);
+        THR_TRY(upload(h->d_tspec4k, s4));
         if (nt > 1) {
             // the C table in pairs, for the kernel form that re-reads its twiddle column every pass
             std::vector<float2> cp(1024);
@@ -312,21 +305,13 @@ int build_constants(thr_handle* h) {
                     cp[(j * 32 + c) * 2] = tab[(2 * j) * 32 + c];
                     cp[(j * 32 + c) * 2 + 1] = tab[(2 * j + 1) * 32 + c];
                 }
-            HIP_TRY(hipMalloc(&h->d_ctab_pair, cp.size() * sizeof(float2)));
-            HIP_TRY(hipMemcpy(h->d_ctab_pair, cp.data(), cp.size() * sizeof(float2), hipMemcpyHostToDevice));
+            THR_TRY(upload(h->d_ctab_pair, cp));
             const size_t pb = thr::park_bytes_4k(4 * h->n_cu);
-            if (pb) HIP_TRY(hipMalloc(&h->d_park, pb));
+            if (pb) HIP_TRY(h->d_park.alloc(pb));
         }
     }
     if (nt == 0) return THR_OK;     // carrier gate: no template spectra
-    float2* d_spec = nullptr;
-    HIP_TRY(hipMalloc(&d_spec, spec.size() * sizeof(float2)));
-    HIP_TRY(hipMemcpy(d_spec, spec.data(), spec.size() * sizeof(float2), hipMemcpyHostToDevice));
-    if (h->fast || h->lng || h->small)
-        h->d_tspec = reinterpret_cast<float4*>(d_spec);
-    else
-        h->d_tspec_nat = d_spec;
-    return THR_OK;
+    return (h->fast || h->lng || h->small) ? upload(h->d_tspec, spec) : upload(h->d_tspec_nat, spec);
 }
 
 // Pre-shifted template spectra of the PreshiftDetector variant (detect_preshift.py:24-40):
@@ -346,15 +331,12 @@ int build_preshift_bank(thr_handle* h) {
         host_fft(buf);
         float2* out = bank.data() + size_t(j) * n;
         for (int k = 0; k < n; ++k) {
-            const std::complex<double> c = std::conj(buf[k]) / double(n);
             // 16384 kernel: bin k = k1 + 16 k2 + 512 k3 lives at (k3 * 16 + k1) * 32 + k2
             const int pos = h->fast ? (((k >> 9) * 16 + (k & 15)) * 32 + ((k >> 4) & 31)) : k;
-            out[pos] = float2{float(c.real()), float(c.imag())};
+            out[pos] = conj_over(buf[k], n);
         }
     }
-    HIP_TRY(hipMalloc(&h->d_bank, bank.size() * sizeof(float2)));
-    HIP_TRY(hipMemcpy(h->d_bank, bank.data(), bank.size() * sizeof(float2), hipMemcpyHostToDevice));
-    return THR_OK;
+    return upload(h->d_bank, bank);
 }
 
 
@@ -574,24 +556,21 @@ int thr_create_ex(const thr_settings* s, int variant, int variant_arg, int path,
 }
 
 
-static int create_body(thr_handle*& h, const thr_settings* s, int preshift_num, thr_handle** out, int variant,
-                       int path, int interp);
+static int create_body(const thr_settings* s, int preshift_num, thr_handle** out, int variant, int path, int interp);
 
 static int create_impl(const thr_settings* s, int preshift_num, thr_handle** out, int variant, int path,
-                       int interp) {
+                       int interp) try {
     if (!s || !out) return fail(THR_ERR_ARG, "thr_create: null argument");
     *out = nullptr;
-    thr_handle* h = nullptr;       // what create_body had built when it threw (host memory) goes back
-    try {
-        return create_body(h, s, preshift_num, out, variant, path, interp);
-    } catch (...) {
-        if (h) thr_destroy(h);
-        return thr::on_exception("thr_create");
-    }
+    return create_body(s, preshift_num, out, variant, path, interp);
+} catch (...) {
+    return thr::on_exception("thr_create");
 }
 
-static int create_body(thr_handle*& h, const thr_settings* s, int preshift_num, thr_handle** out, int variant,
-                       int path, int interp) {
+// Every return before the last one, and an exception (host memory), gives back what the handle had taken:
+// `h` owns it until it is released into *out.
+static int create_body(const thr_settings* s, int preshift_num, thr_handle** out, int variant, int path,
+                       int interp) {
     const int n = s->block_len;
     if (n <= 0 || (n & (n - 1))) return fail(THR_ERR_ARG, "block_len %d is not a power of two", n);
     if (n < 64 || n > (1 << 20))
@@ -617,8 +596,7 @@ static int create_body(thr_handle*& h, const thr_settings* s, int preshift_num, 
         return fail(THR_ERR_ARG, "device_id %d out of range (%d devices)", s->device_id, ndev);
 
     thr_gate_handle* gh = gate ? new thr_gate_handle() : nullptr;
-    h = gate ? gh : new thr_handle();
-    if (gate) h->dev.variant = THR_VARIANT_GATE;      // (from the first moment: thr_destroy deletes by this tag)
+    std::unique_ptr<thr_handle, HandleDeleter> h(gate ? gh : new thr_handle());
     h->cfg = *s;
     h->cfg.templates = nullptr;  // not retained beyond this call (re-pointed below)
     if (gate) {
@@ -633,238 +611,178 @@ static int create_body(thr_handle*& h, const thr_settings* s, int preshift_num, 
     h->fast = (n == 16384) && !multipass;
     // the preshift variant has a fused kernel for 16384 only; other lengths use the multi-pass pipeline
     h->lng = thr::long_supported(n) && !multipass && !preshift_num;
-    int rc = THR_OK;
-    do {
-        if (hipSetDevice(h->device) != hipSuccess) {
-            rc = fail(THR_ERR_DEVICE, "hipSetDevice(%d) failed", h->device);
-            break;
-        }
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) {
-            rc = fail(THR_ERR_DEVICE, "hipGetDeviceProperties failed");
-            break;
-        }
-        h->n_cu = prop.multiProcessorCount;
-        if ((h->fast || h->lng || thr::small_supported(n)) && size_t(prop.maxSharedMemoryPerMultiProcessor) <
-                           thr::lds_bytes_16k()) {
-            rc = fail(THR_ERR_DEVICE, "device has %zu B LDS per CU, need %zu",
-                      size_t(prop.maxSharedMemoryPerMultiProcessor), thr::lds_bytes_16k());
-            break;
-        }
-        thr::DevCfg& d = h->dev;
-        d.block_len = n;
-        d.history_len = s->history_len;
-        d.n_templates = s->n_templates;
-        d.carrier_len = s->carrier_len > 0 ? s->carrier_len : s->template_len;
-        if (gate) {       // cardet_normalize_window (checked by create_gate): [min, max], swapped if reversed
-            int lo = s->carrier_window[0], hi = s->carrier_window[1];
-            if (lo < 0) lo += n;
-            if (hi < 0) hi += n;
-            d.n_templates = 0;
-            d.carrier_len = 1;
-            d.win_lo = std::min(lo, hi);
-            d.win_count = std::abs(hi - lo) + 1;
-        } else if ((rc = window_indices(s->carrier_window[0], s->carrier_window[1], n, &d.win_lo,
-                                        &d.win_count)) != THR_OK)
-            break;
-        // soa_estimator.py:20-39
-        const int corr_len = n - s->template_len + 1;
-        const int pad = s->history_len - s->template_len + 1;
-        d.corr_lo = pad / 2;
-        d.corr_hi = corr_len - (pad - pad / 2);
-        d.corr_len = corr_len;
-        if (!gate && d.corr_hi <= d.corr_lo) {
-            rc = fail(THR_ERR_ARG, "empty correlation window [%d, %d)", d.corr_lo, d.corr_hi);
-            break;
-        }
-        for (int i = 0; i < 3; ++i) {
-            d.car_thr[i] = s->carrier_thresh[i];
-            d.cor_thr[i] = s->corr_thresh[i];
-        }
-#ifdef THR_DEV
-        d.timeline = nullptr;
-        if (hipMalloc(&d.timeline, 128 * sizeof(unsigned long long)) == hipSuccess)
-            hipMemset(d.timeline, 0, 128 * sizeof(unsigned long long));
-#endif
-        d.variant = variant >= 0 ? variant : (preshift_num ? 1 : 0);     // (THR_VARIANT_GATE: the tag of a thr_gate_handle)
-        d.interp = d.variant == 1 ? interp : 0;
-        d.car_want_std = !gate && s->carrier_thresh[2] != 0.0;     // (the gate has no stddev term)
-        d.car_prune = 0;
-        bool prune_ok = !d.car_want_std;
-#ifdef THR_DEV
-        if (getenv("THR_NO_PRUNE")) prune_ok = false;   // dev A/B: the full-spectrum carrier kernel
-#endif
-        if (prune_ok) {
-            // long blocks: R0 sub-transforms, each pruned to its 128 lowest bins (mode 1 only)
-            const int span = 128 * (h->lng ? n / 16384 : 1);
-            if (d.win_lo >= 3 && d.win_lo + d.win_count + 3 <= span)
-                d.car_prune = 1;  // window and fit margin already inside bins [0, span)
-            else if (d.win_count + 6 <= 128 && !h->lng)
-                d.car_prune = 2;  // any narrow window: pre-shift by win_lo - 3
-        }
-        d.cor_want_std = s->corr_thresh[2] != 0.0;
-        d.no_row_geom = path == THR_PATH_GENERIC_ROWS || path == THR_PATH_UNSECTIONED_GENERIC_ROWS;
-        h->small = thr::small_supported(n) && !multipass && !preshift_num;
-        // long blocks: the correlate stage in overlap-save sections wherever the template allows
-        const bool unsectioned = path == THR_PATH_UNSECTIONED || path == THR_PATH_UNSECTIONED_GENERIC_ROWS;
-        h->seg = h->lng && !gate && !unsectioned && plan_sections(d, s->template_len);
-        if (!h->seg) d.n_seg = 0;
-        // block_len 16384, short template(s), no stddev term: the correlate stage as 4096-sample
-        // sections (detect16k_sec.hip); stage dumps and every other launch keep k_correlate
-        h->sec4k = h->fast && !gate && !preshift_num && d.variant == 0 && !d.cor_want_std &&
-                   !unsectioned && plan_sections_4k(d, s->template_len);
-        if (!h->seg && !h->sec4k) d.n_seg = 0;
-        // why not sectioned: the first reason that applies (thr_get_path_info)
-        h->why_unsectioned = (h->seg || h->sec4k)                       ? THR_WHY_SECTIONED
-                             : (multipass || unsectioned)               ? THR_WHY_PATH
-                             : (preshift_num || d.variant != 0 || gate) ? THR_WHY_VARIANT
-                             : !(h->fast || h->lng)                     ? THR_WHY_BLOCK_LEN
-                             : (h->fast && d.cor_want_std)              ? THR_WHY_STDDEV
-                                                                        : THR_WHY_GEOMETRY;
-
-        h->cfg.templates = s->templates;
-        rc = build_constants(h);
-        if (rc == THR_OK && preshift_num) rc = build_preshift_bank(h);
-        h->cfg.templates = nullptr;
-        if (rc != THR_OK) break;
-
-#define CREATE_TRY(expr)                                                              \
-    if ((expr) != hipSuccess) {                                                       \
-        rc = fail(THR_ERR_DEVICE, "%s failed (%s)", #expr, hipGetErrorString(hipGetLastError())); \
-        break;                                                                        \
+    if (hipSetDevice(h->device) != hipSuccess)
+        return fail(THR_ERR_DEVICE, "hipSetDevice(%d) failed", h->device);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, h->device) != hipSuccess)
+        return fail(THR_ERR_DEVICE, "hipGetDeviceProperties failed");
+    h->n_cu = prop.multiProcessorCount;
+    if ((h->fast || h->lng || thr::small_supported(n)) &&
+        size_t(prop.maxSharedMemoryPerMultiProcessor) < thr::lds_bytes_16k())
+        return fail(THR_ERR_DEVICE, "device has %zu B LDS per CU, need %zu",
+                    size_t(prop.maxSharedMemoryPerMultiProcessor), thr::lds_bytes_16k());
+    thr::DevCfg& d = h->dev;
+    d.block_len = n;
+    d.history_len = s->history_len;
+    d.n_templates = s->n_templates;
+    d.carrier_len = s->carrier_len > 0 ? s->carrier_len : s->template_len;
+    if (gate) {       // cardet_normalize_window (checked by create_gate): [min, max], swapped if reversed
+        int lo = s->carrier_window[0], hi = s->carrier_window[1];
+        if (lo < 0) lo += n;
+        if (hi < 0) hi += n;
+        d.n_templates = 0;
+        d.carrier_len = 1;
+        d.win_lo = std::min(lo, hi);
+        d.win_count = std::abs(hi - lo) + 1;
+    } else
+        THR_TRY(window_indices(s->carrier_window[0], s->carrier_window[1], n, &d.win_lo, &d.win_count));
+    // soa_estimator.py:20-39
+    const int corr_len = n - s->template_len + 1;
+    const int pad = s->history_len - s->template_len + 1;
+    d.corr_lo = pad / 2;
+    d.corr_hi = corr_len - (pad - pad / 2);
+    d.corr_len = corr_len;
+    if (!gate && d.corr_hi <= d.corr_lo)
+        return fail(THR_ERR_ARG, "empty correlation window [%d, %d)", d.corr_lo, d.corr_hi);
+    for (int i = 0; i < 3; ++i) {
+        d.car_thr[i] = s->carrier_thresh[i];
+        d.cor_thr[i] = s->corr_thresh[i];
     }
-        // (the > 64 KiB dynamic-LDS opt-in is per device and kernel, not per handle: each family of
-        // kernels is prepared once per device and process -- dozens of hipFuncSetAttribute calls
-        // that a second handle on the same device need not repeat)
-        static std::mutex prep_mu;
-        static std::vector<unsigned> prepared;      // per device: bit per kernel family / block length
-        auto once = [&](unsigned bit, auto&& fn) -> hipError_t {
-            std::lock_guard<std::mutex> lk(prep_mu);
-            if (prepared.size() <= size_t(h->device)) prepared.resize(size_t(h->device) + 1, 0u);
-            if (prepared[h->device] & bit) return hipSuccess;
-            const hipError_t e = fn();
-            if (e == hipSuccess) prepared[h->device] |= bit;
-            return e;
-        };
-        const unsigned len_bit = 1u << (8 + (31 - __builtin_clz(unsigned(n))) % 20);   // (per block length)
-        if (h->fast) CREATE_TRY(once(1u, [] { return thr::prepare_16k(); }));
-        if (h->fast && preshift_num) CREATE_TRY(once(2u, [] { return thr::prepare_preshift_16k(); }));
-        if (h->small) CREATE_TRY(once(len_bit, [&] { return thr::prepare_small(n); }));
-        if (h->seg) {
-            CREATE_TRY(once(4u, [] { return thr::prepare_seg(); }));
-        }
-        if (h->lng) {
-            CREATE_TRY(once(len_bit, [&] { return thr::prepare_long(n); }));
-            const int r0 = n / 16384;
-            // sub-batch: large enough to amortise the kernels' launch latency, ramps and tails
-            // (the exchange rows no longer grow with it -- one row set per workgroup -- so the
-            // sub-batch is as large as the small per-block buffers allow: fewer kernel ramps and
-            // tails, +3.7 % from 4096 to 16384 blocks)
-            h->long_batch = std::min(s->max_batch, std::max(64, 16384 / std::max(1, s->n_templates)));
-            const size_t lb = size_t(h->long_batch);
-            const size_t win_w = size_t(std::min(h->dev.win_count + 6, n));
-            // (the decimation-in-time carrier stage parks R0 complex values per window bin here)
-            CREATE_TRY(hipMalloc(&h->d_win_pow, lb * win_w * sizeof(float) * 2 * r0));
-            CREATE_TRY(hipMalloc(&h->d_partial, lb * r0 * 2 * sizeof(float)));
-            if (gate) {      // (no correlate stage: none of its exchange buffers)
-                h->long_chunk = 0;
-            } else {
+#ifdef THR_DEV
+    if (h->d_timeline.alloc(128 * sizeof(unsigned long long)) == hipSuccess)
+        hipMemset(h->d_timeline, 0, 128 * sizeof(unsigned long long));
+    d.timeline = h->d_timeline;
+#endif
+    d.variant = variant >= 0 ? variant : (preshift_num ? 1 : 0);     // (THR_VARIANT_GATE: the tag of a thr_gate_handle)
+    d.interp = d.variant == 1 ? interp : 0;
+    d.car_want_std = !gate && s->carrier_thresh[2] != 0.0;     // (the gate has no stddev term)
+    d.car_prune = 0;
+    bool prune_ok = !d.car_want_std;
+#ifdef THR_DEV
+    if (getenv("THR_NO_PRUNE")) prune_ok = false;   // dev A/B: the full-spectrum carrier kernel
+#endif
+    if (prune_ok) {
+        // long blocks: R0 sub-transforms, each pruned to its 128 lowest bins (mode 1 only)
+        const int span = 128 * (h->lng ? n / 16384 : 1);
+        if (d.win_lo >= 3 && d.win_lo + d.win_count + 3 <= span)
+            d.car_prune = 1;  // window and fit margin already inside bins [0, span)
+        else if (d.win_count + 6 <= 128 && !h->lng)
+            d.car_prune = 2;  // any narrow window: pre-shift by win_lo - 3
+    }
+    d.cor_want_std = s->corr_thresh[2] != 0.0;
+    d.no_row_geom = path == THR_PATH_GENERIC_ROWS || path == THR_PATH_UNSECTIONED_GENERIC_ROWS;
+    h->small = thr::small_supported(n) && !multipass && !preshift_num;
+    // long blocks: the correlate stage in overlap-save sections wherever the template allows
+    const bool unsectioned = path == THR_PATH_UNSECTIONED || path == THR_PATH_UNSECTIONED_GENERIC_ROWS;
+    h->seg = h->lng && !gate && !unsectioned && plan_sections(d, s->template_len);
+    if (!h->seg) d.n_seg = 0;
+    // block_len 16384, short template(s), no stddev term: the correlate stage as 4096-sample
+    // sections (detect16k_sec.hip); stage dumps and every other launch keep k_correlate
+    h->sec4k = h->fast && !gate && !preshift_num && d.variant == 0 && !d.cor_want_std &&
+               !unsectioned && plan_sections_4k(d, s->template_len);
+    if (!h->seg && !h->sec4k) d.n_seg = 0;
+    // why not sectioned: the first reason that applies (thr_get_path_info)
+    h->why_unsectioned = (h->seg || h->sec4k)                       ? THR_WHY_SECTIONED
+                         : (multipass || unsectioned)               ? THR_WHY_PATH
+                         : (preshift_num || d.variant != 0 || gate) ? THR_WHY_VARIANT
+                         : !(h->fast || h->lng)                     ? THR_WHY_BLOCK_LEN
+                         : (h->fast && d.cor_want_std)              ? THR_WHY_STDDEV
+                                                                    : THR_WHY_GEOMETRY;
+
+    h->cfg.templates = s->templates;
+    int rc = build_constants(h.get());
+    if (rc == THR_OK && preshift_num) rc = build_preshift_bank(h.get());
+    h->cfg.templates = nullptr;
+    if (rc != THR_OK) return rc;
+
+    // (the > 64 KiB dynamic-LDS opt-in is per device and kernel, not per handle: each family of
+    // kernels is prepared once per device and process -- dozens of hipFuncSetAttribute calls
+    // that a second handle on the same device need not repeat)
+    static std::mutex prep_mu;
+    static std::vector<unsigned> prepared;      // per device: bit per kernel family / block length
+    auto once = [&](unsigned bit, auto&& fn) -> hipError_t {
+        std::lock_guard<std::mutex> lk(prep_mu);
+        if (prepared.size() <= size_t(h->device)) prepared.resize(size_t(h->device) + 1, 0u);
+        if (prepared[h->device] & bit) return hipSuccess;
+        const hipError_t e = fn();
+        if (e == hipSuccess) prepared[h->device] |= bit;
+        return e;
+    };
+    const unsigned len_bit = 1u << (8 + (31 - __builtin_clz(unsigned(n))) % 20);   // (per block length)
+    if (h->fast) HIP_TRY(once(1u, [] { return thr::prepare_16k(); }));
+    if (h->fast && preshift_num) HIP_TRY(once(2u, [] { return thr::prepare_preshift_16k(); }));
+    if (h->small) HIP_TRY(once(len_bit, [&] { return thr::prepare_small(n); }));
+    if (h->seg) HIP_TRY(once(4u, [] { return thr::prepare_seg(); }));
+    if (h->lng) {
+        HIP_TRY(once(len_bit, [&] { return thr::prepare_long(n); }));
+        const int r0 = n / 16384;
+        // sub-batch: large enough to amortise the kernels' launch latency, ramps and tails
+        // (the exchange rows no longer grow with it -- one row set per workgroup -- so the
+        // sub-batch is as large as the small per-block buffers allow: fewer kernel ramps and
+        // tails, +3.7 % from 4096 to 16384 blocks)
+        h->long_batch = std::min(s->max_batch, std::max(64, 16384 / std::max(1, s->n_templates)));
+        const size_t lb = size_t(h->long_batch);
+        const size_t win_w = size_t(std::min(h->dev.win_count + 6, n));
+        // (the decimation-in-time carrier stage parks R0 complex values per window bin here)
+        HIP_TRY(h->d_win_pow.alloc(lb * win_w * sizeof(float) * 2 * r0));
+        HIP_TRY(h->d_partial.alloc(lb * r0 * 2 * sizeof(float)));
+        if (gate) {      // (no correlate stage: none of its exchange buffers)
+            h->long_chunk = 0;
+        } else {
             h->long_chunk = std::min(h->long_batch, thr::long_chunk_blocks(n, s->n_templates));
             const size_t lc = size_t(h->long_chunk);
             // (one chunk of the two-kernel form, or one row per workgroup of the fused form)
             const size_t rows = std::max(lc, size_t(std::min(h->long_batch, h->n_cu)));
-            CREATE_TRY(hipMalloc(&h->d_dsub, rows * s->n_templates * size_t(n) * sizeof(float2)));
-            CREATE_TRY(hipMalloc(&h->d_xhat_scratch, size_t(h->n_cu) * 16384 * sizeof(float2)));
-            }
-            if (h->seg)
-                CREATE_TRY(hipMalloc(&h->d_seg_stats, lb * s->n_templates * size_t(d.n_seg) * sizeof(thr::CorrStats)));
+            HIP_TRY(h->d_dsub.alloc(rows * s->n_templates * size_t(n) * sizeof(float2)));
+            HIP_TRY(h->d_xhat_scratch.alloc(size_t(h->n_cu) * 16384 * sizeof(float2)));
         }
-        if (!h->fast && !h->lng) {
-            // sub-batch so that the 3 ping-pong buffers stay near 256 MiB (Infinity-Cache sized)
-            const size_t per_block = size_t(3) * n * sizeof(float2);
-            h->gen_batch = int(std::max<size_t>(1, std::min<size_t>(size_t(s->max_batch),
-                                                                    (size_t(256) << 20) / per_block)));
-            if (!h->small)   // (short blocks run LDS-resident)
-                CREATE_TRY(hipMalloc(&h->d_gen_scratch, thr::generic_scratch_bytes(n, h->gen_batch)));
-        }
-        CREATE_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-        h->stream = h->own_stream;
-        const size_t mb = size_t(s->max_batch);
-        CREATE_TRY(hipMalloc(&h->d_stats, mb * sizeof(thr::CarStats)));
-        if (gate) {
-            CREATE_TRY(hipMalloc(&gh->d_gate_pos, mb * sizeof(int)));
-            CREATE_TRY(hipMalloc(&gh->d_gate_count, 2 * sizeof(int)));
-            CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&gh->h_gate_count), 2 * sizeof(int), hipHostMallocDefault));
-            CREATE_TRY(hipMalloc(&gh->d_gate_rec, mb * sizeof(thr_record)));
-            CREATE_TRY(hipMalloc(&gh->d_gate_off, 2 * mb * sizeof(long long)));
-        } else {
-            CREATE_TRY(hipMalloc(&h->d_shifts, mb * sizeof(thr::ShiftParams)));
-            CREATE_TRY(hipMalloc(&h->d_corr_stats, mb * s->n_templates * sizeof(thr::CorrStats)));
-        }
-        if (h->sec4k)
-            CREATE_TRY(hipMalloc(&h->d_seg_stats, mb * s->n_templates * size_t(d.n_seg) * sizeof(thr::CorrStats)));
-        CREATE_TRY(hipMalloc(&h->d_work_list, mb * sizeof(int)));
-        CREATE_TRY(hipMalloc(&h->d_work_count, 4 * sizeof(int)));  // [0] work count, [1] dynamic cursor
-        CREATE_TRY(hipMemset(h->d_work_count, 0, 4 * sizeof(int)));  // re-armed by k_finish
-        CREATE_TRY(hipMalloc(&h->d_ncompact, sizeof(int)));
-#undef CREATE_TRY
-    } while (0);
-    if (rc != THR_OK) {
-        thr_handle* dead = h;
-        h = nullptr;
-        thr_destroy(dead);
-        return rc;
+        if (h->seg)
+            HIP_TRY(h->d_seg_stats.alloc(lb * s->n_templates * size_t(d.n_seg) * sizeof(thr::CorrStats)));
     }
-    *out = h;
+    if (!h->fast && !h->lng) {
+        // sub-batch so that the 3 ping-pong buffers stay near 256 MiB (Infinity-Cache sized)
+        const size_t per_block = size_t(3) * n * sizeof(float2);
+        h->gen_batch = int(std::max<size_t>(1, std::min<size_t>(size_t(s->max_batch),
+                                                                (size_t(256) << 20) / per_block)));
+        if (!h->small)   // (short blocks run LDS-resident)
+            HIP_TRY(h->d_gen_scratch.alloc(thr::generic_scratch_bytes(n, h->gen_batch)));
+    }
+    HIP_TRY(h->own_stream.create(hipStreamNonBlocking));
+    h->stream = h->own_stream;
+    const size_t mb = size_t(s->max_batch);
+    HIP_TRY(h->d_stats.alloc(mb * sizeof(thr::CarStats)));
+    if (gate) {
+        HIP_TRY(gh->d_gate_pos.alloc(mb * sizeof(int)));
+        HIP_TRY(gh->d_gate_count.alloc(2 * sizeof(int)));
+        HIP_TRY(gh->h_gate_count.alloc(2 * sizeof(int)));
+        HIP_TRY(gh->d_gate_rec.alloc(mb * sizeof(thr_record)));
+        HIP_TRY(gh->d_gate_off.alloc(2 * mb * sizeof(long long)));
+    } else {
+        HIP_TRY(h->d_shifts.alloc(mb * sizeof(thr::ShiftParams)));
+        HIP_TRY(h->d_corr_stats.alloc(mb * s->n_templates * sizeof(thr::CorrStats)));
+    }
+    if (h->sec4k)
+        HIP_TRY(h->d_seg_stats.alloc(mb * s->n_templates * size_t(d.n_seg) * sizeof(thr::CorrStats)));
+    HIP_TRY(h->d_work_list.alloc(mb * sizeof(int)));
+    HIP_TRY(h->d_work_count.alloc(4 * sizeof(int)));  // [0] work count, [1] dynamic cursor
+    HIP_TRY(hipMemset(h->d_work_count, 0, 4 * sizeof(int)));  // re-armed by k_finish
+    HIP_TRY(h->d_ncompact.alloc(sizeof(int)));
+    *out = h.release();
     return THR_OK;
 }
 
+// The order: the device the handle lives on; nothing of the handle's may still run on its two streams; the
+// window's threads stop (they call hipHostUnregister: they go while the runtime still knows the handle's
+// device and before anything is freed under them); then the handle's members give back what they own --
+// a gate handle's own members first (~thr_handle is virtual), then events and buffers, the streams last
+// (host_internal.hpp declares them first).  A stream set with thr_set_stream is the caller's.
 void thr_destroy(thr_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
-    if (h->hp.copy) (void)hipStreamSynchronize(h->hp.copy);
+    if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
     h->win.close();
-    if (h->hp.ready || h->hp.copy) {
-        auto& p = h->hp;
-        if (p.copy) {
-            (void)hipStreamSynchronize(p.copy);
-            (void)hipStreamDestroy(p.copy);
-        }
-        if (p.h_bad) (void)hipHostFree(p.h_bad);
-        for (int b = 0; b < thr_handle::kPipeDepth; ++b) {
-            if (p.ev_h2d[b]) (void)hipEventDestroy(p.ev_h2d[b]);
-            if (p.ev_done[b]) (void)hipEventDestroy(p.ev_done[b]);
-            if (p.h_rec[b]) (void)hipHostFree(p.h_rec[b]);
-            if (p.h_meta[b]) (void)hipHostFree(p.h_meta[b]);
-            for (void* q : {p.d_in[b], static_cast<void*>(p.d_idx[b]), static_cast<void*>(p.d_rec[b]),
-                            static_cast<void*>(p.d_text[b]), static_cast<void*>(p.d_bad[b])})
-                if (q) (void)hipFree(q);
-        }
-    }
-    for (auto& v : h->pending)
-        for (auto& e : v) h->free_events.push_back(e);
-    for (auto& e : h->free_events) {
-        (void)hipEventDestroy(e.a);
-        (void)hipEventDestroy(e.b);
-    }
-    thr_gate_handle* gh = thr_gate_of(h);
-    if (gh) {
-        if (gh->h_gate_count) (void)hipHostFree(gh->h_gate_count);
-        if (gh->h_gate_slots) (void)hipHostFree(gh->h_gate_slots);
-        for (void* b : {static_cast<void*>(gh->d_gate_pos), static_cast<void*>(gh->d_gate_count), static_cast<void*>(gh->d_gate_rec),
-                        gh->d_gate_slots, gh->d_gate_text, static_cast<void*>(gh->d_gate_off)})
-            if (b) (void)hipFree(b);
-    }
-    void* bufs[] = {h->d_tables, h->d_twn, h->d_tspec, h->d_stats, h->d_shifts, h->d_corr_stats, h->d_gen_scratch, h->d_tspec_nat, h->d_bank, h->d_gtw, h->d_tspec16k, h->d_tspec4k, h->d_ctab_pair, h->d_park, h->d_seg_stats, h->d_win_pow, h->d_partial, h->d_dsub, h->d_work_list,
-                    h->d_work_count, h->d_xhat_scratch, h->d_ncompact, h->d_compact_tiles, h->d_in, h->d_idx, h->d_rec, h->d_forced};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    if (gh)
-        delete gh;
-    else
-        delete h;
+    delete h;
 }
 
 int thr_set_wait_mode(thr_handle* h, int sleeping) try {
@@ -931,7 +849,7 @@ int thr_profile_read(thr_handle* h, double ms[THR_N_KERNEL_SLOTS],
                 h->ms[s] += t;
                 h->launches[s] += 1;
             }
-            h->free_events.push_back(e);
+            h->free_events.push_back(std::move(e));
         }
         h->pending[s].clear();
         ms[s] = h->ms[s];
@@ -942,6 +860,14 @@ int thr_profile_read(thr_handle* h, double ms[THR_N_KERNEL_SLOTS],
     return THR_OK;
 } catch (...) {
     return thr::on_exception("thr_profile_read");
+}
+
+int thr_debug_live_resources(int64_t out[4]) try {
+    if (!out) return fail(THR_ERR_ARG, "thr_debug_live_resources: null argument");
+    for (int k = 0; k < 4; ++k) out[k] = thr::g_live[k].load();
+    return THR_OK;
+} catch (...) {
+    return thr::on_exception("thr_debug_live_resources");
 }
 
 #ifdef THR_DEV

@@ -368,7 +368,7 @@ extern "C" int thr_match(int device_id, size_t n_in, const int32_t* rxid, const 
     const int n = int(n_in);
     hipStream_t s = nullptr;
     Event ev[4];
-    for (Event& e : ev) M_TRY(hipEventCreate(&e.e));
+    for (Event& e : ev) M_TRY(e.create());
 
     DevBuf d_rx, d_tx, d_ts, d_en;
     M_TRY(d_rx.alloc(size_t(n) * 4));

@@ -11,18 +11,15 @@ int ensure_pipe(thr_handle* h) {
     auto& p = h->hp;
     if (p.ready) return THR_OK;
     const size_t mb = size_t(h->cfg.max_batch), nt = size_t(h->cfg.n_templates);
-    HIP_TRY(hipStreamCreateWithFlags(&p.copy, hipStreamNonBlocking));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p.h_bad), thr_handle::kPipeDepth * sizeof(int),
-                          hipHostMallocDefault));
-    for (int b = 0; b < thr_handle::kPipeDepth; ++b) {
-        HIP_TRY(hipEventCreateWithFlags(&p.ev_h2d[b], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&p.ev_done[b], hipEventDisableTiming));
-        HIP_TRY(hipMalloc(&p.d_idx[b], 2 * mb * sizeof(long long)));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p.h_meta[b]), 2 * mb * sizeof(long long),
-                              hipHostMallocDefault));
-        HIP_TRY(hipMalloc(&p.d_rec[b], mb * nt * sizeof(thr_record)));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p.h_rec[b]), mb * nt * sizeof(thr_record),
-                              hipHostMallocDefault));
+    HIP_TRY(h->copy_stream.create(hipStreamNonBlocking));
+    HIP_TRY(p.h_bad.alloc(thr_handle::kPipeDepth * sizeof(int)));
+    for (auto& s : p.slot) {
+        HIP_TRY(s.ev_h2d.create(hipEventDisableTiming));
+        HIP_TRY(s.ev_done.create(hipEventDisableTiming));
+        HIP_TRY(s.d_idx.alloc(2 * mb * sizeof(long long)));
+        HIP_TRY(s.h_meta.alloc(2 * mb * sizeof(long long)));
+        HIP_TRY(s.d_rec.alloc(mb * nt * sizeof(thr_record)));
+        HIP_TRY(s.h_rec.alloc(mb * nt * sizeof(thr_record)));
     }
     p.ready = true;
     return THR_OK;
@@ -37,7 +34,8 @@ int ensure_pipe(thr_handle* h) {
 // asynchronous copy per locked segment (a copy never straddles two registrations), the call
 // returns at once and buffer b remembers how far the window has been read.
 int pipe_h2d(thr_handle* h, int b, void* d_dst, const void* src, size_t bytes) {
-    h->hp.win_end[b] = 0;
+    auto& slot = h->hp.slot[b];
+    slot.win_end = 0;
     if (h->win.acquire(src, bytes)) {
         const uintptr_t a = reinterpret_cast<uintptr_t>(src);
         size_t done = 0;
@@ -47,27 +45,27 @@ int pipe_h2d(thr_handle* h, int b, void* d_dst, const void* src, size_t bytes) {
             const uintptr_t seg_end = h->win.base + (size_t((at - h->win.base) / h->win.kSeg) + 1) * h->win.kSeg;
             const size_t n = std::min<size_t>(bytes - done, size_t(seg_end - at));
             HIP_TRY(hipMemcpyAsync(static_cast<char*>(d_dst) + done, reinterpret_cast<const void*>(at), n,
-                                   hipMemcpyHostToDevice, h->hp.copy));
+                                   hipMemcpyHostToDevice, h->copy_stream));
             done += n;
         }
-        h->hp.win_lo[b] = a;
-        h->hp.win_end[b] = a + bytes;
+        slot.win_lo = a;
+        slot.win_end = a + bytes;
         return THR_OK;
     }
-    HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, h->hp.copy));
+    HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, h->copy_stream));
     return THR_OK;
 }
 
 // buffer b's chunk has left host memory (its H2D event or its done event has been waited for)
 void pipe_inputs_done(thr_handle* h, int b) {
-    auto& p = h->hp;
-    if (!p.win_end[b]) return;
-    uintptr_t upto = p.win_end[b];
-    p.win_end[b] = p.win_lo[b] = 0;
+    auto& s = h->hp.slot[b];
+    if (!s.win_end) return;
+    uintptr_t upto = s.win_end;
+    s.win_end = s.win_lo = 0;
     // nothing an open chunk still reads may be unlocked: a later chunk of a raw stream starts
     // 2 * history bytes BEFORE the end of this one, possibly in the segment below
-    for (int o = 0; o < thr_handle::kPipeDepth; ++o)
-        if (p.win_end[o]) upto = std::min(upto, p.win_lo[o]);
+    for (const auto& o : h->hp.slot)
+        if (o.win_end) upto = std::min(upto, o.win_lo);
     h->win.release_below(upto);
 }
 
@@ -75,16 +73,6 @@ void pipe_inputs_done(thr_handle* h, int b) {
 size_t pipe_chunk_blocks(const thr_handle* h, size_t bytes_per_block) {
     const size_t cap = std::max<size_t>(1, (size_t(64) << 20) / std::max<size_t>(1, bytes_per_block));
     return std::min(size_t(h->cfg.max_batch), cap);
-}
-
-int pipe_grow(void** buf, size_t* have, size_t need) {
-    if (*have >= need) return THR_OK;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc(buf, need + (need >> 3)));
-    *have = need + (need >> 3);
-    return THR_OK;
 }
 
 // Wait for an event.  hipEventSynchronize polls (the calling thread stays busy for the length of the
@@ -109,43 +97,38 @@ int wait_event(thr_handle* h, hipEvent_t ev) {
 
 // hand the finished chunk of buffer b to the caller (waits for it); THR_OK if nothing is pending
 int pipe_drain(thr_handle* h, int b) {
-    auto& p = h->hp;
-    if (p.pend_n[b] == 0) return THR_OK;
-    {
-        const int wrc = wait_event(h, p.ev_done[b]);
-        if (wrc != THR_OK) return wrc;
-    }
+    auto& s = h->hp.slot[b];
+    if (s.pend_n == 0) return THR_OK;
+    THR_TRY(wait_event(h, s.ev_done));
     pipe_inputs_done(h, b);
-    std::memcpy(p.pend_dst[b], p.h_rec[b], p.pend_n[b] * sizeof(thr_record));
-    const size_t n = p.pend_n[b], first = p.pend_first[b];
-    p.pend_n[b] = 0;
-    if (p.pend_card[b] && p.h_bad[b] != 0)
+    std::memcpy(s.pend_dst, s.h_rec, s.pend_n * sizeof(thr_record));
+    const size_t n = s.pend_n, first = s.pend_first;
+    s.pend_n = 0;
+    if (s.pend_card && h->hp.h_bad[b] != 0)
         return fail(THR_ERR_ARG, "%d .card payload(s) in blocks [%zu, %zu) are not valid base64",
-                    p.h_bad[b], first, first + n / size_t(h->cfg.n_templates));
+                    h->hp.h_bad[b], first, first + n / size_t(h->cfg.n_templates));
     return THR_OK;
 }
 
 // after the chunk's H2D copies were enqueued on the copy stream: make the main stream wait for them
 int pipe_inputs_enqueued(thr_handle* h, int b) {
-    auto& p = h->hp;
-    HIP_TRY(hipEventRecord(p.ev_h2d[b], p.copy));
-    HIP_TRY(hipStreamWaitEvent(h->stream, p.ev_h2d[b], 0));
+    HIP_TRY(hipEventRecord(h->hp.slot[b].ev_h2d, h->copy_stream));
+    HIP_TRY(hipStreamWaitEvent(h->stream, h->hp.slot[b].ev_h2d, 0));
     return THR_OK;
 }
 
 // after the chunk's kernels were enqueued on the main stream: records -> pinned staging, async
 int pipe_records_enqueued(thr_handle* h, int b, thr_record* dst, size_t n_rec, size_t first, bool card) {
-    auto& p = h->hp;
-    HIP_TRY(hipMemcpyAsync(p.h_rec[b], p.d_rec[b], n_rec * sizeof(thr_record), hipMemcpyDeviceToHost,
-                           h->stream));
+    auto& s = h->hp.slot[b];
+    HIP_TRY(hipMemcpyAsync(s.h_rec, s.d_rec, n_rec * sizeof(thr_record), hipMemcpyDeviceToHost, h->stream));
     if (card)
-        HIP_TRY(hipMemcpyAsync(p.h_bad + b, p.d_bad[b], sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->hp.h_bad + b, s.d_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
 
-    HIP_TRY(hipEventRecord(p.ev_done[b], h->stream));
-    p.pend_dst[b] = dst;
-    p.pend_n[b] = n_rec;
-    p.pend_first[b] = first;
-    p.pend_card[b] = card;
+    HIP_TRY(hipEventRecord(s.ev_done, h->stream));
+    s.pend_dst = dst;
+    s.pend_n = n_rec;
+    s.pend_first = first;
+    s.pend_card = card;
     return THR_OK;
 }
 
@@ -155,26 +138,18 @@ int pipe_finish(thr_handle* h, int rc) {   // drain every buffer; keeps the firs
         if (rc == THR_OK) rc = r;
     }
     if (rc != THR_OK) {
-        (void)hipStreamSynchronize(h->hp.copy);
+        (void)hipStreamSynchronize(h->copy_stream);
         (void)hipStreamSynchronize(h->stream);
-        for (int b = 0; b < thr_handle::kPipeDepth; ++b) h->hp.pend_n[b] = 0;
+        for (auto& s : h->hp.slot) s.pend_n = 0;
     }
     return rc;
 }
 
 int ensure_staging(thr_handle* h, int format) {
     const size_t need = size_t(h->cfg.max_batch) * h->cfg.block_len * (format == THR_IN_U8 ? 2 : 8);
-    if (h->d_in_bytes < need) {
-        if (h->d_in) (void)hipFree(h->d_in);
-        h->d_in = nullptr;
-        h->d_in_bytes = 0;
-        HIP_TRY(hipMalloc(&h->d_in, need));
-        h->d_in_bytes = need;
-    }
-    if (!h->d_idx) HIP_TRY(hipMalloc(&h->d_idx, size_t(h->cfg.max_batch) * sizeof(long long)));
-    if (!h->d_rec)
-        HIP_TRY(hipMalloc(&h->d_rec,
-                          size_t(h->cfg.max_batch) * h->cfg.n_templates * sizeof(thr_record)));
+    HIP_TRY(h->d_in.grow(need));
+    if (!h->d_idx) HIP_TRY(h->d_idx.alloc(size_t(h->cfg.max_batch) * sizeof(long long)));
+    if (!h->d_rec) HIP_TRY(h->d_rec.alloc(size_t(h->cfg.max_batch) * h->cfg.n_templates * sizeof(thr_record)));
     return THR_OK;
 }
 
@@ -476,7 +451,7 @@ int stream_stride(thr_handle* h, size_t* stride) {
 int chunk_samples(thr_handle* h, int b, const void* src, int format, size_t blk_bytes, size_t stride,
                          const int64_t* block_idx, int64_t first_idx, size_t nb, thr_record* dst,
                          size_t first) {
-    auto& p = h->hp;
+    auto& s = h->hp.slot[b];
     // dense blocks: nb * blk_bytes; raw stream: (nb - 1) strides + one whole block
     const size_t bytes = stride ? (nb - 1) * stride + blk_bytes : nb * blk_bytes;
     int rc;
@@ -487,25 +462,24 @@ int chunk_samples(thr_handle* h, int b, const void* src, int format, size_t blk_
         h->t_pipe_max[k] = std::max(h->t_pipe_max[k], t1 - t0);
         t0 = t1;
     };
-    if ((rc = pipe_grow(&p.d_in[b], &p.in_bytes[b], bytes)) != THR_OK) return rc;
+    HIP_TRY(s.d_in.grow(bytes, bytes >> 3));
     lap(0);
-    if ((rc = pipe_h2d(h, b, p.d_in[b], src, bytes)) != THR_OK) return rc;
+    if ((rc = pipe_h2d(h, b, s.d_in, src, bytes)) != THR_OK) return rc;
     lap(1);
     for (size_t i = 0; i < nb; ++i)
-        p.h_meta[b][i] = block_idx ? (long long)block_idx[i] : (long long)(first_idx + int64_t(i));
+        s.h_meta[i] = block_idx ? (long long)block_idx[i] : (long long)(first_idx + int64_t(i));
     lap(7);
-    HIP_TRY(hipMemcpyAsync(p.d_idx[b], p.h_meta[b], nb * sizeof(long long), hipMemcpyHostToDevice, p.copy));
+    HIP_TRY(hipMemcpyAsync(s.d_idx, s.h_meta, nb * sizeof(long long), hipMemcpyHostToDevice, h->copy_stream));
     lap(2);
     // (raw streams: hipStreamWaitEvent in here is where this thread meets the device's pace -- it
     // returns ~0.45 ms late per 2048-block chunk whatever precedes it on either stream, whatever
     // engine does the copy; profiles/README.md, round 5)
     if ((rc = pipe_inputs_enqueued(h, b)) != THR_OK) return rc;
     lap(6);
-    rc = run_batch(h, p.d_in[b], format, p.d_idx[b], int(nb), p.d_rec[b], nullptr, nullptr, nullptr, 0,
-                   false, stride);
+    rc = run_batch(h, s.d_in, format, s.d_idx, int(nb), s.d_rec, nullptr, nullptr, nullptr, 0, false, stride);
     if (rc != THR_OK) return rc;
     // (a template extraction in progress folds the batch's records and keeps the winner's samples here)
-    if ((rc = extract_after_chunk(h, b, p.d_in[b], format, stride, first, nb)) != THR_OK) return rc;
+    if ((rc = extract_after_chunk(h, b, s.d_in, format, stride, first, nb)) != THR_OK) return rc;
     lap(3);
     rc = pipe_records_enqueued(h, b, dst, nb * size_t(h->cfg.n_templates), first, false);
     lap(4);
@@ -515,7 +489,7 @@ int chunk_samples(thr_handle* h, int b, const void* src, int format, size_t blk_
 
 int chunk_card(thr_handle* h, int b, const char* text, size_t text_len, const int64_t* payload_off,
                       const int64_t* block_idx, size_t first, size_t nb, thr_record* dst) {
-    auto& p = h->hp;
+    auto& s = h->hp.slot[b];
     const size_t out_bytes = size_t(h->cfg.block_len) * 2;
     const size_t chars = ((out_bytes + 2) / 3) * 4;  // base64 payload length of one block
     // contiguous span of text covering the chunk's payloads: [lo, hi + chars)
@@ -537,28 +511,26 @@ int chunk_card(thr_handle* h, int b, const char* text, size_t text_len, const in
         h->t_pipe_max[k] = std::max(h->t_pipe_max[k], t1 - t0);
         t0 = t1;
     };
-    if ((rc = pipe_grow(reinterpret_cast<void**>(&p.d_text[b]), &p.text_bytes[b], span)) != THR_OK) return rc;
-    if ((rc = pipe_grow(&p.d_in[b], &p.in_bytes[b], nb * out_bytes)) != THR_OK) return rc;
-    if (!p.d_bad[b]) HIP_TRY(hipMalloc(&p.d_bad[b], sizeof(int)));
+    HIP_TRY(s.d_text.grow(span, span >> 3));
+    HIP_TRY(s.d_in.grow(nb * out_bytes, (nb * out_bytes) >> 3));
+    if (!s.d_bad) HIP_TRY(s.d_bad.alloc(sizeof(int)));
     lap(0);
-    long long* meta = p.h_meta[b];
+    long long* meta = s.h_meta;
     for (size_t i = 0; i < nb; ++i) {
         meta[i] = block_idx ? (long long)block_idx[first + i] : (long long)(first + i);
         meta[nb + i] = payload_off[first + i] - lo;
     }
     lap(2);
-    if ((rc = pipe_h2d(h, b, p.d_text[b], text + lo, span)) != THR_OK) return rc;
+    if ((rc = pipe_h2d(h, b, s.d_text, text + lo, span)) != THR_OK) return rc;
     lap(1);
-    HIP_TRY(hipMemcpyAsync(p.d_idx[b], meta, 2 * nb * sizeof(long long), hipMemcpyHostToDevice, p.copy));
-    HIP_TRY(hipMemsetAsync(p.d_bad[b], 0, sizeof(int), p.copy));
+    HIP_TRY(hipMemcpyAsync(s.d_idx, meta, 2 * nb * sizeof(long long), hipMemcpyHostToDevice, h->copy_stream));
+    HIP_TRY(hipMemsetAsync(s.d_bad, 0, sizeof(int), h->copy_stream));
     if ((rc = pipe_inputs_enqueued(h, b)) != THR_OK) return rc;
     lap(2);
-    HIP_TRY(thr::launch_b64_decode(p.d_text[b], p.d_idx[b] + nb, int(nb), int(out_bytes),
-                                   static_cast<unsigned char*>(p.d_in[b]), p.d_bad[b], h->stream));
-    rc = run_batch(h, p.d_in[b], THR_IN_U8, p.d_idx[b], int(nb), p.d_rec[b], nullptr, nullptr, nullptr,
-                   0, false);
+    HIP_TRY(thr::launch_b64_decode(s.d_text, s.d_idx + nb, int(nb), int(out_bytes), s.d_in, s.d_bad, h->stream));
+    rc = run_batch(h, s.d_in, THR_IN_U8, s.d_idx, int(nb), s.d_rec, nullptr, nullptr, nullptr, 0, false);
     if (rc != THR_OK) return rc;
-    if ((rc = extract_after_chunk(h, b, p.d_in[b], THR_IN_U8, 0, first, nb)) != THR_OK) return rc;
+    if ((rc = extract_after_chunk(h, b, s.d_in, THR_IN_U8, 0, first, nb)) != THR_OK) return rc;
     lap(3);
     rc = pipe_records_enqueued(h, b, dst, nb * size_t(h->cfg.n_templates), first, true);
     lap(4);

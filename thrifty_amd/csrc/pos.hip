@@ -351,7 +351,7 @@ extern "C" int thr_pos(int device_id, size_t n_groups, const int64_t* group_ptr,
     const int ng = int(n_groups);
     hipStream_t s = nullptr;
     Event ev[4];
-    for (Event& e : ev) P_TRY(hipEventCreate(&e.e));
+    for (Event& e : ev) P_TRY(e.create());
 
     DevBuf d_ptr, d_rx0, d_rx1, d_tdoa, d_snr, d_xy;
     P_TRY(d_ptr.alloc((n_groups + 1) * 8));

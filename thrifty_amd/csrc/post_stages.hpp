@@ -1,9 +1,10 @@
 // The four post-detect stages as cores on device pointers (identify.hip, match.hip, tdoa.hip, pos.hip),
-// and what their files shared by copy before: DevBuf, Event, with_temp and the hipError_t -> THR_ERR_DEVICE
-// macro.  A core takes device pointers and a stream, owns its temporaries, and leaves its outputs in a
-// struct of device buffers that the caller owns, with the counts in plain members.  The extern "C"
-// entry points (thr_identify, thr_match, thr_tdoa, thr_pos) are: argument checks, copies in, the core,
-// copies out, the time record; thr_postdetect (postdetect.hip) runs the four cores back to back.
+// and what their files shared by copy before: with_temp and the hipError_t -> THR_ERR_DEVICE macro (the
+// owning DevBuf and Event are hip_own.hpp's).  A core takes device pointers and a stream, owns its
+// temporaries, and leaves its outputs in a struct of device buffers that the caller owns, with the counts
+// in plain members.  The extern "C" entry points (thr_identify, thr_match, thr_tdoa, thr_pos) are: argument
+// checks, copies in, the core, copies out, the time record; thr_postdetect (postdetect.hip) runs the four
+// cores back to back.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,35 +12,12 @@
 #include <cstdint>
 
 #include "../../include/thrifty_hip.h"
+#include "hip_own.hpp"
 
 namespace thr {
 
 int fail_msg(int code, const char* fmt, ...);
 int on_exception(const char* who) noexcept;  // handle.hip
-
-struct DevBuf {
-    void* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    hipError_t alloc(size_t bytes) {
-        release();
-        return hipMalloc(&p, bytes ? bytes : 1);
-    }
-    template <class T>
-    T* as() const { return static_cast<T*>(p); }
-};
-struct Event {
-    hipEvent_t e = nullptr;
-    ~Event() {
-        if (e) (void)hipEventDestroy(e);
-    }
-};
 
 #define THR_HIP_TRY(expr)                                                                    \
     do {                                                                                     \

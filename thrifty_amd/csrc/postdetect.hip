@@ -237,8 +237,8 @@ extern "C" int thr_postdetect(int device_id, size_t n_in, const int32_t* rxid, c
     hipStream_t s = nullptr;
     const dim3 blk(kBlock);
     Event ev[6];
-    for (Event& e : ev) THR_HIP_TRY(hipEventCreate(&e.e));
-    for (Event& e : R->ev) THR_HIP_TRY(hipEventCreate(&e.e));
+    for (Event& e : ev) THR_HIP_TRY(e.create());
+    for (Event& e : R->ev) THR_HIP_TRY(e.create());
 
     // ---- copies in: the eight columns and the four small tables
     DevBuf d_rx, d_blk, d_ts, d_bin, d_off, d_soa, d_en, d_no, d_rxids, d_xy, d_bids, d_dist;

@@ -675,7 +675,7 @@ extern "C" int thr_tdoa(int device_id, size_t n_det, const int32_t* rx, const do
     const size_t n_idx = size_t(match_ptr[n_matches]);
     hipStream_t s = nullptr;
     Event ev[4];
-    for (Event& e : ev) T_TRY(hipEventCreate(&e.e));
+    for (Event& e : ev) T_TRY(e.create());
 
     DevBuf d_rx, d_ts, d_soa, d_en, d_no, d_ptr, d_idx, d_beacon, d_dist;
     T_TRY(d_rx.alloc(size_t(n) * 4));

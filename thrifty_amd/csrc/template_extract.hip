@@ -198,6 +198,10 @@ struct Armed {
     ~Armed() { t_armed = nullptr; }
 };
 
+struct ExtractDeleter {
+    void operator()(thr_extract* x) const { thr_extract_destroy(x); }
+};
+
 constexpr unsigned long long kMaxFed = 0xFFFFFFFFull;    // positions are 32 bits of the fold's key
 
 int feed_enter(thr_extract* x, const char* who, size_t n_blocks) {
@@ -207,29 +211,15 @@ int feed_enter(thr_extract* x, const char* who, size_t n_blocks) {
     return THR_OK;
 }
 
-void release(thr_extract* x) {
-    if (!x) return;
-    if (x->h) (void)hipSetDevice(x->h->device);
-    if (x->d_state) (void)hipFree(x->d_state);
-    if (x->d_keep) (void)hipFree(x->d_keep);
-    if (x->d_out) (void)hipFree(x->d_out);
-    for (int b = 0; b < thr_handle::kPipeDepth; ++b) {
-        if (x->h_ts[b]) (void)hipHostFree(x->h_ts[b]);
-        if (x->d_ts[b]) (void)hipFree(x->d_ts[b]);
-    }
-    delete x;
-}
-
 int create_body(thr_extract* x) {
     thr_handle* h = x->h;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMalloc(&x->d_state, sizeof(thr::ExtractState)));
-    HIP_TRY(hipMalloc(&x->d_keep, size_t(h->cfg.block_len) * 8));
-    HIP_TRY(hipMalloc(&x->d_out, size_t(h->cfg.template_len) * sizeof(double)));
+    HIP_TRY(x->d_state.alloc(sizeof(thr::ExtractState)));
+    HIP_TRY(x->d_keep.alloc(size_t(h->cfg.block_len) * 8));
+    HIP_TRY(x->d_out.alloc(size_t(h->cfg.template_len) * sizeof(double)));
     for (int b = 0; b < thr_handle::kPipeDepth; ++b) {
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&x->h_ts[b]), size_t(h->cfg.max_batch) * sizeof(double),
-                              hipHostMallocDefault));
-        HIP_TRY(hipMalloc(&x->d_ts[b], size_t(h->cfg.max_batch) * sizeof(double)));
+        HIP_TRY(x->h_ts[b].alloc(size_t(h->cfg.max_batch) * sizeof(double)));
+        HIP_TRY(x->d_ts[b].alloc(size_t(h->cfg.max_batch) * sizeof(double)));
     }
     HIP_TRY(hipMemsetAsync(x->d_state, 0, sizeof(thr::ExtractState), h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -250,7 +240,7 @@ int extract_after_chunk(thr_handle* h, int b, const void* d_in, int format, size
         d_ts = x->d_ts[b];
     }
     const unsigned blk_bytes = unsigned(h->cfg.block_len) * (format == THR_IN_U8 ? 2u : 8u);
-    HIP_TRY(thr::launch_best_fold(h->hp.d_rec[b], d_ts, x->cur_ts_all, int(nb), x->fed, x->max_offset, x->d_state,
+    HIP_TRY(thr::launch_best_fold(h->hp.slot[b].d_rec, d_ts, x->cur_ts_all, int(nb), x->fed, x->max_offset, x->d_state,
                                   h->stream));
     HIP_TRY(thr::launch_keep_block(x->d_state, d_in, stride ? stride : blk_bytes, blk_bytes, format, x->fed,
                                    int(nb), x->d_keep, h->stream));
@@ -277,25 +267,21 @@ int thr_extract_create(thr_handle* h, double max_offset, thr_extract** out) try 
         return fail(THR_ERR_ARG, "thr_extract_create: template extraction takes ONE base template, this handle "
                                  "has %d", h->cfg.n_templates);
     if (!(max_offset >= 0)) return fail(THR_ERR_ARG, "thr_extract_create: max_offset must be >= 0");
-    thr_extract* x = new thr_extract;
+    std::unique_ptr<thr_extract, thr::host::ExtractDeleter> x(new thr_extract);
     x->h = h;
     x->max_offset = max_offset;
-    const int rc = thr::host::create_body(x);
-    if (rc != THR_OK) {
-        thr::host::release(x);
-        return rc;
-    }
-    *out = x;
+    THR_TRY(thr::host::create_body(x.get()));
+    *out = x.release();
     return THR_OK;
 } catch (...) {
     return thr::on_exception("thr_extract_create");
 }
 
+// the device the buffers live on, then the extraction's members give back what they own
 void thr_extract_destroy(thr_extract* x) {
-    try {
-        thr::host::release(x);
-    } catch (...) {
-    }
+    if (!x) return;
+    if (x->h) (void)hipSetDevice(x->h->device);
+    delete x;
 }
 
 int thr_extract_reset(thr_extract* x) try {

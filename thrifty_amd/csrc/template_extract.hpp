@@ -46,11 +46,11 @@ int extract_after_chunk(thr_handle* h, int b, const void* d_in, int format, size
 struct thr_extract {
     thr_handle* h = nullptr;
     double max_offset = 0;
-    thr::ExtractState* d_state = nullptr;
-    void* d_keep = nullptr;                              // 8 * block_len bytes
-    double* d_out = nullptr;                             // [template_len]
-    double* h_ts[thr_handle::kPipeDepth] = {};           // pinned [max_batch]: a chunk's timestamps
-    double* d_ts[thr_handle::kPipeDepth] = {};
+    Dev<thr::ExtractState> d_state;
+    Dev<void> d_keep;                                    // 8 * block_len bytes
+    Dev<double> d_out;                                   // [template_len]
+    Pinned<double> h_ts[thr_handle::kPipeDepth];         // [max_batch]: a chunk's timestamps
+    Dev<double> d_ts[thr_handle::kPipeDepth];
     unsigned long long fed = 0;                          // blocks fed since the reset
     // the call in progress (extract_after_chunk reads them)
     const double* cur_ts = nullptr;                      // [n_blocks] of the call, or nullptr: cur_ts_all
