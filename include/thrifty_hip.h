@@ -67,7 +67,9 @@ extern "C" {
  *    + thr_pos / thr_debug_pos_times -- the reference's `thrifty pos` (pos_est.py:31-156)
  *    + thr_postdetect / thr_post_fetch / thr_post_free / thr_debug_post_times -- identify, match, tdoa and
  *      pos in one call with device-resident intermediates (the reference's kitchen_sink.postdetect)
- *    + thr_debug_live_resources -- what the process holds of the HIP runtime (the handles own it) */
+ *    + thr_debug_live_resources -- what the process holds of the HIP runtime (the handles own it)
+ *    + thr_survey_create / _destroy / _reset / _shift / _pending / _feed / _feed_stream,
+ *      thr_debug_survey_geometry -- capture survey: mean spectrum, byte histogram, per-block byte sums */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -700,6 +702,50 @@ int thr_run_extract_card(thr_handle* h, const char* text, size_t text_len, const
                          thr_extract* x, thr_run_stats* stats);
 int thr_run_extract_stream(thr_handle* h, const uint8_t* stream, size_t n_bytes, int64_t first_block_idx,
                            const thr_run_opts* opts, thr_extract* x, thr_run_stats* stats);
+
+/*
+ * Capture survey -- the numbers behind the reference's scripts/fft_analysis.py, hist.py and noise_rms.py
+ * (the plots stay out): for a raw u8 capture cut into blocks like everything else, per interval of
+ * `integrate` consecutive blocks, the mean magnitude spectrum, the histogram of the byte values and, per
+ * block, the byte sums the block's energy follows from.  A trailing partial interval is never reported.
+ * Everything that leaves the library is an integer, so the results are bit-identical however a run is
+ * cut into calls, chunks, tiles or workgroups:
+ *   spec_sum[j][k] = sum over the blocks b of interval j of q_b[k],  q = rint(|FFT(x_b)[k]| * 2^S) as
+ *     uint32 (float32 magnitude, square root to 1 ulp, exact scaling, round-half-even), S = 30 - log2
+ *     (block_len) -- thr_survey_shift; the mean spectrum is spec_sum / (integrate * 2^S), natural bin order;
+ *   hist[j][v] = occurrences of byte value v among the 2 * block_len bytes of each block of interval j
+ *     (history bytes of overlapping blocks count in both blocks, as in the scripts);
+ *   sums[b] = (sum v, sum v^2) over block b's bytes: with c = (double)127.4f the block's energy
+ *     sum |x|^2 = (sum v^2 - 2 c sum v + 2 block_len c^2) / 128^2 exactly, noise_rms.py's norm its root.
+ * A thr_survey rides on ANY handle (a gate handle builds no template spectra) and is destroyed before it;
+ * same single-threaded rule; refused with THR_ERR_STATE while submitted batches are open.  block_len 16384
+ * (not THR_PATH_MULTIPASS) runs one fused kernel; other handles the carrier stage's spectrum dump and two
+ * small kernels (thr_debug_survey_geometry: fused, blocks per tile, workgroups).
+ *
+ * thr_survey_feed: n_blocks packed u8 blocks (host memory, any number; chunks of at most max_batch blocks
+ *   and of what 64 MiB of accumulator rows take).  The call completes (open + n_blocks) / integrate
+ *   intervals, written to spec_sum[cap_intervals][block_len] and hist[cap_intervals][256] from index 0;
+ *   fewer rows than that -> THR_ERR_ARG before any device work.  sums: [n_blocks][2] or NULL.  The open
+ *   interval's partial sums stay on the device.  Synchronous; copies go through the handle's input
+ *   window when one is set.  After an error the open interval may hold part of the failed call: reset.
+ * thr_survey_feed_stream: the same for raw-stream framing (thr_detect_stream: block i starts
+ *   2 (block_len - history_len) i bytes in; an odd difference -> THR_ERR_ARG); *n_blocks = blocks framed;
+ *   sums_capacity (in blocks) below that -> THR_ERR_ARG.
+ * thr_survey_pending: blocks fed since the reset, and how many of them wait in the open interval.
+ * thr_survey_reset: forget everything fed so far.
+ */
+typedef struct thr_survey thr_survey;
+int thr_survey_create(thr_handle* h, int integrate, thr_survey** out);
+void thr_survey_destroy(thr_survey* s);
+int thr_survey_reset(thr_survey* s);
+int thr_survey_shift(const thr_survey* s, int* shift);
+int thr_survey_pending(const thr_survey* s, uint64_t* blocks_fed, uint64_t* blocks_in_open_interval);
+int thr_survey_feed(thr_survey* s, const uint8_t* samples, size_t n_blocks, uint64_t* sums, uint64_t* spec_sum,
+                    uint64_t* hist, size_t cap_intervals, size_t* n_intervals);
+int thr_survey_feed_stream(thr_survey* s, const uint8_t* stream, size_t n_bytes, uint64_t* sums, size_t sums_capacity,
+                           size_t* n_blocks, uint64_t* spec_sum, uint64_t* hist, size_t cap_intervals,
+                           size_t* n_intervals);
+int thr_debug_survey_geometry(const thr_survey* s, int* tile_blocks, int* workgroups, int* fused);
 
 /* The settings a handle was created with (`templates` is NULL: the array is not retained). */
 int thr_get_settings(const thr_handle* h, thr_settings* out);

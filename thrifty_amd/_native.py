@@ -44,6 +44,8 @@ EXPORTS = [
     "thr_pos", "thr_debug_pos_times",
     "thr_postdetect", "thr_post_fetch", "thr_post_free", "thr_debug_post_times",
     "thr_debug_live_resources",
+    "thr_survey_create", "thr_survey_destroy", "thr_survey_reset", "thr_survey_shift", "thr_survey_pending",
+    "thr_survey_feed", "thr_survey_feed_stream", "thr_debug_survey_geometry",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -284,6 +286,15 @@ def load_library():
     lib.thr_post_free.restype = None
     lib.thr_debug_post_times.argtypes = [C.POINTER(C.c_double)]
     lib.thr_debug_live_resources.argtypes = [C.POINTER(C.c_int64)]
+    lib.thr_survey_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    lib.thr_survey_destroy.argtypes = [vp]
+    lib.thr_survey_destroy.restype = None
+    lib.thr_survey_reset.argtypes = [vp]
+    lib.thr_survey_shift.argtypes = [vp, ip]
+    lib.thr_survey_pending.argtypes = [vp, u64p, u64p]
+    lib.thr_survey_feed.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, szp]
+    lib.thr_survey_feed_stream.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, szp, vp, vp, C.c_size_t, szp]
+    lib.thr_debug_survey_geometry.argtypes = [vp, ip, ip, ip]
     _lib = lib
     return lib
 
@@ -1121,6 +1132,92 @@ class Extraction(object):
             raise ValueError(self._lib.thr_last_error().decode())
         _check(self._lib, rc)
         return rec[0], ts.value, out, n.value
+
+
+class Survey(object):
+    """A capture survey riding on an Engine (thr_survey_*): feed it the u8 blocks of a capture in any
+    batching; every call returns the intervals of `integrate` blocks it completed, as integers
+    (spec_sum uint64 [J, N], hist uint64 [J, 256]) with the fed blocks' byte sums (uint64 [B, 2]).  The
+    open interval stays on the device.  Any engine will do (Engine.gate builds no template spectra); it
+    must stay open while this object is."""
+
+    def __init__(self, engine, integrate=100):
+        self._lib, self._eng = engine._lib, engine
+        self.integrate = int(integrate)
+        s = C.c_void_p()
+        _check(self._lib, self._lib.thr_survey_create(engine._h, self.integrate, C.byref(s)))
+        self._s = s
+        shift = C.c_int(0)
+        _check(self._lib, self._lib.thr_survey_shift(self._s, C.byref(shift)))
+        self.shift = shift.value
+
+    def close(self):
+        if getattr(self, "_s", None):
+            if getattr(self._eng, "_h", None):      # (an engine that is gone took the device state with it)
+                self._lib.thr_survey_destroy(self._s)
+            self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # noqa: BLE001
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def reset(self):
+        _check(self._lib, self._lib.thr_survey_reset(self._s))
+
+    def pending(self):
+        """-> (blocks fed since the reset, blocks waiting in the open interval)"""
+        fed, waiting = C.c_uint64(0), C.c_uint64(0)
+        _check(self._lib, self._lib.thr_survey_pending(self._s, C.byref(fed), C.byref(waiting)))
+        return fed.value, waiting.value
+
+    def geometry(self):
+        """thr_debug_survey_geometry -> (blocks per tile, workgroups, fused kernel?)"""
+        tile, wgs, fused = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(self._lib, self._lib.thr_debug_survey_geometry(self._s, C.byref(tile), C.byref(wgs), C.byref(fused)))
+        return tile.value, wgs.value, bool(fused.value)
+
+    def _out(self, nb, cap_intervals):
+        cap = (self.pending()[1] + nb) // self.integrate if cap_intervals is None else int(cap_intervals)
+        n = self._eng.block_len
+        return (cap, np.zeros((nb, 2), dtype=np.uint64), np.zeros((max(1, cap), n), dtype=np.uint64),
+                np.zeros((max(1, cap), 256), dtype=np.uint64))
+
+    def feed(self, blocks, cap_intervals=None):
+        """thr_survey_feed: u8 [B, 2N] packed blocks -> (spec_sum [J, N], hist [J, 256], sums [B, 2]).
+        u8 only: anything else is refused like the library refuses a bad argument."""
+        a = np.asarray(blocks)
+        if a.dtype != np.uint8:
+            raise NativeError("Survey.feed: the survey takes raw u8 blocks, not %s (code %d)" % (a.dtype, ERR_ARG), ERR_ARG)
+        a = np.ascontiguousarray(a).reshape(-1, 2 * self._eng.block_len)
+        nb = a.shape[0]
+        cap, sums, spec, hist = self._out(nb, cap_intervals)
+        got = C.c_size_t(0)
+        _check(self._lib, self._lib.thr_survey_feed(self._s, a.ctypes.data if nb else None, nb, sums.ctypes.data,
+                                                    spec.ctypes.data, hist.ctypes.data, cap, C.byref(got)))
+        return spec[:got.value], hist[:got.value], sums
+
+    def feed_stream(self, stream, cap_intervals=None):
+        """thr_survey_feed_stream: raw u8 I/Q bytes, overlapping blocks framed on the device (see
+        Engine.detect_stream) -> (spec_sum, hist, sums [n_whole_blocks, 2])."""
+        eng = self._eng
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        stride = 2 * (eng.block_len - eng.history_len)
+        nb = 0 if buf.size < 2 * eng.block_len else (buf.size - 2 * eng.block_len) // stride + 1
+        cap, sums, spec, hist = self._out(nb, cap_intervals)
+        got, framed = C.c_size_t(0), C.c_size_t(0)
+        _check(self._lib, self._lib.thr_survey_feed_stream(self._s, buf.ctypes.data if buf.size else None, buf.size,
+                                                           sums.ctypes.data, nb, C.byref(framed), spec.ctypes.data,
+                                                           hist.ctypes.data, cap, C.byref(got)))
+        assert framed.value == nb
+        return spec[:got.value], hist[:got.value], sums
 
 
 TDOA_TASKS_PER_WORKGROUP = 4    # kWaves of csrc/tdoa.hip: one wavefront per task, four to a workgroup
