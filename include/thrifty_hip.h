@@ -69,7 +69,9 @@ extern "C" {
  *      pos in one call with device-resident intermediates (the reference's kitchen_sink.postdetect)
  *    + thr_debug_live_resources -- what the process holds of the HIP runtime (the handles own it)
  *    + thr_survey_create / _destroy / _reset / _shift / _pending / _feed / _feed_stream,
- *      thr_debug_survey_geometry -- capture survey: mean spectrum, byte histogram, per-block byte sums */
+ *      thr_debug_survey_geometry -- capture survey: mean spectrum, byte histogram, per-block byte sums
+ *    + thr_chipscan / thr_debug_chipscan_geometry / _budget / _times -- chip-rate scan: blocks x candidate
+ *      template lengths (the reference's scripts/chip_rate_search.py as an exhaustive scan) */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -746,6 +748,47 @@ int thr_survey_feed_stream(thr_survey* s, const uint8_t* stream, size_t n_bytes,
                            size_t* n_blocks, uint64_t* spec_sum, uint64_t* hist, size_t cap_intervals,
                            size_t* n_intervals);
 int thr_debug_survey_geometry(const thr_survey* s, int* tile_blocks, int* workgroups, int* fused);
+
+/*
+ * Chip-rate scan -- the objective of the reference's scripts/chip_rate_search.py, evaluated for every
+ * block of a batch against a bank of Gold-code templates of DIFFERENT lengths.  The reference's template
+ * depends on the chip rate through its length L = int(sps * n_chips) alone (template_generate.py: sample i
+ * is chip (i * n_chips) // L), so scanning integer lengths is exhaustive.  Per (block, length) the record
+ * is what SoaEstimator(template, thresh_coeffs=(0, 0, 0), block_len, history_len = L - 1) returns on the
+ * block's carrier-shifted spectrum: first maximum of |corr| over the lags [0, block_len - L], noise with
+ * template_energy = L, Gaussian offset clipped to +-0.6 (0 at the first and the last lag), detected =
+ * energy > 0.
+ *
+ * thr_chipscan rides on an ordinary handle (not a gate, preshift or THR_PATH_MULTIPASS one) with block_len
+ * 16384 -- every other block length is refused with THR_ERR_ARG: the scan kernels are the 16384-point ones.
+ * The handle's own template plays no part; carrier_len, carrier_thresh and carrier_window are the handle's
+ * (the carrier stage, the fit and the shift are the detect path's own kernels, and the shifted spectra
+ * never leave the device).  samples: n_blocks packed blocks in host memory, any number >= 1 (chunks of at
+ * most max_batch blocks inside).  chips: n_chips values 0 / 1 (1 -> +1, 0 -> -1), 1 <= n_chips <= 2047.
+ * lengths: n_lengths >= 1 values 1 <= L <= block_len - 2 in any order, repeats allowed; out is
+ * [n_blocks][n_lengths] in the order of the list.  A block without a carrier verdict has sample -1, flags 0
+ * and zeros in every record.  carrier_out (or NULL): [n_blocks] records with the carrier fields of
+ * thr_detect (block_idx = the block's index in the call, template_id 0, the correlation fields cleared).  Bad arguments -> THR_ERR_ARG before any
+ * device work; THR_ERR_STATE on a gate handle and while submitted batches are open.  Synchronous.
+ * thr_debug_chipscan_geometry: how a call with n_lengths candidates is cut -- candidates per chunk of the
+ * template bank (128 KiB each inside a fixed budget), and whether two lengths share one forward transform
+ * (0: they do not).  thr_debug_chipscan_budget: the bank budget in bytes (0: the default, 64 MiB; tests
+ * shrink it to meet the chunk seam with few candidates).  thr_debug_chipscan_times: device milliseconds
+ * of the last call -- [0] carrier stage, fit and shift, [1] bank kernel, [2] scan and finish kernels.
+ */
+typedef struct thr_chip_record {   /* out[block][candidate], 24 bytes */
+    int32_t sample;    /* CorrDetectionInfo.sample, -1: block had no carrier */
+    uint32_t flags;    /* THR_FLAG_CARRIER | THR_FLAG_CORR */
+    float energy, noise;
+    double offset;
+} thr_chip_record;
+int thr_chipscan(thr_handle* h, const void* samples, int format, size_t n_blocks,
+                 const uint8_t* chips, int n_chips,          /* 0/1 per chip */
+                 const int32_t* lengths, size_t n_lengths,   /* any order, repeats allowed */
+                 thr_chip_record* out, thr_record* carrier_out /* [n_blocks] or NULL */);
+int thr_debug_chipscan_geometry(thr_handle* h, size_t n_lengths, int* candidates_per_chunk, int* paired);
+int thr_debug_chipscan_budget(thr_handle* h, size_t bank_bytes);
+int thr_debug_chipscan_times(thr_handle* h, double* ms_out /* [3] */);
 
 /* The settings a handle was created with (`templates` is NULL: the array is not retained). */
 int thr_get_settings(const thr_handle* h, thr_settings* out);

@@ -46,6 +46,7 @@ EXPORTS = [
     "thr_debug_live_resources",
     "thr_survey_create", "thr_survey_destroy", "thr_survey_reset", "thr_survey_shift", "thr_survey_pending",
     "thr_survey_feed", "thr_survey_feed_stream", "thr_debug_survey_geometry",
+    "thr_chipscan", "thr_debug_chipscan_geometry", "thr_debug_chipscan_budget", "thr_debug_chipscan_times",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -128,6 +129,12 @@ RECORD_DTYPE = np.dtype([
     ("corr_energy", "<f4"), ("corr_noise", "<f4"), ("reserved", "<u8"),
 ])
 assert RECORD_DTYPE.itemsize == 64
+
+# numpy mirror of thr_chip_record (24 bytes)
+CHIP_RECORD_DTYPE = np.dtype([("sample", "<i4"), ("flags", "<u4"), ("energy", "<f4"), ("noise", "<f4"),
+                              ("offset", "<f8")])
+assert CHIP_RECORD_DTYPE.itemsize == 24
+CHIP_MAX_CHIPS = 2047       # kChipMaxChips of csrc/chipscan.hpp
 
 
 class ThrPostSettings(C.Structure):       # thr_post_settings
@@ -295,6 +302,10 @@ def load_library():
     lib.thr_survey_feed.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, szp]
     lib.thr_survey_feed_stream.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, szp, vp, vp, C.c_size_t, szp]
     lib.thr_debug_survey_geometry.argtypes = [vp, ip, ip, ip]
+    lib.thr_chipscan.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, vp, C.c_size_t, vp, vp]
+    lib.thr_debug_chipscan_geometry.argtypes = [vp, C.c_size_t, ip, ip]
+    lib.thr_debug_chipscan_budget.argtypes = [vp, C.c_size_t]
+    lib.thr_debug_chipscan_times.argtypes = [vp, C.POINTER(C.c_double)]
     _lib = lib
     return lib
 
@@ -1218,6 +1229,58 @@ class Survey(object):
                                                            hist.ctypes.data, cap, C.byref(got)))
         assert framed.value == nb
         return spec[:got.value], hist[:got.value], sums
+
+
+class ChipScan(object):
+    """The chip-rate scan riding on an Engine (thr_chipscan): blocks x candidate template lengths.  The
+    engine is an ordinary one with block_len 16384; its own template plays no part, its carrier settings
+    do.  It must stay open while this object is used; the scan's device buffers are the engine's."""
+
+    def __init__(self, engine):
+        self._lib, self._eng = engine._lib, engine
+
+    def close(self):
+        self._eng = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def scan(self, blocks, chips, lengths, with_carrier=False):
+        """blocks: u8 [B, 2N] or complex64 [B, N]; chips: 0 / 1 per chip; lengths: int32 [K] in any order
+        -> CHIP_RECORD_DTYPE records [B, K] in the order of `lengths` (and the blocks' carrier records,
+        RECORD_DTYPE [B], if with_carrier)."""
+        a, fmt = self._eng._as_input(blocks)
+        nb = a.shape[0]
+        c = np.ascontiguousarray(np.asarray(chips)).astype(np.uint8).reshape(-1)
+        lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int32)).reshape(-1)
+        out = np.zeros((nb, lens.size), dtype=CHIP_RECORD_DTYPE)
+        car = np.zeros(nb, dtype=RECORD_DTYPE) if with_carrier else None
+        _check(self._lib, self._lib.thr_chipscan(self._eng._h, a.ctypes.data if nb else None, fmt, nb,
+                                                 c.ctypes.data if c.size else None, c.size,
+                                                 lens.ctypes.data if lens.size else None, lens.size,
+                                                 out.ctypes.data if out.size else None,
+                                                 car.ctypes.data if with_carrier and nb else None))
+        return (out, car) if with_carrier else out
+
+    def geometry(self, n_lengths):
+        """thr_debug_chipscan_geometry -> (candidates per chunk of the template bank, lengths paired?)"""
+        per, paired = C.c_int(0), C.c_int(0)
+        _check(self._lib, self._lib.thr_debug_chipscan_geometry(self._eng._h, int(n_lengths), C.byref(per),
+                                                                C.byref(paired)))
+        return per.value, bool(paired.value)
+
+    def set_bank_budget(self, n_bytes):
+        """thr_debug_chipscan_budget: bytes of template bank per chunk (0: the default)"""
+        _check(self._lib, self._lib.thr_debug_chipscan_budget(self._eng._h, int(n_bytes)))
+
+    def times(self):
+        """thr_debug_chipscan_times -> device ms of the last scan: (carrier stage, bank kernel, scan kernels)"""
+        ms = (C.c_double * 3)()
+        _check(self._lib, self._lib.thr_debug_chipscan_times(self._eng._h, ms))
+        return tuple(ms)
 
 
 TDOA_TASKS_PER_WORKGROUP = 4    # kWaves of csrc/tdoa.hip: one wavefront per task, four to a workgroup

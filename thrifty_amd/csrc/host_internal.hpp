@@ -35,6 +35,7 @@
 #include "input_window.hpp"
 
 namespace thr {
+struct ChipStats;     // chipscan.hpp
 int fail_msg(int code, const char* fmt, ...);     // error text for thr_last_error(); returns `code`
 int on_exception(const char* who) noexcept;      // the catch (...) of every entry point
 namespace host {
@@ -164,6 +165,19 @@ struct thr_handle {
     double t_pipe[8] = {};
     double t_pipe_max[8] = {};   // the longest single occurrence of each phase
 
+    // thr_chipscan (chipscan.hip): allocated by the first call, grown by a larger one
+    struct ChipScan {
+        Dev<float2> d_xhat;             // [blocks per chunk][16384] carrier-shifted spectra, natural order
+        Dev<float4> d_bank;             // [candidates per chunk][8192] conj(FFT(template)) / N, k_chip_scan's order
+        Dev<thr::ChipStats> d_stats;    // [blocks per chunk][candidates per chunk]
+        Dev<thr_chip_record> d_out;     // [blocks per chunk][n_lengths]
+        Dev<thr_record> d_car;          // [blocks per chunk] carrier records (carrier_out)
+        Dev<int> d_len;                 // [n_lengths]
+        Dev<unsigned char> d_chips;     // [n_chips]
+        Event ev[6];                    // carrier stage, bank kernel, scan + finish: begin and end
+        size_t bank_budget = 0;         // thr_debug_chipscan_budget (0: thr::kChipBankBudget)
+        double ms[3] = {};              // the last call's device time per stage (thr_debug_chipscan_times)
+    } chip;
     // single-chunk staging of the test hooks (lazy)
     Dev<unsigned char> d_in;
     Dev<long long> d_idx;
