@@ -71,7 +71,10 @@ extern "C" {
  *    + thr_survey_create / _destroy / _reset / _shift / _pending / _feed / _feed_stream,
  *      thr_debug_survey_geometry -- capture survey: mean spectrum, byte histogram, per-block byte sums
  *    + thr_chipscan / thr_debug_chipscan_geometry / _budget / _times -- chip-rate scan: blocks x candidate
- *      template lengths (the reference's scripts/chip_rate_search.py as an exhaustive scan) */
+ *      template lengths (the reference's scripts/chip_rate_search.py as an exhaustive scan)
+ *    + thr_toadstats / thr_tstats_fetch / thr_tstats_free / thr_debug_toadstats_times / _geometry -- the
+ *      numbers of the reference's `thrifty analyze_toads` (toads_analysis.py): per (rxid, txid) statistics,
+ *      histograms and the per-receiver timestamp line */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -1118,6 +1121,65 @@ void thr_post_free(thr_post* result);
 /* Milliseconds of the calling thread's last thr_postdetect: {copies in, identify, match, tdoa, pos, copies
  * out} (HIP events); the last slot adds up the thr_post_fetch calls made since. */
 int thr_debug_post_times(double* ms_out /* [6] */);
+
+/* ---- detection statistics (the numbers of the reference's `thrifty analyze_toads`, toads_analysis.py).
+ * Input: the eleven columns of n detections and an optional selection `sel` (n_sel strictly ascending row
+ * indices; NULL: every row).  Timestamps are taken relative to time0, the selection's smallest one (one
+ * float64 subtraction).  A CELL is a distinct (rxid, txid) pair of the selection, cells ordered by rxid, then
+ * txid (signed); inside a cell the rows keep their input order.  Per cell, nine quantities in this order:
+ * carrier_energy, carrier_noise, 20 log10(carrier_energy / carrier_noise), carrier_bin, carrier_offset,
+ * energy, noise, 20 log10(energy / noise), offset -- mean, population std (two passes), min, max with IEEE
+ * semantics (a NaN makes all four NaN) -- and three integer histograms: detections per minute
+ * (floor(timestamp / 60), length = largest minute + 1), carrier bins (from the cell's smallest bin), and
+ * numpy.histogram(offset, 10) with its edges.  Per receiver (all selected rows of one rxid): the line
+ * timestamp ~ a * soa + b, fitted in u = (soa - mean) / max|soa - mean| on timestamp - mean, the residual
+ * a * soa + b - timestamp of every row, the residuals' population std and largest magnitude; a receiver with
+ * fewer than two distinct soa gets NaN.  A cell with a non-finite offset gets NaN edges, a zero histogram
+ * and THR_TSTATS_FLAG_OFFSET_NONFINITE.
+ *
+ * Errors (THR_ERR_ARG): a null pointer; an empty selection; a sel index out of range or not strictly
+ * ascending; a non-finite timestamp in the selection; timestamps that span more than 2^26 minutes -- all
+ * from a host pass before anything is launched; histograms that would together exceed 2^26 counters (known
+ * once the cells' extremes are, after the first reduction pass). */
+typedef struct thr_tstats_counts {
+    size_t rows, cells, receivers, minute_bins, carrier_bins, offset_bins;
+    double time0;
+} thr_tstats_counts;
+typedef struct thr_tstats thr_tstats;
+#define THR_TSTATS_FLAG_OFFSET_NONFINITE 1
+/* what thr_tstats_fetch copies, in terms of thr_tstats_counts */
+#define THR_TSTATS_CELL_RX 0        /* int32[cells] */
+#define THR_TSTATS_CELL_TX 1        /* int32[cells] */
+#define THR_TSTATS_CELL_PTR 2       /* int64[cells + 1] */
+#define THR_TSTATS_ORDER 3          /* int64[rows]: input indices grouped by cell, input order inside a cell */
+#define THR_TSTATS_STATS 4          /* float64[cells][9][4]: mean, std, min, max */
+#define THR_TSTATS_SNR_DB 5         /* float64[rows][2]: carrier dB, correlation dB, selection order */
+#define THR_TSTATS_MINUTE_PTR 6     /* int64[cells + 1] */
+#define THR_TSTATS_MINUTE_HIST 7    /* int64[minute_bins] */
+#define THR_TSTATS_BIN_FIRST 8      /* int32[cells]: the cell's smallest carrier bin */
+#define THR_TSTATS_BIN_PTR 9        /* int64[cells + 1] */
+#define THR_TSTATS_BIN_HIST 10      /* int64[carrier_bins] */
+#define THR_TSTATS_OFFSET_EDGES 11  /* float64[cells][11] */
+#define THR_TSTATS_OFFSET_HIST 12   /* int64[cells][10] */
+#define THR_TSTATS_CELL_FLAGS 13    /* int32[cells], THR_TSTATS_FLAG_* */
+#define THR_TSTATS_RX_ID 14         /* int32[receivers] */
+#define THR_TSTATS_RX_COUNT 15      /* int64[receivers] */
+#define THR_TSTATS_RX_FIT 16        /* float64[receivers][4]: a, b, residual std, max |residual| */
+#define THR_TSTATS_RESIDUAL 17      /* float64[rows], selection order */
+#define THR_TSTATS_N_OUTPUTS 18
+int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const int32_t* txid, const int32_t* carrier_bin,
+                  const double* timestamp, const double* soa, const double* carrier_offset,
+                  const double* carrier_energy, const double* carrier_noise, const double* energy,
+                  const double* noise, const double* offset, const int64_t* sel, size_t n_sel,
+                  thr_tstats** result_out, thr_tstats_counts* counts_out);
+/* Copies output `which` to dst; dst_bytes must be its exact size (THR_ERR_ARG otherwise). */
+int thr_tstats_fetch(thr_tstats* result, int which, void* dst, size_t dst_bytes);
+void thr_tstats_free(thr_tstats* result);
+/* Milliseconds of the calling thread's last thr_toadstats: {copies in, sort and cells, reductions and
+ * histograms, fit, copies out} (HIP events); the last slot adds up the thr_tstats_fetch calls made since. */
+int thr_debug_toadstats_times(double* ms_out /* [5] */);
+/* The tile length T (positions of the sorted order one workgroup reduces per loop trip) and the workgroup size. */
+int thr_debug_toadstats_geometry(int* tile_len, int* workgroup);
 
 #ifdef __cplusplus
 }

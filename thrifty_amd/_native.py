@@ -47,6 +47,7 @@ EXPORTS = [
     "thr_survey_create", "thr_survey_destroy", "thr_survey_reset", "thr_survey_shift", "thr_survey_pending",
     "thr_survey_feed", "thr_survey_feed_stream", "thr_debug_survey_geometry",
     "thr_chipscan", "thr_debug_chipscan_geometry", "thr_debug_chipscan_budget", "thr_debug_chipscan_times",
+    "thr_toadstats", "thr_tstats_fetch", "thr_tstats_free", "thr_debug_toadstats_times", "thr_debug_toadstats_geometry",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -150,6 +151,13 @@ POST_COUNTS = ("kept", "matches", "match_entries", "misses", "collisions", "task
 
 class ThrPostCounts(C.Structure):         # thr_post_counts
     _fields_ = [(name, C.c_size_t) for name in POST_COUNTS]
+
+
+TSTATS_COUNTS = ("rows", "cells", "receivers", "minute_bins", "carrier_bins", "offset_bins")
+
+
+class ThrTstatsCounts(C.Structure):       # thr_tstats_counts
+    _fields_ = [(name, C.c_size_t) for name in TSTATS_COUNTS] + [("time0", C.c_double)]
 
 
 class NativeError(RuntimeError):
@@ -306,6 +314,13 @@ def load_library():
     lib.thr_debug_chipscan_geometry.argtypes = [vp, C.c_size_t, ip, ip]
     lib.thr_debug_chipscan_budget.argtypes = [vp, C.c_size_t]
     lib.thr_debug_chipscan_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.thr_toadstats.argtypes = ([C.c_int, C.c_size_t] + [vp] * 11 +
+                                  [vp, C.c_size_t, C.POINTER(vp), C.POINTER(ThrTstatsCounts)])
+    lib.thr_tstats_fetch.argtypes = [vp, C.c_int, vp, C.c_size_t]
+    lib.thr_tstats_free.argtypes = [vp]
+    lib.thr_tstats_free.restype = None
+    lib.thr_debug_toadstats_times.argtypes = [C.POINTER(C.c_double)]
+    lib.thr_debug_toadstats_geometry.argtypes = [ip, ip]
     _lib = lib
     return lib
 
@@ -1479,3 +1494,85 @@ def live_resources():
     out = (C.c_int64 * 4)()
     _check(lib, lib.thr_debug_live_resources(out))
     return tuple(int(v) for v in out)
+
+
+# the eleven detection columns of thr_toadstats, in its argument order
+TSTATS_COLUMNS = (("rxid", np.int32), ("txid", np.int32), ("carrier_bin", np.int32), ("timestamp", np.float64),
+                  ("soa", np.float64), ("carrier_offset", np.float64), ("carrier_energy", np.float64),
+                  ("carrier_noise", np.float64), ("energy", np.float64), ("noise", np.float64), ("offset", np.float64))
+# the nine quantities of a cell, in the order of STATS' second axis
+TSTATS_QUANTITIES = ("carrier_energy", "carrier_noise", "carrier_snr_db", "carrier_bin", "carrier_offset", "energy",
+                     "noise", "snr_db", "offset")
+TSTATS_FLAG_OFFSET_NONFINITE = 1        # THR_TSTATS_FLAG_OFFSET_NONFINITE
+# THR_TSTATS_*: name -> (index, dtype, shape as a function of the counts)
+TSTATS_OUTPUTS = {
+    "cell_rx": (0, np.int32, lambda c: (c["cells"],)),
+    "cell_tx": (1, np.int32, lambda c: (c["cells"],)),
+    "cell_ptr": (2, np.int64, lambda c: (c["cells"] + 1,)),
+    "order": (3, np.int64, lambda c: (c["rows"],)),
+    "stats": (4, np.float64, lambda c: (c["cells"], 9, 4)),
+    "snr_db": (5, np.float64, lambda c: (c["rows"], 2)),
+    "minute_ptr": (6, np.int64, lambda c: (c["cells"] + 1,)),
+    "minute_hist": (7, np.int64, lambda c: (c["minute_bins"],)),
+    "bin_first": (8, np.int32, lambda c: (c["cells"],)),
+    "bin_ptr": (9, np.int64, lambda c: (c["cells"] + 1,)),
+    "bin_hist": (10, np.int64, lambda c: (c["carrier_bins"],)),
+    "offset_edges": (11, np.float64, lambda c: (c["cells"], 11)),
+    "offset_hist": (12, np.int64, lambda c: (c["cells"], 10)),
+    "cell_flags": (13, np.int32, lambda c: (c["cells"],)),
+    "rx_id": (14, np.int32, lambda c: (c["receivers"],)),
+    "rx_count": (15, np.int64, lambda c: (c["receivers"],)),
+    "rx_fit": (16, np.float64, lambda c: (c["receivers"], 4)),
+    "residual": (17, np.float64, lambda c: (c["rows"],)),
+}
+
+
+def toadstats(columns, sel=None, outputs=None, device_id=0):
+    """thr_toadstats on the eleven detection columns (a mapping with the names of TSTATS_COLUMNS) and an
+    optional selection of row indices -> (counts dict with time0, {name: array}) with every output of
+    TSTATS_OUTPUTS (or those named in `outputs`) fetched.  ValueError for what thr_toadstats refuses."""
+    lib = load_library()
+    cols = [np.ascontiguousarray(columns[name], dtype=kind) for name, kind in TSTATS_COLUMNS]
+    n = len(cols[0])
+    if any(col.ndim != 1 or len(col) != n for col in cols):
+        raise ValueError("toadstats: the detection columns differ in length")
+    if sel is not None:
+        sel = np.ascontiguousarray(sel, dtype=np.int64)
+        if sel.ndim != 1:
+            raise ValueError("toadstats: sel must be one-dimensional")
+    keep = np.zeros(1, dtype=np.int64)      # a selection of no rows still needs a pointer that is not NULL
+    sel_ptr = None if sel is None else (sel.ctypes.data if len(sel) else keep.ctypes.data)
+    handle, counts = C.c_void_p(), ThrTstatsCounts()
+    rc = lib.thr_toadstats(int(device_id), n, *[col.ctypes.data if n else None for col in cols], sel_ptr,
+                           0 if sel is None else len(sel), C.byref(handle), C.byref(counts))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    try:
+        c = {name: int(getattr(counts, name)) for name in TSTATS_COUNTS}
+        out = {}
+        for name in (TSTATS_OUTPUTS if outputs is None else outputs):
+            which, kind, shape = TSTATS_OUTPUTS[name]
+            out[name] = np.zeros(shape(c), dtype=kind)
+            _check(lib, lib.thr_tstats_fetch(handle, which, out[name].ctypes.data, out[name].nbytes))
+        c["time0"] = float(counts.time0)
+    finally:
+        lib.thr_tstats_free(handle)
+    return c, out
+
+
+def toadstats_times():
+    """{copies in, sort and cells, reductions and histograms, fit, copies out} of this thread's last toadstats(),
+    milliseconds (HIP events)."""
+    lib = load_library()
+    ms = (C.c_double * 5)()
+    _check(lib, lib.thr_debug_toadstats_times(ms))
+    return tuple(ms)
+
+
+def toadstats_geometry():
+    """thr_debug_toadstats_geometry -> (tile length T, workgroup size W)."""
+    lib = load_library()
+    t, w = C.c_int(), C.c_int()
+    _check(lib, lib.thr_debug_toadstats_geometry(C.byref(t), C.byref(w)))
+    return t.value, w.value
