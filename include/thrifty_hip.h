@@ -74,7 +74,9 @@ extern "C" {
  *      template lengths (the reference's scripts/chip_rate_search.py as an exhaustive scan)
  *    + thr_toadstats / thr_tstats_fetch / thr_tstats_free / thr_debug_toadstats_times / _geometry -- the
  *      numbers of the reference's `thrifty analyze_toads` (toads_analysis.py): per (rxid, txid) statistics,
- *      histograms and the per-receiver timestamp line */
+ *      histograms and the per-receiver timestamp line
+ *    + thr_debug_section_counts -- sections the one-template section kernel searched / left out by their
+ *      energy bound (records unchanged) */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -873,6 +875,11 @@ int thr_get_path_info(thr_handle* h, thr_path_info* out);
  *   *n_sections (0: unsectioned) of *section_len samples (16384 for long blocks, 4096 for block_len
  *   16384). */
 int thr_debug_sections(thr_handle* h, int* n_sections, int* section_len);
+/* thr_debug_section_counts: the (block, section) items the one-template 4096-sample section kernel has
+ *   searched (*computed) and has left out because their energy bound ruled the peak out (*skipped) since
+ *   the last call; waits for the handle's stream, reads the two counters and zeroes them (32 bits each:
+ *   read them before 2^32 items).  Both stay 0 for every other correlate kernel. */
+int thr_debug_section_counts(thr_handle* h, long long* computed, long long* skipped);
 /* thr_debug_window: the input window's state, in bytes from its (page-aligned) start:
  *   out[0] = everything below this offset has been released by the chunk copies (may be unlocked),
  *   out[1], out[2] = the range that is page-locked now, out[3] = the segment size (0: no window). */

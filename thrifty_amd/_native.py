@@ -33,7 +33,7 @@ EXPORTS = [
     "thr_debug_stage", "thr_debug_stage_offsets", "thr_identify", "thr_frame_card",
     "thr_submit", "thr_submit_card", "thr_submit_stream", "thr_collect", "thr_inputs_consumed", "thr_poll",
     "thr_set_stream_default", "thr_format_toad",
-    "thr_run_card", "thr_run_stream", "thr_get_settings", "thr_input_window_ex", "thr_input_window_release", "thr_detect_offsets", "thr_set_wait_mode", "thr_debug_window", "thr_debug_window_times", "thr_debug_correlate_geom", "thr_debug_sections", "thr_debug_pipe_times", "thr_get_path_info",
+    "thr_run_card", "thr_run_stream", "thr_get_settings", "thr_input_window_ex", "thr_input_window_release", "thr_detect_offsets", "thr_set_wait_mode", "thr_debug_window", "thr_debug_window_times", "thr_debug_correlate_geom", "thr_debug_sections", "thr_debug_section_counts", "thr_debug_pipe_times", "thr_get_path_info",
     "thr_gate", "thr_gate_stream", "thr_gate_card", "thr_gate_slot_stride", "thr_format_card",
     "thr_run_gate_stream", "thr_run_gate_card",
     "thr_extract_create", "thr_extract_destroy", "thr_extract_reset", "thr_extract_feed", "thr_extract_feed_card",
@@ -948,6 +948,14 @@ class Engine(object):
         self._lib.thr_debug_sections.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         _check(self._lib, self._lib.thr_debug_sections(self._h, C.byref(n), C.byref(ln)))
         return n.value, ln.value
+
+    def section_counts(self):
+        """thr_debug_section_counts -> (computed, skipped): the (block, section) items the one-template
+        section kernel has searched / left out by its energy bound since the last call (reads and zeroes)."""
+        done, skipped = C.c_longlong(0), C.c_longlong(0)
+        self._lib.thr_debug_section_counts.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        _check(self._lib, self._lib.thr_debug_section_counts(self._h, C.byref(done), C.byref(skipped)))
+        return done.value, skipped.value
 
     def debug_pipe_times(self):
         """thr_debug_pipe_times -> seconds per phase of the host entry points' chunks (reads and resets)."""

@@ -71,8 +71,10 @@ constexpr int QR = 4;             // radix of the first forward / last inverse p
 constexpr int QA = 8;             // adjacent columns per thread in those passes
 constexpr int QT = 128;           // threads per workgroup: two waves
 constexpr int QDATA = QR * ROW;   // LDS image, complex
-// scratch behind the image (bytes): [0, 128) reductions (2 parities x 2 waves x 32 B), [128, 132) the
-// dynamic work cursor, [192, 192 + 98 x 8) the next item's shift-phasor factors and pass-1 twiddle steps
+// scratch behind the image (bytes): [0, 128) reductions (2 parities x 2 waves x 32 B; of a wave's 32 B the
+// first 8 hold its energy sums of the NEXT item, k_correlate_4k's skip rule), [128, 136) the dynamic work
+// cursor (one slot per parity), [192, 192 + 98 x 8) the next item's shift-phasor factors and pass-1
+// twiddle steps
 constexpr int Q_DYN = 128, Q_PH = 192, Q_NPH = 98;
 constexpr size_t QLDS = size_t(QDATA) * sizeof(cpx) + 1024;   // 35 840 B: four workgroups per CU
 #ifndef THR_Q_MULTI_FORM
@@ -85,6 +87,20 @@ constexpr int Q_MULTI_FORM = THR_Q_MULTI_FORM;   // several templates: 1 spectru
 // m = 8 t .. 8 t + 7 (n = n1 * 1024 + m)
 template <int FMT>
 struct RawQ;
+
+// integer wave sum on the DPP path (kernel_util.hpp's wave_sum, for unsigned)
+__device__ __forceinline__ unsigned q_wave_sum_u32(unsigned v) {
+    v += dpp_u32<DPP_ROW_SHR1, 0xf>(0u, v);
+    v += dpp_u32<DPP_ROW_SHR2, 0xf>(0u, v);
+    v += dpp_u32<DPP_ROW_SHR4, 0xf>(0u, v);
+    v += dpp_u32<DPP_ROW_SHR8, 0xf>(0u, v);
+    v += dpp_u32<DPP_ROW_BCAST15, 0xa>(0u, v);
+    v += dpp_u32<DPP_ROW_BCAST31, 0xc>(0u, v);
+    return unsigned(__builtin_amdgcn_readlane(int(v), 63));
+}
+
+// Energy of a section, sum |x|^2 over its 4096 samples, for the skip rule: every wave forms its half
+// as one 64-bit word (wave_esum, uniform in the wave), energy() adds the two halves.
 
 template <>
 struct RawQ<THR_IN_U8> {
@@ -102,6 +118,23 @@ struct RawQ<THR_IN_U8> {
         a = __builtin_elementwise_fma(cpx{float(w & 0xffu), float((w >> 8) & 0xffu)}, cpx{sc, sc}, cpx{of, of});
         b = __builtin_elementwise_fma(cpx{float((w >> 16) & 0xffu), float(w >> 24)}, cpx{sc, sc}, cpx{of, of});
     }
+    // EXACT: sum u^2 (a wave's 4096 bytes: <= 266,342,400) in the low word, sum u in the high one
+    __device__ __forceinline__ unsigned long long wave_esum() const {
+        unsigned s2 = 0, s1 = 0;
+#pragma unroll
+        for (int i = 0; i < QR * QA / 2; ++i) {
+            s2 = __builtin_amdgcn_udot4(q[i], q[i], s2, false);
+            s1 = __builtin_amdgcn_udot4(q[i], 0x01010101u, s1, false);
+        }
+        return ((unsigned long long)q_wave_sum_u32(s1) << 32) | q_wave_sum_u32(s2);
+    }
+    // sum ((u - c) / 128)^2 over the section's 8192 bytes, c = 127.4f
+    static __device__ __forceinline__ double energy(unsigned long long a, unsigned long long b) {
+        constexpr double c = double(127.4f);
+        const double s2 = double(unsigned(a)) + double(unsigned(b));
+        const double s1 = double(unsigned(a >> 32)) + double(unsigned(b >> 32));
+        return (s2 - 2.0 * c * s1 + 2.0 * QN * c * c) * (1.0 / 16384.0);
+    }
 };
 
 template <>
@@ -114,6 +147,24 @@ struct RawQ<THR_IN_C64> {
         const f4 w = p[n1 * 512 + i];
         a = cpx{w.x, w.y};
         b = cpx{w.z, w.w};
+    }
+    // fp32 sums of re^2 + im^2 (the samples are read here a second time: they are not held in registers);
+    // the rounding of 4096 terms, < 1e-5 relative, is far inside the skip rule's margin
+    __device__ __forceinline__ unsigned long long wave_esum() const {
+        float s = 0.f;
+#pragma unroll
+        for (int n1 = 0; n1 < QR; ++n1) {
+            f4 w[QA / 2];
+#pragma unroll
+            for (int i = 0; i < QA / 2; ++i) w[i] = p[n1 * 512 + i];
+#pragma unroll
+            for (int i = 0; i < QA / 2; ++i)
+                s = fmaf(w[i].x, w[i].x, fmaf(w[i].y, w[i].y, fmaf(w[i].z, w[i].z, fmaf(w[i].w, w[i].w, s))));
+        }
+        return __float_as_uint(wave_sum(s));
+    }
+    static __device__ __forceinline__ double energy(unsigned long long a, unsigned long long b) {
+        return double(__uint_as_float(unsigned(a))) + double(__uint_as_float(unsigned(b)));
     }
 };
 
@@ -487,6 +538,22 @@ __global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(2))) void k_
     auto last_of_ticket = [&](int wi) -> bool {
         return tk == 1 ? true : tk == 4 ? ((wi + 1) & 3) == 0 : (wi + 1) % tk == 0;
     };
+    // SKIP RULE (one template, not the cross-check form).  By Cauchy-Schwarz no lag of a section exceeds
+    // |corr[l]|^2 <= (sum over the section's 4096 samples of |x|^2) * sum t^2 (the shift phasor has unit
+    // modulus; the 1 / 4096 sits in tspec, so pm2 is the reference's |corr|^2, the scale of tmpl_energy).
+    // A section whose bound, widened by 2^-7 -- far above the transform's fp32 error of about 1e-5 relative
+    // to |x| |t| --, lies below the largest pm2 of the sections of the same ticket searched before it cannot
+    // win k_finish's merge, nor tie it, and adds nothing else to the record: it is not transformed.  The
+    // energy comes from the raw samples of the NEXT item, which every iteration holds anyway, and crosses
+    // the workgroup through the reduction scratch one item ahead.  A ticket's first section is always
+    // searched; with tk == 1 a block's sections sit on different workgroups and nothing is skipped.
+    constexpr bool SKIP = MULTI == 0 && !GENERIC_ROWS;
+    auto first_of_ticket = [&](int wi) -> bool {
+        return tk == 1 ? true : tk == 4 ? (wi & 3) == 0 : wi % tk == 0;
+    };
+    const double skip_scale = (1.0 + 1.0 / 128.0) * double(cfg.tmpl_energy[0]);
+    float blk_best = 0.f;             // largest pm2 of the ticket's sections searched so far
+    int n_done = 0, n_skipped = 0;    // this workgroup's items (one template): work_count[2], [3] at exit
     bool static_ticket = true;   // ticket g + G not handed out yet
     int wi0 = int(blockIdx.x) * tk, wi_nxt;
     if (!last_of_ticket(wi0)) {
@@ -529,6 +596,18 @@ __global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(2))) void k_
         const int b = item >> 3, seg = item & 7;
         const int t = opaque_tid();
         const ShiftParams* sp = shifts + b;
+        unsigned long long* const sc_en = reinterpret_cast<unsigned long long*>(sc_red + parity * red_slot_bytes<QT / 64>());
+        bool skip = false;
+        if constexpr (SKIP) {
+            if (first_of_ticket(wi)) {
+                blk_best = 0.f;
+            } else {   // this item's energy: left in the other parity's slots by the iteration before
+                const unsigned long long* en =
+                    reinterpret_cast<const unsigned long long*>(sc_red + (parity ^ 1) * red_slot_bytes<QT / 64>());
+                const double e = RawQ<FMT>::energy(en[0], en[4]);
+                skip = __builtin_amdgcn_readfirstlane(int(skip_scale * e < double(blk_best))) != 0;
+            }
+        }
         // (the cursor's value is first touched behind pass 1: nothing waits for the atomic's round trip)
         const bool need_ticket = last_of_ticket(wi_nxt);
         int wi_dyn = 0;
@@ -547,7 +626,7 @@ __global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(2))) void k_
         // (unconditional: past the last item it re-fetches the current one's and nothing is stored)
         const QPhasor ph = q_phasor_fetch(shifts + (it_next >> 3), it_next & 7, twn, t);
         THR_STAMP(1);
-        {
+        if (!skip) {
             cpx qk[QR];
             qk[0] = cmul(sc_ph[64 + (t >> 6)], sc_ph[t & 63]);
 #pragma unroll
@@ -556,14 +635,24 @@ __global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(2))) void k_
         }
         cur = nxt;
         THR_STAMP(2);
+        // a skipped item has this one barrier: the next item's energy and phasor factors go in front of it
+        // (sc_dyn takes a slot per parity for the same reason: the next iteration's cursor may be written
+        // while a slow wave still reads this one's)
+        if constexpr (SKIP) {
+            if (skip) {
+                const unsigned long long es = cur.wave_esum();
+                if ((t & 63) == 0) sc_en[(t >> 6) * 4] = es;
+                if (more) q_phasor_store(ph, t, sc_ph);
+            }
+        }
         if (t == 0)
-            *sc_dyn = !need_ticket ? wi_nxt + 1
-                                   : (static_ticket ? int(blockIdx.x) + G : 2 * G + wi_dyn) * tk;
+            sc_dyn[parity] = !need_ticket ? wi_nxt + 1
+                                          : (static_ticket ? int(blockIdx.x) + G : 2 * G + wi_dyn) * tk;
         if (need_ticket) static_ticket = false;
         THR_STAMP(3);
         __syncthreads();
         THR_STAMP(4);
-        const int wi_nxt2 = __builtin_amdgcn_readfirstlane(*sc_dyn);
+        const int wi_nxt2 = __builtin_amdgcn_readfirstlane(sc_dyn[parity]);
         if (wi_nxt2 < n_work) {
             const int e = item_entry(wi_nxt2);
             blk_next2 = work_list[e];
@@ -573,6 +662,23 @@ __global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(2))) void k_
         wi_nxt = wi_nxt2;
         // the next item's phasor factors: this item's were read before the barrier above, the new
         // ones are read after the two barriers that follow
+        if constexpr (SKIP) {
+            if (skip) {   // nothing of the section is transformed: k_finish ignores pk < 0
+                if (t == 0) {
+                    CorrStats* cs = seg_stats + size_t(b) * cfg.n_templates * n_seg + seg;
+                    cs->pm2 = 0.f;
+                    cs->m2[0] = 0.f;
+                    cs->m2[1] = 0.f;
+                    cs->m2[2] = 0.f;
+                    cs->sum_mag = 0.f;
+                    cs->sum_mag2 = 0.f;
+                    cs->pk = -1;
+                }
+                ++n_skipped;
+                parity ^= 1;
+                continue;
+            }
+        }
         if (more) q_phasor_store(ph, t, sc_ph);
         if constexpr (MULTI == 0) request_tq(0);   // here: two passes ahead of the product
         // rows 2w, 2w + 1 belong to wave w through passes 2, 3, A and B: no barriers
@@ -617,6 +723,14 @@ __global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(2))) void k_
         THR_STAMP(8);
         __syncthreads();
         THR_STAMP(9);
+        // the next item's energy, from the raw samples requested at the top (they have had five passes to
+        // arrive): read at the top of the next iteration, behind the reduction's barrier below
+        if constexpr (SKIP) {
+            if (tk != 1) {
+                const unsigned long long es = cur.wave_esum();
+                if ((t & 63) == 0) sc_en[(t >> 6) * 4] = es;
+            }
+        }
         cpx c[QR * QA];
         q_passC(lds, opaque_tid(), c);
         THR_STAMP(10);
@@ -730,6 +844,8 @@ __global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(2))) void k_
             cs->sum_mag = 0.f;
             cs->sum_mag2 = 0.f;
         }
+        if constexpr (SKIP)
+            blk_best = __builtin_fmaxf(blk_best, __uint_as_float(__builtin_amdgcn_readfirstlane(unsigned(best >> 32))));
         THR_STAMP(13);
         if (++tpl >= n_tpl) break;
         if constexpr (MULTI == 2) {   // X^ conj(T^) / 4096 of the next template
@@ -753,6 +869,13 @@ __global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(2))) void k_
             });
         }
       }   // templates
+        ++n_done;
+    }
+    if constexpr (MULTI == 0) {
+        if (threadIdx.x == 0 && n_done + n_skipped != 0) {
+            atomicAdd(const_cast<int*>(work_count) + 2, n_done);
+            atomicAdd(const_cast<int*>(work_count) + 3, n_skipped);
+        }
     }
 }
 

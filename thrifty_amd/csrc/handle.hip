@@ -441,6 +441,21 @@ int thr_debug_sections(thr_handle* h, int* n_sections, int* section_len) try {
     return thr::on_exception("thr_debug_sections");
 }
 
+int thr_debug_section_counts(thr_handle* h, long long* computed, long long* skipped) try {
+    if (!h || !computed || !skipped) return fail(THR_ERR_ARG, "thr_debug_section_counts: null argument");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    unsigned n[2] = {0u, 0u};   // d_work_count[2], [3]: k_correlate_4k adds to them, nothing else re-arms them
+    HIP_TRY(hipMemcpyAsync(n, h->d_work_count.p + 2, sizeof n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_work_count.p + 2, 0, sizeof n, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *computed = (long long)n[0];
+    *skipped = (long long)n[1];
+    return THR_OK;
+} catch (...) {
+    return thr::on_exception("thr_debug_section_counts");
+}
+
 int thr_get_path_info(thr_handle* h, thr_path_info* out) try {
     if (!h || !out) return fail(THR_ERR_ARG, "thr_get_path_info: null argument");
     std::memset(out, 0, sizeof(*out));
@@ -764,7 +779,7 @@ static int create_body(const thr_settings* s, int preshift_num, thr_handle** out
     if (h->sec4k)
         HIP_TRY(h->d_seg_stats.alloc(mb * s->n_templates * size_t(d.n_seg) * sizeof(thr::CorrStats)));
     HIP_TRY(h->d_work_list.alloc(mb * sizeof(int)));
-    HIP_TRY(h->d_work_count.alloc(4 * sizeof(int)));  // [0] work count, [1] dynamic cursor
+    HIP_TRY(h->d_work_count.alloc(4 * sizeof(int)));  // [0] work count, [1] dynamic cursor, [2] / [3] sections searched / skipped
     HIP_TRY(hipMemset(h->d_work_count, 0, 4 * sizeof(int)));  // re-armed by k_finish
     HIP_TRY(h->d_ncompact.alloc(sizeof(int)));
     *out = h.release();
