@@ -76,7 +76,10 @@ extern "C" {
  *      numbers of the reference's `thrifty analyze_toads` (toads_analysis.py): per (rxid, txid) statistics,
  *      histograms and the per-receiver timestamp line
  *    + thr_debug_section_counts -- sections the one-template section kernel searched / left out by their
- *      energy bound (records unchanged) */
+ *      energy bound (records unchanged)
+ *    + thr_beaconsync / thr_bsync_fetch / thr_bsync_free and thr_tdoastats / thr_tdstats_fetch /
+ *      thr_tdstats_free, with thr_debug_{beaconsync,tdoastats}_{times,geometry} -- the numbers of the
+ *      reference's `thrifty analyze_beacon` and `thrifty analyze_tdoa`, for every cell in one call */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -1187,6 +1190,102 @@ void thr_tstats_free(thr_tstats* result);
 int thr_debug_toadstats_times(double* ms_out /* [5] */);
 /* The tile length T (positions of the sorted order one workgroup reduces per loop trip) and the workgroup size. */
 int thr_debug_toadstats_geometry(int* tile_len, int* workgroup);
+
+/* ---- clock-sync quality (the numbers of the reference's `thrifty analyze_beacon`, beacon_analysis.py:62-136)
+ * for every cell at once.  Input: the detection columns rxid, txid, soa, energy, noise and the detection id
+ * idx; the matches as CSR (what thr_match returns); deg in 1..3; an optional closed detection-id range
+ * id_range[2] (a row is kept when both of its detections' ids lie inside); optional lists of beacon txids and
+ * of receiver ids (NULL: every one that occurs).  A match belongs to the transmitter of its FIRST detection.
+ * A CELL is (beacon, rx0 < rx1); its rows are the matches of the beacon that hold both receivers, in match
+ * order, as (detection at rx0, detection at rx1); cells are ordered by (beacon, rx0, rx1), signed.
+ * Per cell: sdoa = soa1 - soa0, dsdoa = diff(sdoa), mean = sum(dsdoa) / count (one division); row k is a
+ * discontinuity when dsdoa[k] > mean * 10 (strict, sign-sensitive, never for a NaN).  With edges = [0, d1, ...,
+ * n], cut i is rows [edges[i] + 1, edges[i + 1]); every cell has discontinuities + 1 cuts; a cut with
+ * left + 8 >= right is not fitted.  Per fitted cut: the least-squares polynomial of degree deg of soa1 on
+ * soa0 as {x_mean, x_scale, y_mean, c0..c3}: soa1 ~ y_mean + sum c_k u^k with u = (soa0 - x_mean) / x_scale
+ * (x_scale = max|soa0 - x_mean|; c_k = 0 above deg); the residual soa1 - fit(soa0) of its rows (NaN for rows
+ * of no fitted cut); snr = mean(energy^2 / noise^2) over both detections of its rows; disc_soa = soa0 of row
+ * `right` when right != n.  Everything of a cut that is not fitted is NaN.  A cut that is long enough but
+ * cannot be fitted (all soa0 equal, a NaN) has THR_BSYNC_CUT_DEGENERATE.  Per cell: the population std of all
+ * residuals, the largest magnitude, the mean of the fitted cuts' snr; NaN and THR_BSYNC_CELL_NO_FIT without a
+ * fitted cut.  A repeated call returns the same bits.
+ *
+ * Errors (THR_ERR_ARG), all before anything is launched unless noted: a null pointer; deg outside 1..3; a
+ * CSR that is not one; a match with two detections of one receiver; an inverted id range; more than 2^28
+ * detections, matches or detection pairs, a list of more than 2^20 ids; no match at all, or (known after the
+ * first kernel) no row left by the lists and the range. */
+typedef struct thr_bsync_counts {
+    size_t rows, cells, discontinuities, cuts;
+} thr_bsync_counts;
+typedef struct thr_bsync thr_bsync;
+#define THR_BSYNC_CUT_FITTED 1
+#define THR_BSYNC_CUT_DEGENERATE 2
+#define THR_BSYNC_CELL_NO_FIT 1
+/* what thr_bsync_fetch copies, in terms of thr_bsync_counts */
+#define THR_BSYNC_CELL_KEY 0        /* int32[cells][3]: beacon, rx0, rx1 */
+#define THR_BSYNC_CELL_PTR 1        /* int64[cells + 1] into the rows */
+#define THR_BSYNC_ROW_DET 2         /* int64[rows][2]: detection at rx0, at rx1 (positions in the columns) */
+#define THR_BSYNC_ROW_MATCH 3       /* int64[rows]: the match the row came from */
+#define THR_BSYNC_SDOA 4            /* float64[rows] */
+#define THR_BSYNC_DISC_PTR 5        /* int64[cells + 1] */
+#define THR_BSYNC_DISC_IDX 6        /* int64[discontinuities]: row index inside the cell */
+#define THR_BSYNC_CUT_PTR 7         /* int64[cells + 1] */
+#define THR_BSYNC_CUT_LEFT 8        /* int64[cuts] */
+#define THR_BSYNC_CUT_RIGHT 9       /* int64[cuts] */
+#define THR_BSYNC_CUT_FLAGS 10      /* int32[cuts]: 0 too short, THR_BSYNC_CUT_* */
+#define THR_BSYNC_CUT_FIT 11        /* float64[cuts][7]: x_mean, x_scale, y_mean, c0, c1, c2, c3 */
+#define THR_BSYNC_CUT_SNR 12        /* float64[cuts] */
+#define THR_BSYNC_CUT_DISC_SOA 13   /* float64[cuts] */
+#define THR_BSYNC_RESIDUAL 14       /* float64[rows] */
+#define THR_BSYNC_CELL_COUNTS 15    /* int64[cells][3]: rows, discontinuities, fitted cuts */
+#define THR_BSYNC_CELL_STATS 16     /* float64[cells][4]: mean dsdoa, residual std, max |residual|, mean snr */
+#define THR_BSYNC_CELL_FLAGS 17     /* int32[cells], THR_BSYNC_CELL_* */
+#define THR_BSYNC_N_OUTPUTS 18
+int thr_beaconsync(int device_id, size_t n_det, const int32_t* rxid, const int32_t* txid, const double* soa,
+                   const double* energy, const double* noise, const int64_t* idx, size_t n_matches,
+                   const int64_t* match_ptr, const int64_t* match_idx, int deg, const int64_t* id_range /* [2] or NULL */,
+                   const int32_t* beacons, size_t n_beacons, const int32_t* receivers, size_t n_receivers,
+                   thr_bsync** result_out, thr_bsync_counts* counts_out);
+/* Copies output `which` to dst; dst_bytes must be its exact size (THR_ERR_ARG otherwise). */
+int thr_bsync_fetch(thr_bsync* result, int which, void* dst, size_t dst_bytes);
+void thr_bsync_free(thr_bsync* result);
+/* Milliseconds of the calling thread's last thr_beaconsync: {copies in, rows and cells, discontinuities and
+ * cuts, fits and summary, copies out} (HIP events); the last slot adds up the fetches made since. */
+int thr_debug_beaconsync_times(double* ms_out /* [5] */);
+/* The tile length T (positions one workgroup reduces per loop trip) and the workgroup size. */
+int thr_debug_beaconsync_geometry(int* tile_len, int* workgroup);
+
+/* ---- TDOA quality (the reference's `thrifty analyze_tdoa`, tdoa_analysis.py) for every cell at once.
+ * Input: the columns of a .tdoa matrix; optional closed ranges ts_range[2] on the timestamp and det_range[2]
+ * on the detection ids (both ids must lie inside).  A CELL is (rx0, rx1, tx) as stored, cells ordered by that
+ * key (signed), rows in input order inside a cell.  Per cell on x = tdoa * 2.997e8: mean, population std (two
+ * passes), RMS = sqrt(mean(x^2)), min, max (a NaN makes them NaN).  With `robust`, the same again over the
+ * rows that stat_tools.is_outlier(x) keeps (applied to cells of more than one row): median = mean of the two
+ * middle values, dev = sqrt((x - median)^2), MAD = median(dev), mask = 0.6745 * dev / MAD > 3.5 in float64,
+ * operation for operation (MAD = 0 gives numpy's inf / NaN pattern: a NaN keeps the row).
+ * Errors (THR_ERR_ARG): a null pointer, an inverted range, more than 2^28 rows, an empty selection. */
+typedef struct thr_tdstats_counts {
+    size_t rows, cells, robust;
+} thr_tdstats_counts;
+typedef struct thr_tdstats thr_tdstats;
+#define THR_TDSTATS_CELL_KEY 0      /* int32[cells][3]: rx0, rx1, tx */
+#define THR_TDSTATS_CELL_PTR 1      /* int64[cells + 1] */
+#define THR_TDSTATS_ORDER 2         /* int64[rows]: input rows grouped by cell, input order inside a cell */
+#define THR_TDSTATS_STATS 3         /* float64[cells][5]: mean, std, rms, min, max (metres) */
+#define THR_TDSTATS_ROBUST_STATS 4  /* float64[cells][5], empty without `robust` (and so the next three) */
+#define THR_TDSTATS_ROBUST_COUNT 5  /* int64[cells]: rows the mask keeps */
+#define THR_TDSTATS_MASK 6          /* uint8[rows] in the order of ORDER: 1 = outlier */
+#define THR_TDSTATS_MEDIAN 7        /* float64[cells][2]: median, MAD */
+#define THR_TDSTATS_N_OUTPUTS 8
+int thr_tdoastats(int device_id, size_t n, const int32_t* rx0, const int32_t* rx1, const int32_t* tx,
+                  const double* timestamp, const int64_t* det0_idx, const int64_t* det1_idx, const double* tdoa,
+                  const double* ts_range /* [2] or NULL */, const int64_t* det_range /* [2] or NULL */, int robust,
+                  thr_tdstats** result_out, thr_tdstats_counts* counts_out);
+int thr_tdstats_fetch(thr_tdstats* result, int which, void* dst, size_t dst_bytes);
+void thr_tdstats_free(thr_tdstats* result);
+/* {copies in, selection and cells, statistics, the robust part, copies out} of the thread's last thr_tdoastats */
+int thr_debug_tdoastats_times(double* ms_out /* [5] */);
+int thr_debug_tdoastats_geometry(int* tile_len, int* workgroup);
 
 #ifdef __cplusplus
 }

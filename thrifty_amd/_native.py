@@ -48,6 +48,8 @@ EXPORTS = [
     "thr_survey_feed", "thr_survey_feed_stream", "thr_debug_survey_geometry",
     "thr_chipscan", "thr_debug_chipscan_geometry", "thr_debug_chipscan_budget", "thr_debug_chipscan_times",
     "thr_toadstats", "thr_tstats_fetch", "thr_tstats_free", "thr_debug_toadstats_times", "thr_debug_toadstats_geometry",
+    "thr_beaconsync", "thr_bsync_fetch", "thr_bsync_free", "thr_debug_beaconsync_times", "thr_debug_beaconsync_geometry",
+    "thr_tdoastats", "thr_tdstats_fetch", "thr_tdstats_free", "thr_debug_tdoastats_times", "thr_debug_tdoastats_geometry",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -56,6 +58,18 @@ PATHS = {"auto": 0, "multipass": 1, "unsectioned": 2, "generic_rows": 3, "unsect
 MAX_IN_FLIGHT = 3       # THR_MAX_IN_FLIGHT
 TOAD_LINE_MAX = 384     # THR_TOAD_LINE_MAX
 CARD_HEADER_MAX = 48    # THR_CARD_HEADER_MAX
+
+
+BSYNC_COUNTS = ("rows", "cells", "discontinuities", "cuts")
+TDSTATS_COUNTS = ("rows", "cells", "robust")
+
+
+class ThrBsyncCounts(C.Structure):        # thr_bsync_counts
+    _fields_ = [(name, C.c_size_t) for name in BSYNC_COUNTS]
+
+
+class ThrTdstatsCounts(C.Structure):      # thr_tdstats_counts
+    _fields_ = [(name, C.c_size_t) for name in TDSTATS_COUNTS]
 
 
 class ThrSettings(C.Structure):
@@ -321,6 +335,17 @@ def load_library():
     lib.thr_tstats_free.restype = None
     lib.thr_debug_toadstats_times.argtypes = [C.POINTER(C.c_double)]
     lib.thr_debug_toadstats_geometry.argtypes = [ip, ip]
+    lib.thr_beaconsync.argtypes = ([C.c_int, C.c_size_t] + [vp] * 6 + [C.c_size_t, vp, vp, C.c_int, vp, vp, C.c_size_t,
+                                   vp, C.c_size_t, C.POINTER(vp), C.POINTER(ThrBsyncCounts)])
+    lib.thr_tdoastats.argtypes = ([C.c_int, C.c_size_t] + [vp] * 7 + [vp, vp, C.c_int, C.POINTER(vp),
+                                  C.POINTER(ThrTdstatsCounts)])
+    for stem in ("bsync", "tdstats"):
+        getattr(lib, "thr_%s_fetch" % stem).argtypes = [vp, C.c_int, vp, C.c_size_t]
+        getattr(lib, "thr_%s_free" % stem).argtypes = [vp]
+        getattr(lib, "thr_%s_free" % stem).restype = None
+    for stem in ("beaconsync", "tdoastats"):
+        getattr(lib, "thr_debug_%s_times" % stem).argtypes = [C.POINTER(C.c_double)]
+        getattr(lib, "thr_debug_%s_geometry" % stem).argtypes = [ip, ip]
     _lib = lib
     return lib
 
@@ -1583,4 +1608,142 @@ def toadstats_geometry():
     lib = load_library()
     t, w = C.c_int(), C.c_int()
     _check(lib, lib.thr_debug_toadstats_geometry(C.byref(t), C.byref(w)))
+    return t.value, w.value
+
+
+# the detection columns of thr_beaconsync, in its argument order
+BSYNC_COLUMNS = (("rxid", np.int32), ("txid", np.int32), ("soa", np.float64), ("energy", np.float64),
+                 ("noise", np.float64), ("idx", np.int64))
+BSYNC_CUT_FITTED, BSYNC_CUT_DEGENERATE, BSYNC_CELL_NO_FIT = 1, 2, 1       # THR_BSYNC_CUT_*, THR_BSYNC_CELL_NO_FIT
+# THR_BSYNC_*: name -> (index, dtype, shape as a function of the counts)
+BSYNC_OUTPUTS = {
+    "cell_key": (0, np.int32, lambda c: (c["cells"], 3)),
+    "cell_ptr": (1, np.int64, lambda c: (c["cells"] + 1,)),
+    "row_det": (2, np.int64, lambda c: (c["rows"], 2)),
+    "row_match": (3, np.int64, lambda c: (c["rows"],)),
+    "sdoa": (4, np.float64, lambda c: (c["rows"],)),
+    "disc_ptr": (5, np.int64, lambda c: (c["cells"] + 1,)),
+    "disc_idx": (6, np.int64, lambda c: (c["discontinuities"],)),
+    "cut_ptr": (7, np.int64, lambda c: (c["cells"] + 1,)),
+    "cut_left": (8, np.int64, lambda c: (c["cuts"],)),
+    "cut_right": (9, np.int64, lambda c: (c["cuts"],)),
+    "cut_flags": (10, np.int32, lambda c: (c["cuts"],)),
+    "cut_fit": (11, np.float64, lambda c: (c["cuts"], 7)),
+    "cut_snr": (12, np.float64, lambda c: (c["cuts"],)),
+    "cut_disc_soa": (13, np.float64, lambda c: (c["cuts"],)),
+    "residual": (14, np.float64, lambda c: (c["rows"],)),
+    "cell_counts": (15, np.int64, lambda c: (c["cells"], 3)),
+    "cell_stats": (16, np.float64, lambda c: (c["cells"], 4)),
+    "cell_flags": (17, np.int32, lambda c: (c["cells"],)),
+}
+# the columns of a .tdoa matrix as thr_tdoastats takes them
+TDSTATS_COLUMNS = (("rx0", np.int32), ("rx1", np.int32), ("tx", np.int32), ("timestamp", np.float64),
+                   ("det0_idx", np.int64), ("det1_idx", np.int64), ("tdoa", np.float64))
+TDSTATS_OUTPUTS = {
+    "cell_key": (0, np.int32, lambda c: (c["cells"], 3)),
+    "cell_ptr": (1, np.int64, lambda c: (c["cells"] + 1,)),
+    "order": (2, np.int64, lambda c: (c["rows"],)),
+    "stats": (3, np.float64, lambda c: (c["cells"], 5)),
+    "robust_stats": (4, np.float64, lambda c: (c["cells"] * c["robust"], 5)),
+    "robust_count": (5, np.int64, lambda c: (c["cells"] * c["robust"],)),
+    "mask": (6, np.uint8, lambda c: (c["rows"] * c["robust"],)),
+    "median": (7, np.float64, lambda c: (c["cells"] * c["robust"], 2)),
+}
+
+
+def _columns(columns, spec, who):
+    cols = [np.ascontiguousarray(columns[name], dtype=kind) for name, kind in spec]
+    if any(col.ndim != 1 or len(col) != len(cols[0]) for col in cols):
+        raise ValueError("%s: the columns differ in length" % who)
+    return cols
+
+
+def _pair(value, kind, who):
+    """A closed range as a two-element array, None for none."""
+    if value is None:
+        return None
+    value = np.ascontiguousarray(value, dtype=kind)
+    if value.shape != (2,):
+        raise ValueError("%s: a range is two numbers" % who)
+    return value
+
+
+def _fetch_all(lib, stem, handle, counts, table, outputs):
+    fetch, free = getattr(lib, "thr_%s_fetch" % stem), getattr(lib, "thr_%s_free" % stem)
+    try:
+        out = {}
+        for name in (table if outputs is None else outputs):
+            which, kind, shape = table[name]
+            out[name] = np.zeros(shape(counts), dtype=kind)
+            _check(lib, fetch(handle, which, out[name].ctypes.data, out[name].nbytes))
+    finally:
+        free(handle)
+    return out
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def beaconsync(columns, match_ptr, match_idx, deg=2, id_range=None, beacons=None, receivers=None, outputs=None,
+               device_id=0):
+    """thr_beaconsync on the six detection columns (a mapping with the names of BSYNC_COLUMNS) and the matches
+    as CSR -> (counts dict, {name: array}) with every output of BSYNC_OUTPUTS (or those named in `outputs`)
+    fetched.  ValueError for what thr_beaconsync refuses."""
+    lib = load_library()
+    cols = _columns(columns, BSYNC_COLUMNS, "beaconsync")
+    n = len(cols[0])
+    ptr = np.ascontiguousarray(match_ptr, dtype=np.int64)
+    idx = np.ascontiguousarray(match_idx, dtype=np.int64)
+    if ptr.ndim != 1 or idx.ndim != 1 or len(ptr) < 1 or (ptr[-1] != len(idx) if len(ptr) else True):
+        raise ValueError("beaconsync: match_ptr and match_idx are not a CSR pair")
+    rng = _pair(id_range, np.int64, "beaconsync")
+    lists = [None if v is None else np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (beacons, receivers)]
+    keep = np.zeros(1, dtype=np.int64)      # an empty array still needs a pointer that is not NULL
+    handle, counts = C.c_void_p(), ThrBsyncCounts()
+    rc = lib.thr_beaconsync(int(device_id), n, *[col.ctypes.data if n else None for col in cols], len(ptr) - 1,
+                            ptr.ctypes.data, idx.ctypes.data if len(idx) else keep.ctypes.data, int(deg), _ptr(rng),
+                            None if lists[0] is None else (lists[0].ctypes.data if len(lists[0]) else keep.ctypes.data),
+                            0 if lists[0] is None else len(lists[0]),
+                            None if lists[1] is None else (lists[1].ctypes.data if len(lists[1]) else keep.ctypes.data),
+                            0 if lists[1] is None else len(lists[1]), C.byref(handle), C.byref(counts))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    c = {name: int(getattr(counts, name)) for name in BSYNC_COUNTS}
+    return c, _fetch_all(lib, "bsync", handle, c, BSYNC_OUTPUTS, outputs)
+
+
+def tdoastats(columns, timestamp=None, detidx=None, robust=False, outputs=None, device_id=0):
+    """thr_tdoastats on the seven columns of a .tdoa matrix (a mapping or a structured array with the names of
+    TDSTATS_COLUMNS) -> (counts dict, {name: array}).  ValueError for what thr_tdoastats refuses."""
+    lib = load_library()
+    cols = _columns(columns, TDSTATS_COLUMNS, "tdoastats")
+    n = len(cols[0])
+    ts, det = _pair(timestamp, np.float64, "tdoastats"), _pair(detidx, np.int64, "tdoastats")
+    handle, counts = C.c_void_p(), ThrTdstatsCounts()
+    rc = lib.thr_tdoastats(int(device_id), n, *[col.ctypes.data if n else None for col in cols], _ptr(ts), _ptr(det),
+                           int(bool(robust)), C.byref(handle), C.byref(counts))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    c = {name: int(getattr(counts, name)) for name in TDSTATS_COUNTS}
+    return c, _fetch_all(lib, "tdstats", handle, c, TDSTATS_OUTPUTS, outputs)
+
+
+def syncstats_times(which):
+    """Milliseconds (HIP events) of this thread's last beaconsync() (`which` = "beaconsync": copies in, rows and
+    cells, discontinuities and cuts, fits and summary, copies out) or tdoastats() ("tdoastats": copies in,
+    selection and cells, statistics, the robust part, copies out)."""
+    lib = load_library()
+    ms = (C.c_double * 5)()
+    _check(lib, getattr(lib, "thr_debug_%s_times" % which)(ms))
+    return tuple(ms)
+
+
+def syncstats_geometry(which):
+    """thr_debug_{beaconsync,tdoastats}_geometry -> (tile length T, workgroup size W)."""
+    lib = load_library()
+    t, w = C.c_int(), C.c_int()
+    _check(lib, getattr(lib, "thr_debug_%s_geometry" % which)(C.byref(t), C.byref(w)))
     return t.value, w.value
