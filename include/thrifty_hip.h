@@ -79,7 +79,10 @@ extern "C" {
  *      energy bound (records unchanged)
  *    + thr_beaconsync / thr_bsync_fetch / thr_bsync_free and thr_tdoastats / thr_tdstats_fetch /
  *      thr_tdstats_free, with thr_debug_{beaconsync,tdoastats}_{times,geometry} -- the numbers of the
- *      reference's `thrifty analyze_beacon` and `thrifty analyze_tdoa`, for every cell in one call */
+ *      reference's `thrifty analyze_beacon` and `thrifty analyze_tdoa`, for every cell in one call
+ *    + thr_dossier_create / _destroy / _reset / _feed / _feed_card / _feed_stream / _result / _geometry -- the
+ *      numbers of the reference's `thrifty analyze_detect` (detect_analysis.py): the first detected blocks
+ *      inside a list of index ranges, kept on the device, and per kept block what its plots are drawn from */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -712,6 +715,87 @@ int thr_run_extract_card(thr_handle* h, const char* text, size_t text_len, const
                          thr_extract* x, thr_run_stats* stats);
 int thr_run_extract_stream(thr_handle* h, const uint8_t* stream, size_t n_bytes, int64_t first_block_idx,
                            const thr_run_opts* opts, thr_extract* x, thr_run_stats* stats);
+
+/*
+ * Detection dossiers -- the numbers behind the reference's `thrifty analyze_detect` (detect_analysis.py:
+ * ForcibleDetector over the blocks of a capture whose index lies in a list of ranges, keep the first
+ * `max` that are detected, and for each of them everything its Plotter derives; the plots stay out).
+ * A thr_dossier rides on a default single-template detector handle like template extraction's object (preshift, fastdet,
+ * gate and several-template handles: THR_ERR_ARG); forcing a verdict is the handle's business (create it
+ * with the threshold (0, 0, 0)).  Behind the kernels of every batch, on the same stream and with no host
+ * decision in between, one kernel hands the next free slots to the records that qualify and one copies
+ * their input samples into the slots:
+ *   qualifies: THR_FLAG_CARRIER and THR_FLAG_CORR both set and block_idx inside one of the `n_ranges`
+ *     closed ranges ranges[2 i] .. ranges[2 i + 1] (an open end is INT64_MIN / INT64_MAX; at most 16);
+ *   slots are taken in feed order, up to `max_keep`, whatever the batching;
+ *   n_checked = in-range records seen, n_skipped = those of them that were not detected; counting ends
+ *     with the record that fills the last slot (where the reference's loop breaks).
+ * thr_dossier_create: THR_ERR_ARG for n_ranges > 16, max_keep < 1, or max_keep blocks of complex64
+ *   samples (8 * block_len bytes each, the larger of the two input formats) above 256 MiB.
+ * thr_dossier_feed / _feed_card / _feed_stream: their thr_extract_feed* twins plus the pick; they return
+ *   when the batch is done, with the counts after it (any of the three outputs may be NULL).  All feeds of
+ *   a dossier carry one sample format.  Feeding on after the slots are full changes nothing.
+ * thr_dossier_result: for the slots [first, first + count) (clipped to the kept ones; *n_kept = all kept),
+ *   every array of `out` that is not NULL is filled, one row per slot:
+ *     records, timestamps, positions (blocks fed before it since the reset);
+ *     hist[256]       occurrences of each byte value among the block's 2 N bytes (zeros for complex64 input)
+ *     fft_mag[N]      |FFT(x)|, natural order
+ *     filtered[N - F/2]  sqrt(sum_j w_j^2 m[i + j]^2), j = -F/2 .. F/2, m = fft_mag (0 below bin 0), w the
+ *                     unit-energy Dirichlet weights of F + 1 taps, F = 2 * (N / carrier_len)
+ *     synced[N][2]    x[n] * exp(2 pi i s (n / N - 1/2)), s = -(carrier_bin + carrier_offset)
+ *     synced_fft_mag[N]  magnitude of the shifted spectrum
+ *     corr[corr_len][2]  the correlation, corr_len = N - template_len + 1 (thr_dossier_geometry)
+ *     scalars         thr_dossier_scalars below
+ *   and autocorr[17] = sum_i t[i + l] t[i], l = 0 .. 16, once.  The spectra and the correlation are the
+ *   handle's unsectioned stage dumps (thr_debug_stage) of the kept samples; the work runs in chunks of at
+ *   most max_batch blocks.  No kept block: THR_OK with *n_kept = 0.
+ * Same single-threaded rule and destroy order as thr_extract: the dossier goes before its handle.
+ */
+typedef struct thr_dossier_scalars {
+    double rms_unsynced, rms_synced;     /* sqrt(mean |x|^2) of the input and of `synced`            */
+    double fft_std, corr_std;            /* np.std(fft_mag), np.std(|corr|); 0 without a stddev term */
+    double synced_fft_std, filtered_std; /* np.std of synced_fft_mag and of filtered, likewise: the
+                                            spectrum views put the carrier threshold formula over them */
+    double carrier_threshold;            /* carrier_detect._calculate_threshold                      */
+    double corr_threshold;               /* soa_estimator.calculate_threshold                        */
+    double fit_amplitude, fit_offset;    /* Dirichlet fit on the 7 magnitudes around carrier_bin;
+                                            NaN when fit_valid == 0                                  */
+    int32_t fit_valid;                   /* 0: carrier_bin < 6 or > N - 7 (the reference wraps inside
+                                            its slice there)                                         */
+    int32_t peak_start, peak_len;        /* corr[p - 5 : p + 6] clipped to [0, corr_len)             */
+    int32_t reserved;
+    double corr_shifted[11];             /* |time_shift(corr[peak window], corr_offset)|, peak_len valid */
+} thr_dossier_scalars;
+typedef struct thr_dossier_out {
+    thr_record* records;
+    double* timestamps;
+    uint64_t* positions;
+    uint32_t* hist;
+    float* fft_mag;
+    float* filtered;
+    float* synced;
+    float* synced_fft_mag;
+    float* corr;
+    thr_dossier_scalars* scalars;
+    double* autocorr;
+} thr_dossier_out;
+typedef struct thr_dossier thr_dossier;
+int thr_dossier_create(thr_handle* h, const int64_t* ranges, int n_ranges, int64_t max_keep, thr_dossier** out);
+void thr_dossier_destroy(thr_dossier* d);
+int thr_dossier_reset(thr_dossier* d);
+int thr_dossier_feed(thr_dossier* d, const void* samples, int format, const int64_t* block_idx,
+                     const double* timestamps, size_t n_blocks, thr_record* out, size_t* n_kept,
+                     uint64_t* n_checked, uint64_t* n_skipped);
+int thr_dossier_feed_card(thr_dossier* d, const char* text, size_t text_len, const int64_t* payload_off,
+                          const int64_t* block_idx, const double* timestamps, size_t n_blocks, thr_record* out,
+                          size_t* n_kept, uint64_t* n_checked, uint64_t* n_skipped);
+int thr_dossier_feed_stream(thr_dossier* d, const uint8_t* stream, size_t n_bytes, int64_t first_block_idx,
+                            const double* timestamps, thr_record* out, size_t out_capacity, size_t* n_blocks_out,
+                            size_t* n_kept, uint64_t* n_checked, uint64_t* n_skipped);
+int thr_dossier_result(thr_dossier* d, size_t first, size_t count, const thr_dossier_out* out, size_t* n_kept);
+/* thr_dossier_geometry: out[0] = F (filter taps - 1), out[1] = rows of `filtered` (N - F/2), out[2] = corr_len,
+ *   out[3] = blocks per result-time chunk. */
+int thr_dossier_geometry(thr_dossier* d, int64_t out[4]);
 
 /*
  * Capture survey -- the numbers behind the reference's scripts/fft_analysis.py, hist.py and noise_rms.py

@@ -50,6 +50,8 @@ EXPORTS = [
     "thr_toadstats", "thr_tstats_fetch", "thr_tstats_free", "thr_debug_toadstats_times", "thr_debug_toadstats_geometry",
     "thr_beaconsync", "thr_bsync_fetch", "thr_bsync_free", "thr_debug_beaconsync_times", "thr_debug_beaconsync_geometry",
     "thr_tdoastats", "thr_tdstats_fetch", "thr_tdstats_free", "thr_debug_tdoastats_times", "thr_debug_tdoastats_geometry",
+    "thr_dossier_create", "thr_dossier_destroy", "thr_dossier_reset", "thr_dossier_feed", "thr_dossier_feed_card",
+    "thr_dossier_feed_stream", "thr_dossier_result", "thr_dossier_geometry",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -172,6 +174,22 @@ TSTATS_COUNTS = ("rows", "cells", "receivers", "minute_bins", "carrier_bins", "o
 
 class ThrTstatsCounts(C.Structure):       # thr_tstats_counts
     _fields_ = [(name, C.c_size_t) for name in TSTATS_COUNTS] + [("time0", C.c_double)]
+
+
+class ThrDossierOut(C.Structure):          # thr_dossier_out
+    _fields_ = [(name, C.c_void_p) for name in (
+        "records", "timestamps", "positions", "hist", "fft_mag", "filtered", "synced", "synced_fft_mag", "corr",
+        "scalars", "autocorr")]
+
+
+DOSSIER_SCALARS_DTYPE = np.dtype([      # thr_dossier_scalars
+    ("rms_unsynced", "<f8"), ("rms_synced", "<f8"), ("fft_std", "<f8"), ("corr_std", "<f8"),
+    ("synced_fft_std", "<f8"), ("filtered_std", "<f8"),
+    ("carrier_threshold", "<f8"), ("corr_threshold", "<f8"), ("fit_amplitude", "<f8"), ("fit_offset", "<f8"),
+    ("fit_valid", "<i4"), ("peak_start", "<i4"), ("peak_len", "<i4"), ("reserved", "<i4"),
+    ("corr_shifted", "<f8", (11,))])
+DOSSIER_MAX_RANGES = 16
+DOSSIER_ARRAYS = ("hist", "fft_mag", "filtered", "synced", "synced_fft_mag", "corr", "scalars")
 
 
 class NativeError(RuntimeError):
@@ -298,6 +316,15 @@ def load_library():
     lib.thr_extract_submit_card.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp, u64p]
     lib.thr_extract_submit_stream.argtypes = [vp, vp, C.c_size_t, C.c_int64, C.c_double, vp, C.c_size_t, szp, u64p]
     lib.thr_extract_result.argtypes = [vp, vp, C.POINTER(C.c_double), vp, C.c_size_t, u64p]
+    lib.thr_dossier_create.argtypes = [vp, vp, C.c_int, C.c_int64, C.POINTER(vp)]
+    lib.thr_dossier_destroy.argtypes = [vp]
+    lib.thr_dossier_destroy.restype = None
+    lib.thr_dossier_reset.argtypes = [vp]
+    lib.thr_dossier_feed.argtypes = [vp, vp, C.c_int, vp, vp, C.c_size_t, vp, szp, u64p, u64p]
+    lib.thr_dossier_feed_card.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp, szp, u64p, u64p]
+    lib.thr_dossier_feed_stream.argtypes = [vp, vp, C.c_size_t, C.c_int64, vp, vp, C.c_size_t, szp, szp, u64p, u64p]
+    lib.thr_dossier_result.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(ThrDossierOut), szp]
+    lib.thr_dossier_geometry.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.thr_run_extract_card.argtypes = [vp, vp, C.c_size_t, C.POINTER(ThrRunOpts), vp, C.POINTER(ThrRunStats)]
     lib.thr_run_extract_stream.argtypes = [vp, vp, C.c_size_t, C.c_int64, C.POINTER(ThrRunOpts), vp,
                                            C.POINTER(ThrRunStats)]
@@ -1191,6 +1218,129 @@ class Extraction(object):
             raise ValueError(self._lib.thr_last_error().decode())
         _check(self._lib, rc)
         return rec[0], ts.value, out, n.value
+
+
+class Dossiers(object):
+    """Detection dossiers riding on an Engine (thr_dossier_*): feed it the blocks of a capture in any batching,
+    through any of the engine's input forms; the first `max_keep` blocks that are detected and whose index lies
+    in one of `ranges` ((lo, hi) closed, None = open) are kept on the device.  `result()` then returns, per kept
+    block, what the reference's analyze_detect derives from it.  Every feed returns the batch's records and
+    updates `n_kept`, `n_checked`, `n_skipped`.  The engine must be the default single-template detector."""
+
+    def __init__(self, engine, ranges=((None, None),), max_keep=20):
+        self._lib, self._eng = engine._lib, engine
+        flat = np.array([[-2**63 if lo is None else int(lo), 2**63 - 1 if hi is None else int(hi)]
+                         for lo, hi in ranges], dtype=np.int64).reshape(-1, 2)
+        self.max_keep = int(max_keep)
+        self.n_kept = self.n_checked = self.n_skipped = 0
+        d = C.c_void_p()
+        _check(self._lib, self._lib.thr_dossier_create(engine._h, flat.ctypes.data if flat.size else None,
+                                                       flat.shape[0], self.max_keep, C.byref(d)))
+        self._d = d
+        geo = (C.c_int64 * 4)()
+        _check(self._lib, self._lib.thr_dossier_geometry(d, geo))
+        self.filter_width, self.filtered_len, self.corr_len, self.chunk_blocks = (int(v) for v in geo)
+
+    def close(self):
+        if getattr(self, "_d", None):
+            if getattr(self._eng, "_h", None):      # (an engine that is gone took the device state with it)
+                self._lib.thr_dossier_destroy(self._d)
+            self._d = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # noqa: BLE001
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def full(self):
+        return self.n_kept >= self.max_keep
+
+    def reset(self):
+        _check(self._lib, self._lib.thr_dossier_reset(self._d))
+        self.n_kept = self.n_checked = self.n_skipped = 0
+
+    def _counts(self):
+        k, c, s = C.c_size_t(0), C.c_uint64(0), C.c_uint64(0)
+        return (k, c, s), (C.byref(k), C.byref(c), C.byref(s))
+
+    def _done(self, rc, counts):
+        _check(self._lib, rc)
+        self.n_kept, self.n_checked, self.n_skipped = (int(v.value) for v in counts)
+
+    def feed(self, blocks, timestamps=None, block_idx=None):
+        """thr_dossier_feed: u8 [B, 2N] or complex64 [B, N] blocks -> the batch's records [B]."""
+        eng = self._eng
+        a, fmt = eng._as_input(blocks)
+        nb = a.shape[0]
+        out = np.zeros(nb, dtype=RECORD_DTYPE)
+        idx, idx_p = eng._idx_ptr(block_idx, nb)
+        ts, ts_p = Extraction._stamps(timestamps, nb)
+        counts, refs = self._counts()
+        self._done(self._lib.thr_dossier_feed(self._d, a.ctypes.data, fmt, idx_p, ts_p, nb, out.ctypes.data, *refs),
+                   counts)
+        return out
+
+    def feed_card(self, text, payload_off, timestamps=None, block_idx=None):
+        """thr_dossier_feed_card: .card text + payload offsets (see Engine.detect_card) -> records [B]."""
+        buf = np.frombuffer(text, dtype=np.uint8)
+        off = np.ascontiguousarray(np.asarray(payload_off, dtype=np.int64))
+        nb = off.shape[0]
+        out = np.zeros(nb, dtype=RECORD_DTYPE)
+        idx, idx_p = self._eng._idx_ptr(block_idx, nb)
+        ts, ts_p = Extraction._stamps(timestamps, nb)
+        counts, refs = self._counts()
+        self._done(self._lib.thr_dossier_feed_card(self._d, buf.ctypes.data, buf.size, off.ctypes.data, idx_p, ts_p,
+                                                   nb, out.ctypes.data, *refs), counts)
+        return out
+
+    def feed_stream(self, stream, first_block_idx=0, timestamps=None):
+        """thr_dossier_feed_stream: raw u8 I/Q bytes, overlapping blocks framed on the device -> records."""
+        eng = self._eng
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        stride = 2 * (eng.block_len - eng.history_len)
+        nb = 0 if buf.size < 2 * eng.block_len else (buf.size - 2 * eng.block_len) // stride + 1
+        out = np.zeros(nb, dtype=RECORD_DTYPE)
+        ts, ts_p = Extraction._stamps(timestamps, nb)
+        got = C.c_size_t(0)
+        counts, refs = self._counts()
+        self._done(self._lib.thr_dossier_feed_stream(self._d, buf.ctypes.data if buf.size else None, buf.size,
+                                                     int(first_block_idx), ts_p, out.ctypes.data, max(1, nb),
+                                                     C.byref(got), *refs), counts)
+        assert got.value == nb
+        return out
+
+    def result(self, first=0, count=None, arrays=DOSSIER_ARRAYS):
+        """thr_dossier_result for the slots [first, first + count) -> dict: records, timestamps, positions,
+        autocorr (float64 [17]) and the arrays asked for (hist uint32 [K, 256], fft_mag / synced_fft_mag
+        float32 [K, N], filtered float32 [K, N - F/2], synced complex64 [K, N], corr complex64 [K, corr_len],
+        scalars DOSSIER_SCALARS_DTYPE [K])."""
+        total = C.c_size_t(0)
+        _check(self._lib, self._lib.thr_dossier_result(self._d, 0, 0, None, C.byref(total)))
+        first = int(first)
+        k = max(0, min(total.value - first, total.value if count is None else int(count)))
+        n = self._eng.block_len
+        shapes = {"hist": ((k, 256), np.uint32), "fft_mag": ((k, n), np.float32),
+                  "filtered": ((k, self.filtered_len), np.float32), "synced": ((k, n), np.complex64),
+                  "synced_fft_mag": ((k, n), np.float32), "corr": ((k, self.corr_len), np.complex64),
+                  "scalars": ((k,), DOSSIER_SCALARS_DTYPE)}
+        res = {"records": np.zeros(k, dtype=RECORD_DTYPE), "timestamps": np.zeros(k), "positions": np.zeros(k, np.uint64),
+               "autocorr": np.zeros(17)}
+        for name in arrays:
+            res[name] = np.zeros(*shapes[name])
+        if k:
+            o = ThrDossierOut()
+            for name, a in res.items():
+                setattr(o, name, a.ctypes.data)
+            _check(self._lib, self._lib.thr_dossier_result(self._d, first, k, C.byref(o), None))
+        return res
 
 
 class Survey(object):

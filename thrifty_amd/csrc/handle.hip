@@ -709,6 +709,9 @@ static int create_body(const thr_settings* s, int preshift_num, thr_handle** out
     if (rc == THR_OK && preshift_num) rc = build_preshift_bank(h.get());
     h->cfg.templates = nullptr;
     if (rc != THR_OK) return rc;
+    // (time domain, for thr_dossier_create's autocorrelation: the caller's array is gone after this call)
+    if (s->templates && s->n_templates >= 1)
+        h->tpl_time.assign(s->templates, s->templates + size_t(s->n_templates) * size_t(s->template_len));
 
     // (the > 64 KiB dynamic-LDS opt-in is per device and kernel, not per handle: each family of
     // kernels is prepared once per device and process -- dozens of hipFuncSetAttribute calls

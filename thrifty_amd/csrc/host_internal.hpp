@@ -103,6 +103,7 @@ struct thr_handle {
     Dev<float2> d_tables;
     Dev<float2> d_twn;
     Dev<float4> d_tspec;
+    std::vector<double> tpl_time;   // the templates as given, [n_templates][template_len] (dossier.hip)
     // per-batch work buffers
     Dev<thr::CarStats> d_stats;
     Dev<thr::ShiftParams> d_shifts;

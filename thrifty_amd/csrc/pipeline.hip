@@ -3,6 +3,7 @@
 
 #include "card_gate.hpp"
 #include "template_extract.hpp"
+#include "dossier.hpp"
 
 namespace thr {
 namespace host {
@@ -480,6 +481,8 @@ int chunk_samples(thr_handle* h, int b, const void* src, int format, size_t blk_
     if (rc != THR_OK) return rc;
     // (a template extraction in progress folds the batch's records and keeps the winner's samples here)
     if ((rc = extract_after_chunk(h, b, s.d_in, format, stride, first, nb)) != THR_OK) return rc;
+    // (a dossier feed in progress picks the batch's detections and keeps their samples here)
+    if ((rc = dossier_after_chunk(h, b, s.d_in, format, stride, first, nb)) != THR_OK) return rc;
     lap(3);
     rc = pipe_records_enqueued(h, b, dst, nb * size_t(h->cfg.n_templates), first, false);
     lap(4);
@@ -531,6 +534,7 @@ int chunk_card(thr_handle* h, int b, const char* text, size_t text_len, const in
     rc = run_batch(h, s.d_in, THR_IN_U8, s.d_idx, int(nb), s.d_rec, nullptr, nullptr, nullptr, 0, false);
     if (rc != THR_OK) return rc;
     if ((rc = extract_after_chunk(h, b, s.d_in, THR_IN_U8, 0, first, nb)) != THR_OK) return rc;
+    if ((rc = dossier_after_chunk(h, b, s.d_in, THR_IN_U8, 0, first, nb)) != THR_OK) return rc;
     lap(3);
     rc = pipe_records_enqueued(h, b, dst, nb * size_t(h->cfg.n_templates), first, true);
     lap(4);
