@@ -82,7 +82,9 @@ extern "C" {
  *      reference's `thrifty analyze_beacon` and `thrifty analyze_tdoa`, for every cell in one call
  *    + thr_dossier_create / _destroy / _reset / _feed / _feed_card / _feed_stream / _result / _geometry -- the
  *      numbers of the reference's `thrifty analyze_detect` (detect_analysis.py): the first detected blocks
- *      inside a list of index ranges, kept on the device, and per kept block what its plots are drawn from */
+ *      inside a list of index ranges, kept on the device, and per kept block what its plots are drawn from
+ *    + thr_tdoa_model and THR_TDOA_* -- thr_tdoa with the reference's weighted, nearest and linear models
+ *      (tdoa_est.py:108-222); thr_post_settings.reserved (always 0) is now .tdoa_model, 0 = the polynomial */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -1100,7 +1102,48 @@ int thr_tdoa(int device_id, size_t n_det, const int32_t* rx, const double* times
              int32_t* row_rx_out, int64_t* row_det_out, double* row_val_out, size_t* n_rows_out,
              int64_t* group_id_out, int64_t* group_ptr_out, size_t* n_groups_out,
              int64_t* fail_out, size_t* n_fail_out, int32_t* n_window_out, int32_t* n_kept_out);
-/* Milliseconds of the calling thread's last thr_tdoa: {copies in, kernels, copies out} (HIP events). */
+/*
+ * thr_tdoa with the reference's other three models (thrifty/tdoa_est.py:108-222).  Everything up to the
+ * KEPT LIST of a task -- the lists, the window, the outlier mask -- and everything after its tdoa -- the
+ * |tdoa| >= 30e3 / 2.997e8 failure, snr, model_quality, the output orders -- is thr_tdoa's.  The kept list
+ * is the window's pairs the mask left, in list order (the models' own sort, with the same never-negative
+ * cmp, leaves it alone); n_kept its length; T, S0, S1 its det0 timestamps and SoAs; b_sdoa[i] =
+ * (dist[rx0][b_i] - dist[rx1][b_i]) / 2.997e8 * sample_rate; t0, soa0, soa1 the task's own.  `model`:
+ *  THR_TDOA_POLY           thr_tdoa's polynomial; thr_tdoa is this call with null picks.
+ *  THR_TDOA_WEIGHTED_POLY  n_kept < deg + 1: a failure.  w = sqrt(1 / |S0 - soa0|); w / max(w); sqrt(w);
+ *     (w + 2) / 3 -- float64, each operation correctly rounded, so the weights are numpy's bits; the
+ *     polynomial of degree deg minimises sum (w_i (S0_i - p(S1_i + b_sdoa_i)))^2 (np.polyfit's w=), fitted
+ *     in the same centred and scaled variable with w_i^2 in the moments; tdoa = (soa0 - p(soa1)) /
+ *     sample_rate.  Fewer than deg + 1 distinct kept abscissae: a failure, as for thr_tdoa.
+ *  THR_TDOA_NEAREST        n_kept < 1: a failure.  idx = bisect_left(T, t0) -- Python's probes over the kept
+ *     list, sorted or not; idx - 1 instead if idx > 0 and (idx == n_kept or |t0 - T[idx - 1]| <
+ *     |t0 - T[idx]|) (strict: a tie stays on idx); tdoa = ((soa0 - S0[idx]) - (soa1 - S1[idx]) +
+ *     b_sdoa[idx]) / sample_rate, in that order of operations: the reference's bits.
+ *  THR_TDOA_LINEAR         n_kept < 2: a failure.  high = bisect_left(T, t0), n_kept - 1 if that is n_kept;
+ *     low = high - 1, then down while low >= 0 and the pair's beacon (match_beacon) differs from pair
+ *     high's; low < 0: a failure.  weight = (soa0 - S0[low]) / (S0[high] - S0[low]); tau = (S1[low] *
+ *     (1 - weight) + S1[high] * weight) - soa1; tdoa = (tau + b_sdoa[high]) / sample_rate -- the
+ *     reference's signs and operation order, hence its bits.
+ * deg is read by the two polynomials only.  pick_out (may be null) holds 2 * n_tasks values: per task, as
+ * positions in the kept list, {idx, -1} (nearest), {low, high} (linear; low == -1 where the walk ran out),
+ * {-1, -1} for the polynomials and for a task that failed before it picked.  Deviations from the
+ * reference: S0[high] == S0[low] is a failure (linear; reference: ZeroDivisionError); a kept pair with
+ * S0_i == soa0 is a failure (weighted; the reference's weights turn inf / NaN and it appends a NaN row).
+ * A model outside 0..3: THR_ERR_ARG before anything is launched.
+ */
+#define THR_TDOA_POLY 0
+#define THR_TDOA_WEIGHTED_POLY 1
+#define THR_TDOA_NEAREST 2
+#define THR_TDOA_LINEAR 3
+int thr_tdoa_model(int device_id, size_t n_det, const int32_t* rx, const double* timestamp, const double* soa,
+                   const double* energy, const double* noise, size_t n_matches, const int64_t* match_ptr,
+                   const int64_t* match_idx, const int32_t* match_beacon, int n_rx, int n_beacons,
+                   const double* dist, double window, double sample_rate, int deg, size_t n_tasks,
+                   int32_t* row_rx_out, int64_t* row_det_out, double* row_val_out, size_t* n_rows_out,
+                   int64_t* group_id_out, int64_t* group_ptr_out, size_t* n_groups_out,
+                   int64_t* fail_out, size_t* n_fail_out, int32_t* n_window_out, int32_t* n_kept_out,
+                   int model, int32_t* pick_out);
+/* Milliseconds of the calling thread's last thr_tdoa / thr_tdoa_model: {copies in, kernels, copies out} (HIP events). */
 int thr_debug_tdoa_times(double* ms_out /* [3] */);
 
 /* pos -- the reference's `thrifty pos` (thrifty/pos_est.py) on host columns: synchronous, no handle, no
@@ -1151,7 +1194,7 @@ int thr_debug_pos_times(double* ms_out /* [3] */);
  * detection pair, no row) leaves the later stages at their n == 0 case: nothing is launched for them.
  *
  * Errors (THR_ERR_ARG): a null pointer, rx_ids / beacon_ids not strictly ascending, n_rx outside 1..64,
- * dims other than 1 or 2 (1-D takes two receivers), deg outside 1..3, a non-finite coordinate or x0, a
+ * dims other than 1 or 2 (1-D takes two receivers), deg outside 1..3, tdoa_model outside 0..3, a non-finite coordinate or x0, a
  * negative window, n_beacons, min_match or max_iter -- all before the device is queried; timestamps that
  * decrease or hold a NaN after the identify sort (thr_match's sentence); a detection of a match whose
  * receiver rx_ids lacks ("... detection D is of receiver R ...").  */
@@ -1175,7 +1218,7 @@ typedef struct thr_post_settings {
     double x0[2];
     int32_t tdoa_as_text;        /* nonzero: the position stage reads every tdoa as (tdoa * 1e9) / 1e9, the value a
                                   * reader of the .tdoa text (nanoseconds) gets -- what `thrifty pos` works on */
-    int32_t reserved;            /* 0 */
+    int32_t tdoa_model;          /* THR_TDOA_*; 0 = the polynomial */
 } thr_post_settings;
 typedef struct thr_post_counts {
     size_t kept, matches, match_entries, misses, collisions, tasks, rows, groups, failures;

@@ -6,7 +6,13 @@ and range of the wall time and of its split into copies in / kernels / copies ou
 `thr_debug_tdoa_times`), and the rate in mobile detection pairs per second.  Beside it the sequential
 statement tests/tdoa_ref.py on the first --ref-matches matches of the same columns on one host core
 (its rows are compared with the device's while at it).  Writes one JSON record (default
-profiles/r10_tdoa.json); no figure is asserted anywhere."""
+profiles/r10_tdoa.json); no figure is asserted anywhere.
+
+--model M [M ...] chooses the clock model(s) (default poly).  With --postdetect-scene N the columns are
+instead the TDOA stage's input on scripts/bench_postdetect.py's scene of N raw detections (identify and
+match run first, untimed), every model is measured on them in turn in the same process, and the record
+(default profiles/r19_tdoa_models.json) holds the kernel milliseconds per model, the polynomial's as the
+yardstick beside the others."""
 import argparse
 import hashlib
 import json
@@ -56,15 +62,68 @@ def spread(values):
     return {"median": statistics.median(values), "min": min(values), "max": max(values)}
 
 
+def tdoa_hip_hash():
+    with open(os.path.join(build.CSRC, "tdoa.hip"), "rb") as f:       # (csrc_hash() leaves tdoa.hip out: UNPROFILED_TDOA)
+        return hashlib.sha256(f.read()).hexdigest()[:16]
+
+
+def measure_models(args):
+    """Every model of --model on the TDOA stage's input of the post-detect scene -> the record."""
+    import bench_postdetect
+    from thrifty_amd import identify, matchmaker
+    raw, st = bench_postdetect.scene(args.postdetect_scene)
+    txid, _, order = identify.integrate_columns(raw, st.tx_freqs)
+    cols = {name: raw[name][order] for name in ("rxid", "timestamp", "soa", "energy", "noise")}
+    cols["txid"] = txid[order]
+    ptr, idx, _, _ = matchmaker.match_columns(cols, st.match_window)
+    rec = {"csrc_hash": build.csrc_hash(), "tdoa_hip_sha256": tdoa_hip_hash(), "scene": "scripts/bench_postdetect.py",
+           "raw_detections": args.postdetect_scene, "detections": len(order), "matches": len(ptr) - 1,
+           "window_s": st.tdoa_est_window, "deg": DEG, "repeats": args.repeats, "models": {}}
+    for model in args.model:
+        run = lambda: tdoa_est.tdoa_columns(cols, ptr, idx, st.tdoa_est_window, st.beacon_pos, st.rx_pos,   # noqa: E731
+                                            st.sample_rate, DEG, model=model)
+        out = run()                                              # warm-up
+        wall, parts = [], []
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            out = run()
+            wall.append(time.perf_counter() - t0)
+            parts.append(_native.tdoa_times())
+        rec["pairs"] = len(out["n_window"])
+        rec["window_pairs"] = {"median": float(np.median(out["n_window"])), "max": int(out["n_window"].max())}
+        rec["models"][model] = {"tdoas": len(out["tdoas"]), "failures": len(out["failures"]),
+                                "kernels_ms": spread([p[1] for p in parts]), "wall_ms": spread([1e3 * w for w in wall])}
+    if "poly" in rec["models"]:
+        yardstick = rec["models"]["poly"]["kernels_ms"]["median"]
+        for model in rec["models"]:
+            rec["models"][model]["kernels_over_poly"] = rec["models"][model]["kernels_ms"]["median"] / yardstick
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--matches", type=int, default=1000000)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--ref-matches", type=int, default=4000, help="matches tests/tdoa_ref.py is run on")
-    ap.add_argument("-o", "--output", default=os.path.join(ROOT, "profiles", "r10_tdoa.json"))
+    ap.add_argument("--model", nargs="+", choices=sorted(tdoa_est.MODELS), default=["poly"])
+    ap.add_argument("--postdetect-scene", type=int, default=None, metavar="N",
+                    help="measure on the TDOA input of scripts/bench_postdetect.py's scene of N raw detections")
+    ap.add_argument("-o", "--output", default=None)
     args = ap.parse_args()
+    if args.postdetect_scene:
+        rec = measure_models(args)
+        args.output = args.output or os.path.join(ROOT, "profiles", "r19_tdoa_models.json")
+        print(json.dumps(rec), flush=True)
+        with open(args.output, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+        return
+    if len(args.model) != 1:
+        ap.error("several models are measured with --postdetect-scene only")
+    model = args.model[0]
+    args.output = args.output or os.path.join(ROOT, "profiles", "r10_tdoa.json")
     cols, ptr, idx, beacon_pos, rx_pos = scene(args.matches)
-    run = lambda: tdoa_est.tdoa_columns(cols, ptr, idx, WINDOW, beacon_pos, rx_pos, FS, DEG)   # noqa: E731
+    run = lambda: tdoa_est.tdoa_columns(cols, ptr, idx, WINDOW, beacon_pos, rx_pos, FS, DEG, model=model)   # noqa: E731
     out = run()                                                  # warm-up
     wall, parts = [], []
     for _ in range(args.repeats):
@@ -74,16 +133,14 @@ def main():
         parts.append(_native.tdoa_times())
     pairs = len(out["n_window"])
     kernels = statistics.median([p[1] for p in parts])
-    with open(os.path.join(build.CSRC, "tdoa.hip"), "rb") as f:       # (csrc_hash() leaves tdoa.hip out: UNPROFILED_TDOA)
-        kernel_hash = hashlib.sha256(f.read()).hexdigest()[:16]
-    rec = {"csrc_hash": build.csrc_hash(), "tdoa_hip_sha256": kernel_hash, "receivers": N_RX, "beacons": N_BEACON, "mobiles": N_MOBILE,
+    rec = {"csrc_hash": build.csrc_hash(), "tdoa_hip_sha256": tdoa_hip_hash(), "model": model, "receivers": N_RX, "beacons": N_BEACON, "mobiles": N_MOBILE,
            "window_s": WINDOW, "deg": DEG, "repeats": args.repeats, "matches": args.matches,
            "detections": len(cols["rxid"]), "pairs": pairs, "tdoas": len(out["tdoas"]), "failures": len(out["failures"]),
            "window_pairs": {"median": float(np.median(out["n_window"])), "max": int(out["n_window"].max())},
            "wall_ms": spread([1e3 * w for w in wall]), "copies_in_ms": spread([p[0] for p in parts]),
            "kernels_ms": spread([p[1] for p in parts]), "copies_out_ms": spread([p[2] for p in parts]),
            "pairs_per_s": pairs / statistics.median(wall), "pairs_per_s_kernels_only": pairs / (1e-3 * kernels)}
-    if args.ref_matches:
+    if args.ref_matches and model == "poly":      # (tests/tdoa_ref.py states the polynomial)
         m = min(args.ref_matches, args.matches)
         matches = idx[:m * N_RX].reshape(m, N_RX).tolist()
         t0 = time.perf_counter()

@@ -40,7 +40,7 @@ EXPORTS = [
     "thr_extract_feed_stream", "thr_extract_submit_card", "thr_extract_submit_stream", "thr_extract_result",
     "thr_run_extract_card", "thr_run_extract_stream",
     "thr_match", "thr_debug_match_times",
-    "thr_tdoa", "thr_debug_tdoa_times",
+    "thr_tdoa", "thr_debug_tdoa_times", "thr_tdoa_model",
     "thr_pos", "thr_debug_pos_times",
     "thr_postdetect", "thr_post_fetch", "thr_post_free", "thr_debug_post_times",
     "thr_debug_live_resources",
@@ -159,7 +159,7 @@ class ThrPostSettings(C.Structure):       # thr_post_settings
                 ("n_rx", C.c_int32), ("rx_ids", C.c_void_p), ("dims", C.c_int32), ("n_beacons", C.c_int32),
                 ("rx_coords", C.c_void_p), ("first_two_rx", C.c_int32 * 2), ("beacon_ids", C.c_void_p),
                 ("dist", C.c_void_p), ("tdoa_window", C.c_double), ("sample_rate", C.c_double), ("deg", C.c_int32),
-                ("max_iter", C.c_int32), ("x0", C.c_double * 2), ("tdoa_as_text", C.c_int32), ("reserved", C.c_int32)]
+                ("max_iter", C.c_int32), ("x0", C.c_double * 2), ("tdoa_as_text", C.c_int32), ("tdoa_model", C.c_int32)]
 
 
 POST_COUNTS = ("kept", "matches", "match_entries", "misses", "collisions", "tasks", "rows", "groups", "failures")
@@ -332,6 +332,7 @@ def load_library():
     lib.thr_debug_match_times.argtypes = [C.POINTER(C.c_double)]
     lib.thr_tdoa.argtypes = ([C.c_int, C.c_size_t] + [vp] * 5 + [C.c_size_t, vp, vp, vp, C.c_int, C.c_int, vp,
                              C.c_double, C.c_double, C.c_int, C.c_size_t, vp, vp, vp, szp, vp, vp, szp, vp, szp, vp, vp])
+    lib.thr_tdoa_model.argtypes = lib.thr_tdoa.argtypes + [C.c_int, vp]
     lib.thr_debug_tdoa_times.argtypes = [C.POINTER(C.c_double)]
     lib.thr_pos.argtypes = [C.c_int, C.c_size_t, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     lib.thr_debug_pos_times.argtypes = [C.POINTER(C.c_double)]
@@ -1483,14 +1484,17 @@ class ChipScan(object):
 
 TDOA_TASKS_PER_WORKGROUP = 4    # kWaves of csrc/tdoa.hip: one wavefront per task, four to a workgroup
 TDOA_LDS_WINDOW = 256           # kLdsWindow: longer windows are ranked from the columns instead of LDS
+TDOA_MODELS = {"poly": 0, "weighted_poly": 1, "nearest": 2, "linear": 3}      # THR_TDOA_*
 
 
 def tdoa(rx, timestamp, soa, energy, noise, match_ptr, match_idx, match_beacon, dist, window, sample_rate,
-         deg=2, device_id=0):
-    """thr_tdoa on detection columns (rx: dense receiver index), the matches as CSR, the beacon index of
+         deg=2, device_id=0, model=0):
+    """thr_tdoa_model (`model`: a TDOA_MODELS code; None: the older entry point thr_tdoa, the polynomial) on
+    detection columns (rx: dense receiver index), the matches as CSR, the beacon index of
     every match (-1: mobile) and dist[receiver][beacon] -> dict of row_rx int32[r, 2] (dense),
     row_det int64[r, 2], tdoa / snr / model_quality float64[r], group_id int64[g], group_ptr int64[g + 1],
-    failures int64[f, 2], n_window / n_kept int32[tasks].  ValueError for what thr_tdoa refuses."""
+    failures int64[f, 2], n_window / n_kept int32[tasks], picks int32[tasks, 2] (positions in the kept list:
+    {idx, -1} nearest, {low, high} linear, else -1).  ValueError for what thr_tdoa_model refuses."""
     lib = load_library()
     cols = [np.ascontiguousarray(rx, dtype=np.int32)] + [np.ascontiguousarray(c, dtype=np.float64)
                                                           for c in (timestamp, soa, energy, noise)]
@@ -1513,19 +1517,21 @@ def tdoa(rx, timestamp, soa, energy, noise, match_ptr, match_idx, match_beacon, 
     group_ptr = np.zeros(n_matches + 1, dtype=np.int64)
     n_window = np.zeros(n_tasks, dtype=np.int32)
     n_kept = np.zeros(n_tasks, dtype=np.int32)
+    picks = np.full((n_tasks, 2), -1, dtype=np.int32)
     n_rows, n_groups, n_fail = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-    rc = lib.thr_tdoa(int(device_id), len(cols[0]), *[c.ctypes.data for c in cols], n_matches, ptr.ctypes.data,
-                      idx.ctypes.data, beacon.ctypes.data, dist.shape[0], dist.shape[1], dist.ctypes.data,
-                      float(window), float(sample_rate), int(deg), n_tasks, row_rx.ctypes.data, row_det.ctypes.data,
-                      row_val.ctypes.data, C.byref(n_rows), group_id.ctypes.data, group_ptr.ctypes.data,
-                      C.byref(n_groups), fail.ctypes.data, C.byref(n_fail), n_window.ctypes.data, n_kept.ctypes.data)
+    args = [int(device_id), len(cols[0])] + [c.ctypes.data for c in cols] + [
+        n_matches, ptr.ctypes.data, idx.ctypes.data, beacon.ctypes.data, dist.shape[0], dist.shape[1], dist.ctypes.data,
+        float(window), float(sample_rate), int(deg), n_tasks, row_rx.ctypes.data, row_det.ctypes.data,
+        row_val.ctypes.data, C.byref(n_rows), group_id.ctypes.data, group_ptr.ctypes.data, C.byref(n_groups),
+        fail.ctypes.data, C.byref(n_fail), n_window.ctypes.data, n_kept.ctypes.data]
+    rc = lib.thr_tdoa(*args) if model is None else lib.thr_tdoa_model(*(args + [int(model), picks.ctypes.data]))
     if rc == ERR_ARG:
         raise ValueError(lib.thr_last_error().decode())
     _check(lib, rc)
     r, g = n_rows.value, n_groups.value
     return {"row_rx": row_rx[:r], "row_det": row_det[:r], "tdoa": row_val[:r, 0].copy(), "snr": row_val[:r, 1].copy(),
             "model_quality": row_val[:r, 2].copy(), "group_id": group_id[:g], "group_ptr": group_ptr[:g + 1],
-            "failures": fail[:n_fail.value], "n_window": n_window, "n_kept": n_kept}
+            "failures": fail[:n_fail.value], "n_window": n_window, "n_kept": n_kept, "picks": picks}
 
 
 def tdoa_times():
@@ -1608,7 +1614,7 @@ POST_OUTPUTS = {
 
 
 def post_settings(freq_ranges, match_window, min_match, rx_ids, rx_coords, first_two_rx, beacon_ids, dist, tdoa_window,
-                  sample_rate, deg=2, x0=(0.1, 0.1), max_iter=100, tdoa_as_text=False):
+                  sample_rate, deg=2, x0=(0.1, 0.1), max_iter=100, tdoa_as_text=False, tdoa_model=0):
     """(ThrPostSettings, the arrays it points into -- keep them alive as long as the struct)."""
     fmap = (np.zeros(0, dtype=FREQ_RANGE_DTYPE) if freq_ranges is None
             else np.ascontiguousarray(np.asarray(freq_ranges, dtype=FREQ_RANGE_DTYPE)))
@@ -1629,6 +1635,7 @@ def post_settings(freq_ranges, match_window, min_match, rx_ids, rx_coords, first
     st.tdoa_window, st.sample_rate, st.deg, st.max_iter = float(tdoa_window), float(sample_rate), int(deg), int(max_iter)
     st.x0[0], st.x0[1] = float(x0[0]), float(x0[1])
     st.tdoa_as_text = 1 if tdoa_as_text else 0
+    st.tdoa_model = int(tdoa_model)
     return st, (fmap, ids, xy, beacons, dist)
 
 

@@ -81,10 +81,13 @@ struct TdoaOut {
 };
 // n_tasks / n_pairs < 0: not known to the caller; they are read off the scans of k_pair_counts.  With no
 // task the core returns after those scans (out.n_tasks == 0, nothing else allocated or launched).
+// model: THR_TDOA_* (deg is read by the two polynomials only).  picks (may be null): receives int32[n_tasks][2],
+// the nearest / linear model's choice per task as positions in the kept list (thr_tdoa_model's pick_out).
 int tdoa_core(int n_det, const int* d_rx, const double* d_ts, const double* d_soa, const double* d_en,
               const double* d_no, int n_matches, const long long* d_ptr, const long long* d_idx,
               const int* d_beacon, int n_rx, int n_beacons, const double* d_dist, double window, double sample_rate,
-              int deg, long long n_tasks, long long n_pairs, hipStream_t s, TdoaOut& out);
+              int deg, int model, long long n_tasks, long long n_pairs, hipStream_t s, TdoaOut& out,
+              DevBuf* picks = nullptr);
 
 // ---------------------------------------------------------------- pos (pos.hip), n_groups >= 1
 struct PosPlan {  // what the host derives from the receiver table

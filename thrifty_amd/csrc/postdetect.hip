@@ -173,6 +173,9 @@ int check_settings(const thr_post_settings* st, thr::PosPlan& plan) {
         return thr::fail_msg(THR_ERR_ARG, "thr_postdetect: beacon_ids must be ascending and distinct");
     if (st->deg < 1 || st->deg > 3)
         return thr::fail_msg(THR_ERR_ARG, "thr_postdetect: deg must be 1, 2 or 3, not %d", st->deg);
+    if (st->tdoa_model < THR_TDOA_POLY || st->tdoa_model > THR_TDOA_LINEAR)
+        return thr::fail_msg(THR_ERR_ARG, "thr_postdetect: tdoa_model must be THR_TDOA_POLY (0) to THR_TDOA_LINEAR (3), not %d",
+                             st->tdoa_model);
     if (st->max_iter < 0) return thr::fail_msg(THR_ERR_ARG, "thr_postdetect: max_iter must not be negative");
     return thr::pos_plan("thr_postdetect", st->n_rx, st->dims, st->rx_coords, st->first_two_rx, st->x0, plan);
 }
@@ -340,7 +343,7 @@ extern "C" int thr_postdetect(int device_id, size_t n_in, const int32_t* rxid, c
         if (const int rc = thr::tdoa_core(k, t_dense.as<int>(), t_ts.as<double>(), t_soa.as<double>(), t_en.as<double>(),
                                           t_no.as<double>(), nm, R->mt.ptr.as<long long>(), R->mt.idx.as<long long>(),
                                           d_beacon.as<int>(), n_rx, n_beacons, d_dist.as<double>(), st->tdoa_window,
-                                          st->sample_rate, st->deg, -1, -1, s, R->td))
+                                          st->sample_rate, st->deg, st->tdoa_model, -1, -1, s, R->td))
             return rc;
         c.tasks = R->td.n_tasks;
         c.rows = R->td.n_rows;

@@ -5,12 +5,16 @@
 //      exclusive scan, scatter -- hipCUB's radix sort over the key's bits);
 //   2. every mobile match expands the same way into TASKS; one wavefront runs one task: Python's two
 //      bisections on the list's det0 timestamps (sorted or not), the median / MAD outlier mask on
-//      soa0 - soa1 in the reference's float64 operations, a least-squares polynomial of soa0 on
-//      soa1 + beacon_sdoa over the kept pairs, and the row;
+//      soa0 - soa1 in the reference's float64 operations, the MODEL over the kept pairs -- a least-squares
+//      polynomial of soa0 on soa1 + beacon_sdoa (plain or weighted), the nearest kept pair, or the line
+//      through two kept pairs of one beacon (thrifty/tdoa_est.py:89-222) -- and the row;
 //   3. rows, failures and the group table are compacted into the reference's orders by prefix sums.
 // The fit is not LAPACK's: it runs in u = (x - mean) / max|x - mean| on y - mean(y) (normal equations of
 // size deg + 1, partial pivoting, Horner in u), which keeps the digits the raw Vandermonde of abscissae
 // near 1e9..1e11 loses.  Everything that decides WHICH pairs are used is the reference's arithmetic.
+// The nearest and the linear model bisect the KEPT list (the window's pairs the mask left, in list order):
+// kept rank -> window position goes through per-trip ballots and popcounts (kept_at), whatever the window's
+// length; their formulas are the reference's operations in its order, so their results are its bits.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -210,7 +214,7 @@ __device__ double wave_median(const Window& w, int lane) {
     return (v_lo + v_hi) / 2.0;
 }
 
-template <int DEG>
+template <int DEG, int MODEL>
 __global__ __launch_bounds__(kBlock) void k_estimate(
     const int* __restrict__ task_det0, const int* __restrict__ task_det1, const int* __restrict__ rx,
     const double* __restrict__ ts, const double* __restrict__ soa, const double* __restrict__ q,
@@ -218,9 +222,12 @@ __global__ __launch_bounds__(kBlock) void k_estimate(
     const double* __restrict__ b_soa0, const double* __restrict__ b_soa1, const double* __restrict__ b_q0,
     const double* __restrict__ b_q1, const int* __restrict__ b_beacon, const double* __restrict__ dist,
     double window, double sample_rate, int n_tasks, unsigned* __restrict__ ok, double* __restrict__ out_val,
-    int* __restrict__ out_n_window, int* __restrict__ out_n_kept) {
+    int* __restrict__ out_n_window, int* __restrict__ out_n_kept, int* __restrict__ out_pick) {
     __shared__ double s_window[kWaves][kLdsWindow];
     constexpr int M = DEG + 1;
+    constexpr bool kFit = MODEL == THR_TDOA_POLY || MODEL == THR_TDOA_WEIGHTED_POLY;  // DEG is read by these only
+    constexpr bool kWeighted = MODEL == THR_TDOA_WEIGHTED_POLY;
+    constexpr int kMinKept = MODEL == THR_TDOA_NEAREST ? 1 : MODEL == THR_TDOA_LINEAR ? 2 : M;
     const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
     const int task = blockIdx.x * kWaves + wave;
     if (task >= n_tasks) return;  // the whole wavefront
@@ -286,6 +293,42 @@ __global__ __launch_bounds__(kBlock) void k_estimate(
         const double tdoa = (dist[size_t(rx0) * n_beacons + b] - dist[size_t(rx1) * n_beacons + b]) / kSpeedOfLight;
         return w_soa1[i] + tdoa * sample_rate;
     };
+    // beacon_sdoa alone, the same operations
+    auto beacon_sdoa = [&](int i) {
+        const int b = w_beacon[i];
+        const double tdoa = (dist[size_t(rx0) * n_beacons + b] - dist[size_t(rx1) * n_beacons + b]) / kSpeedOfLight;
+        return tdoa * sample_rate;
+    };
+    // window position of the kept pair of rank `rank` (0 <= rank < n_kept, the same in every lane): per trip
+    // of 64 positions a ballot of the kept ones; the trip that holds the rank names the lane by its prefix count
+    auto kept_at = [&](int rank) {
+        int before = 0;
+        for (int base = 0; base < n_window; base += kWave) {
+            const int i = base + lane;
+            const bool mine = i < n_window && kept(i);
+            const unsigned long long set = __ballot(mine);
+            const int here = __popcll(set);
+            if (rank < before + here) {
+                const int prefix = __popcll(set & ((1ull << lane) - 1ull));
+                const unsigned long long hit = __ballot(mine && prefix == rank - before);
+                return base + __ffsll((long long)hit) - 1;
+            }
+            before += here;
+        }
+        return 0;  // not reached for a rank below n_kept
+    };
+    // bisect_left(T, t0) over the kept pairs' det0 timestamps: Python's probes, in kept coordinates
+    auto bisect_kept = [&](int n_kept_) {
+        int a = 0, b = n_kept_;
+        while (a < b) {
+            const int mid = (a + b) / 2;
+            if (list_ts[left + kept_at(mid)] < t0)
+                a = mid + 1;
+            else
+                b = mid;
+        }
+        return a;
+    };
 
     // pass 1: how many are kept, the means, model_quality
     int n_kept = 0;
@@ -293,8 +336,10 @@ __global__ __launch_bounds__(kBlock) void k_estimate(
     for (int i = lane; i < n_window; i += kWave)
         if (kept(i)) {
             ++n_kept;
-            sum_x += abscissa(i);
-            sum_y += w_soa0[i];
+            if constexpr (kFit) {
+                sum_x += abscissa(i);
+                sum_y += w_soa0[i];
+            }
             sum_q0 += w_q0[i];
             sum_q1 += w_q1[i];
         }
@@ -303,11 +348,64 @@ __global__ __launch_bounds__(kBlock) void k_estimate(
         if (out_n_window) out_n_window[task] = n_window;
         if (out_n_kept) out_n_kept[task] = n_kept;
     }
-    bool good = n_kept >= M;
+    bool good = n_kept >= kMinKept;
     double tdoa = 0.0, quality = 0.0;
-    if (good) {
+    int pick0 = -1, pick1 = -1;  // positions in the kept list: {idx, -1} (nearest), {low, high} (linear)
+    if constexpr (MODEL == THR_TDOA_NEAREST) {
+        if (good) {
+            quality = (wave_sum(sum_q0) / n_kept + wave_sum(sum_q1) / n_kept) / 2.0;
+            // the kept pair whose det0 timestamp is nearest to t0; a tie stays on the later one
+            int idx = bisect_kept(n_kept);
+            if (idx > 0) {
+                bool earlier = idx == n_kept;
+                if (!earlier)
+                    earlier = fabs(t0 - list_ts[left + kept_at(idx - 1)]) < fabs(t0 - list_ts[left + kept_at(idx)]);
+                if (earlier) --idx;
+            }
+            pick0 = idx;
+            const int i = kept_at(idx);
+            const double dsoa0 = soa[d0] - w_soa0[i], dsoa1 = soa[d1] - w_soa1[i];
+            tdoa = (dsoa0 - dsoa1 + beacon_sdoa(i)) / sample_rate;
+            good = !(fabs(tdoa) >= kMaxTdoa);
+        }
+    } else if constexpr (MODEL == THR_TDOA_LINEAR) {
+        if (good) {
+            quality = (wave_sum(sum_q0) / n_kept + wave_sum(sum_q1) / n_kept) / 2.0;
+            int high = bisect_kept(n_kept);
+            if (high == n_kept) high = n_kept - 1;
+            const int i_high = kept_at(high);
+            // down the kept list to the nearest pair of the same beacon: window positions, the dropped ones skipped
+            // (every lane reads the same position)
+            int low = high - 1, i_low = i_high - 1;
+            while (i_low >= 0 && !(kept(i_low) && w_beacon[i_low] == w_beacon[i_high])) {
+                if (kept(i_low)) --low;
+                --i_low;
+            }
+            if (i_low < 0) low = -1;
+            pick0 = low;
+            pick1 = high;
+            good = low >= 0 && w_soa0[i_high] != w_soa0[i_low];  // equal SoAs: the reference divides by zero
+            if (good) {
+                const double weight = (soa[d0] - w_soa0[i_low]) / (w_soa0[i_high] - w_soa0[i_low]);
+                const double tau = (w_soa1[i_low] * (1.0 - weight) + w_soa1[i_high] * weight) - soa[d1];
+                tdoa = (tau + beacon_sdoa(i_high)) / sample_rate;
+                good = !(fabs(tdoa) >= kMaxTdoa);
+            }
+        }
+    } else if (good) {
         const double mean_x = wave_sum(sum_x) / n_kept, mean_y = wave_sum(sum_y) / n_kept;
         quality = (wave_sum(sum_q0) / n_kept + wave_sum(sum_q1) / n_kept) / 2.0;
+        // the weighted fit: w = (sqrt(sqrt(1 / |soa0_i - soa0|) / max) + 2) / 3, numpy's float64 operations;
+        // a kept pair AT the task's soa0 has no finite weight: a failure (the reference appends a NaN row)
+        double raw_max = 0.0;
+        auto raw_weight = [&](int i) { return __dsqrt_rn(1.0 / fabs(w_soa0[i] - soa[d0])); };
+        auto weight = [&](int i) { return (__dsqrt_rn(raw_weight(i) / raw_max) + 2.0) / 3.0; };
+        if constexpr (kWeighted) {
+            for (int i = lane; i < n_window; i += kWave)
+                if (kept(i)) raw_max = fmax(raw_max, raw_weight(i));
+            raw_max = wave_max(raw_max);
+            good = raw_max < INFINITY;
+        }
         // pass 2: the scale, and DEG + 1 distinct abscissae (the smallest, the next larger one, ...)
         double below = -INFINITY, scale = 0.0;
         for (int k = 0; k < M && good; ++k) {
@@ -334,6 +432,10 @@ __global__ __launch_bounds__(kBlock) void k_estimate(
                 if (kept(i)) {
                     const double u = (abscissa(i) - mean_x) / scale, v = w_soa0[i] - mean_y;
                     double p = 1.0;
+                    if constexpr (kWeighted) {  // the moments carry w^2
+                        const double wi = weight(i);
+                        p = wi * wi;
+                    }
 #pragma unroll
                     for (int k = 0; k <= 2 * DEG; ++k) {
                         s[k] += p;
@@ -395,6 +497,10 @@ __global__ __launch_bounds__(kBlock) void k_estimate(
         out_val[3 * size_t(task)] = tdoa;
         out_val[3 * size_t(task) + 1] = (q[d0] + q[d1]) / 2.0;
         out_val[3 * size_t(task) + 2] = quality;
+        if (out_pick) {
+            out_pick[2 * size_t(task)] = pick0;
+            out_pick[2 * size_t(task) + 1] = pick1;
+        }
     }
 }
 
@@ -468,7 +574,7 @@ thread_local double g_times_ms[3] = {0, 0, 0};  // last thr_tdoa of this thread:
 int thr::tdoa_core(int n, const int* d_rx, const double* d_ts, const double* d_soa, const double* d_en,
                    const double* d_no, int nm, const long long* d_ptr, const long long* d_idx, const int* d_beacon,
                    int n_rx, int n_beacons, const double* d_dist, double window, double sample_rate, int deg,
-                   long long n_tasks, long long n_pairs, hipStream_t s, TdoaOut& out) {
+                   int model, long long n_tasks, long long n_pairs, hipStream_t s, TdoaOut& out, DevBuf* picks) {
     const int n_keys = n_rx * n_rx;
     const dim3 blk(kBlock);
 
@@ -555,18 +661,34 @@ int thr::tdoa_core(int n, const int* d_rx, const double* d_ts, const double* d_s
     T_TRY(out.n_kept.alloc(size_t(nt) * 4));
     T_TRY(hipMemsetAsync(d_ok.p, 0, (size_t(nt) + 1) * 4, s));
     const dim3 est_grid(unsigned((nt + kWaves - 1) / kWaves));
-#define LAUNCH_ESTIMATE(DEG)                                                                                        \
-    hipLaunchKernelGGL(k_estimate<DEG>, est_grid, blk, 0, s, d_td0.as<int>(), d_td1.as<int>(), d_rx,        \
+    int* d_pick = nullptr;
+    if (picks) {
+        T_TRY(picks->alloc(size_t(nt) * 8));
+        d_pick = picks->as<int>();
+    }
+#define LAUNCH_ESTIMATE(DEG, MODEL)                                                                                 \
+    hipLaunchKernelGGL((k_estimate<DEG, MODEL>), est_grid, blk, 0, s, d_td0.as<int>(), d_td1.as<int>(), d_rx,       \
                        d_ts, d_soa, d_q.as<double>(), d_bucket.as<unsigned>(), n_rx,        \
                        n_beacons, d_bts.as<double>(), d_bs0.as<double>(), d_bs1.as<double>(), d_bq0.as<double>(),     \
                        d_bq1.as<double>(), d_bb.as<int>(), d_dist, window, sample_rate, nt,              \
-                       d_ok.as<unsigned>(), d_val.as<double>(), out.n_window.as<int>(), out.n_kept.as<int>())
-    if (deg == 1)
-        LAUNCH_ESTIMATE(1);
+                       d_ok.as<unsigned>(), d_val.as<double>(), out.n_window.as<int>(), out.n_kept.as<int>(), d_pick)
+    if (model == THR_TDOA_NEAREST)
+        LAUNCH_ESTIMATE(1, THR_TDOA_NEAREST);  // (the degree is not read)
+    else if (model == THR_TDOA_LINEAR)
+        LAUNCH_ESTIMATE(1, THR_TDOA_LINEAR);
+    else if (model == THR_TDOA_WEIGHTED_POLY) {
+        if (deg == 1)
+            LAUNCH_ESTIMATE(1, THR_TDOA_WEIGHTED_POLY);
+        else if (deg == 2)
+            LAUNCH_ESTIMATE(2, THR_TDOA_WEIGHTED_POLY);
+        else
+            LAUNCH_ESTIMATE(3, THR_TDOA_WEIGHTED_POLY);
+    } else if (deg == 1)
+        LAUNCH_ESTIMATE(1, THR_TDOA_POLY);
     else if (deg == 2)
-        LAUNCH_ESTIMATE(2);
+        LAUNCH_ESTIMATE(2, THR_TDOA_POLY);
     else
-        LAUNCH_ESTIMATE(3);
+        LAUNCH_ESTIMATE(3, THR_TDOA_POLY);
 #undef LAUNCH_ESTIMATE
     T_TRY(hipGetLastError());
 
@@ -611,20 +733,24 @@ int thr::tdoa_core(int n, const int* d_rx, const double* d_ts, const double* d_s
     return THR_OK;
 }
 
-extern "C" int thr_tdoa(int device_id, size_t n_det, const int32_t* rx, const double* timestamp, const double* soa,
-                        const double* energy, const double* noise, size_t n_matches, const int64_t* match_ptr,
-                        const int64_t* match_idx, const int32_t* match_beacon, int n_rx, int n_beacons,
-                        const double* dist, double window, double sample_rate, int deg, size_t n_tasks,
-                        int32_t* row_rx_out, int64_t* row_det_out, double* row_val_out, size_t* n_rows_out,
-                        int64_t* group_id_out, int64_t* group_ptr_out, size_t* n_groups_out, int64_t* fail_out,
-                        size_t* n_fail_out, int32_t* n_window_out, int32_t* n_kept_out) try {
+extern "C" int thr_tdoa_model(int device_id, size_t n_det, const int32_t* rx, const double* timestamp,
+                              const double* soa, const double* energy, const double* noise, size_t n_matches,
+                              const int64_t* match_ptr, const int64_t* match_idx, const int32_t* match_beacon, int n_rx,
+                              int n_beacons, const double* dist, double window, double sample_rate, int deg,
+                              size_t n_tasks, int32_t* row_rx_out, int64_t* row_det_out, double* row_val_out,
+                              size_t* n_rows_out, int64_t* group_id_out, int64_t* group_ptr_out, size_t* n_groups_out,
+                              int64_t* fail_out, size_t* n_fail_out, int32_t* n_window_out, int32_t* n_kept_out,
+                              int model, int32_t* pick_out) try {
     if (n_rows_out) *n_rows_out = 0;
     if (n_groups_out) *n_groups_out = 0;
     if (n_fail_out) *n_fail_out = 0;
     g_times_ms[0] = g_times_ms[1] = g_times_ms[2] = 0;
     if (!n_rows_out || !n_groups_out || !n_fail_out || !group_ptr_out || !match_ptr)
         return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: null argument");
-    if (deg < 1 || deg > 3) return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: deg must be 1, 2 or 3, not %d", deg);
+    if (model < THR_TDOA_POLY || model > THR_TDOA_LINEAR)
+        return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: model must be THR_TDOA_POLY (0) to THR_TDOA_LINEAR (3), not %d", model);
+    const bool fits = model == THR_TDOA_POLY || model == THR_TDOA_WEIGHTED_POLY;
+    if (fits && (deg < 1 || deg > 3)) return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: deg must be 1, 2 or 3, not %d", deg);
     if (n_rx < 1 || n_rx > kMaxReceivers)
         return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: 1 to %d receivers, not %d", kMaxReceivers, n_rx);
     if (n_beacons < 0 || (n_beacons > 0 && !dist)) return thr::fail_msg(THR_ERR_ARG, "thr_tdoa: bad beacon table");
@@ -700,10 +826,11 @@ extern "C" int thr_tdoa(int device_id, size_t n_det, const int32_t* rx, const do
     T_TRY(hipEventRecord(ev[1].e, s));
 
     thr::TdoaOut out;
+    DevBuf d_pick;
     const int rc = thr::tdoa_core(n, d_rx.as<int>(), d_ts.as<double>(), d_soa.as<double>(), d_en.as<double>(),
                                   d_no.as<double>(), nm, d_ptr.as<long long>(), d_idx.as<long long>(), d_beacon.as<int>(),
-                                  n_rx, n_beacons, d_dist.as<double>(), window, sample_rate, deg, (long long)n_tasks,
-                                  (long long)total_pairs, s, out);
+                                  n_rx, n_beacons, d_dist.as<double>(), window, sample_rate, deg, model,
+                                  (long long)n_tasks, (long long)total_pairs, s, out, pick_out ? &d_pick : nullptr);
     if (rc != THR_OK) return rc;
     const size_t n_rows = out.n_rows, n_fail = out.n_fail, n_groups = out.n_groups;
     T_TRY(hipEventRecord(ev[2].e, s));
@@ -717,6 +844,7 @@ extern "C" int thr_tdoa(int device_id, size_t n_det, const int32_t* rx, const do
     group_ptr_out[n_groups] = int64_t(n_rows);
     if (n_window_out) T_TRY(hipMemcpy(n_window_out, out.n_window.p, size_t(nt) * 4, hipMemcpyDeviceToHost));
     if (n_kept_out) T_TRY(hipMemcpy(n_kept_out, out.n_kept.p, size_t(nt) * 4, hipMemcpyDeviceToHost));
+    if (pick_out) T_TRY(hipMemcpy(pick_out, d_pick.p, size_t(nt) * 8, hipMemcpyDeviceToHost));
     T_TRY(hipEventRecord(ev[3].e, s));
     T_TRY(hipEventSynchronize(ev[3].e));
     for (int k = 0; k < 3; ++k) {
@@ -728,6 +856,21 @@ extern "C" int thr_tdoa(int device_id, size_t n_det, const int32_t* rx, const do
     *n_groups_out = n_groups;
     *n_fail_out = n_fail;
     return THR_OK;
+} catch (...) {
+    return thr::on_exception("thr_tdoa_model");
+}
+
+extern "C" int thr_tdoa(int device_id, size_t n_det, const int32_t* rx, const double* timestamp, const double* soa,
+                        const double* energy, const double* noise, size_t n_matches, const int64_t* match_ptr,
+                        const int64_t* match_idx, const int32_t* match_beacon, int n_rx, int n_beacons,
+                        const double* dist, double window, double sample_rate, int deg, size_t n_tasks,
+                        int32_t* row_rx_out, int64_t* row_det_out, double* row_val_out, size_t* n_rows_out,
+                        int64_t* group_id_out, int64_t* group_ptr_out, size_t* n_groups_out, int64_t* fail_out,
+                        size_t* n_fail_out, int32_t* n_window_out, int32_t* n_kept_out) try {
+    return thr_tdoa_model(device_id, n_det, rx, timestamp, soa, energy, noise, n_matches, match_ptr, match_idx,
+                          match_beacon, n_rx, n_beacons, dist, window, sample_rate, deg, n_tasks, row_rx_out, row_det_out,
+                          row_val_out, n_rows_out, group_id_out, group_ptr_out, n_groups_out, fail_out, n_fail_out,
+                          n_window_out, n_kept_out, THR_TDOA_POLY, nullptr);
 } catch (...) {
     return thr::on_exception("thr_tdoa");
 }

@@ -15,7 +15,11 @@ With any stage replaced, the given callables are chained the way the reference c
 
 `locate` (this module's command line, `python -m thrifty_amd.cli locate`) writes data.toads, data.match,
 data.tdoa and data.pos from one fused call; the four files are byte-identical to running `identify`,
-`match`, `tdoa` and `pos` in turn.
+`match`, `tdoa` and `pos` in turn (`--tdoa-model M` against `tdoa --model M`).
+
+The TDOA stage's clock model (tdoa_est.build_model_*) is `postdetect_columns`' `tdoa_model=`; `postdetect`
+takes it the reference's way, `tdoa_estimator=patch_module(tdoa_est.estimate_tdoas, model_builder=...)`,
+which is recognised and stays one device call.
 
 Deviation from the reference: the fused path needs the receivers of every match in `rx_pos` (KeyError
 otherwise, as `tdoa_est.estimate_tdoas` raises it) and at most 64 receivers (`pos_est`'s limit).
@@ -46,8 +50,10 @@ def _default_detector(*args, **kwargs):
 
 def patch_module(module, **override):
     """`module` with some of its keyword arguments fixed: the returned callable passes its own
-    arguments on, with `override` laid over the keywords."""
-    return lambda *args, **kwargs: module(*args, **dict(kwargs, **override))
+    arguments on, with `override` laid over the keywords (and says what it wraps: `.module`, `.override`)."""
+    patched = lambda *args, **kwargs: module(*args, **dict(kwargs, **override))  # noqa: E731
+    patched.module, patched.override = module, override
+    return patched
 
 
 def _detections_of(rxid, name, settings, detector):
@@ -65,8 +71,9 @@ def detect_all(cards, settings, detector=_default_detector):
     return [result for rxid, name in cards.items() for result in _detections_of(rxid, name, settings, detector)]
 
 
-def _native_settings(settings, min_match, deg, x0, max_iter, tdoa_as_text):
+def _native_settings(settings, min_match, deg, x0, max_iter, tdoa_as_text, tdoa_model="poly"):
     """PostdetectSettings -> (_native.post_settings pair, receiver ids ascending)."""
+    tdoa_model = tdoa_est._model(tdoa_model)
     rx_pos = {rx: np.asarray(p, dtype=np.float64) for rx, p in settings.rx_pos.items()}
     beacon_pos = {tx: np.asarray(p, dtype=np.float64) for tx, p in settings.beacon_pos.items()}
     ids, table = pos_est._receiver_table(rx_pos)          # insertion order; ValueError for what no solver takes
@@ -79,19 +86,21 @@ def _native_settings(settings, min_match, deg, x0, max_iter, tdoa_as_text):
                     dtype=np.float64).reshape(len(rx_ids), len(beacons))
     native = _native.post_settings(identify._flatten(settings.tx_freqs), settings.match_window, min_match, rx_ids,
                                    table[order], first_two, beacons, dist, settings.tdoa_est_window,
-                                   settings.sample_rate, deg, x0, max_iter, tdoa_as_text)
+                                   settings.sample_rate, deg, x0, max_iter, tdoa_as_text,
+                                   tdoa_model.code)
     return native, rx_ids
 
 
 def postdetect_columns(cols, settings, device_id=0, min_match=2, deg=2, x0=(0.1, 0.1), max_iter=100,
-                       tdoa_as_text=False):
+                       tdoa_as_text=False, tdoa_model="poly"):
     """The whole chain on the raw detection columns of all receivers (COLUMNS) in one device call ->
     dict: `txid` / `keep` per input detection and `kept_order` (identify.integrate_columns); `match_ptr`,
     `match_idx`, `misses`, `collisions` (matchmaker.match_columns, indices into the kept order);
     `tdoas`, `group_id`, `group_ptr`, `timestamp`, `tx`, `failures`, `n_window`, `n_kept`
     (tdoa_est.tdoa_columns); `pos`, `dop`, `snr`, `status`, `iters` over ALL groups (pos_est.pos_columns);
-    `counts`.  KeyError for a receiver of a match that `settings.rx_pos` lacks."""
-    native, rx_ids = _native_settings(settings, min_match, deg, x0, max_iter, tdoa_as_text)
+    `counts`.  `tdoa_model`: a tdoa_est selector or its name (tdoa_columns' `model`).  KeyError for a
+    receiver of a match that `settings.rx_pos` lacks."""
+    native, rx_ids = _native_settings(settings, min_match, deg, x0, max_iter, tdoa_as_text, tdoa_model)
     try:
         counts, out = _native.postdetect(*[cols[name] for name in COLUMNS], settings=native, device_id=device_id)
     except ValueError as err:
@@ -150,13 +159,28 @@ def _fused(toad, settings, **options):
                             tdoas=tdoa_est._groups(res), pos=_positions(res, dims)), res
 
 
+def _fused_tdoa_options(tdoa_estimator):
+    """The fused call's options if `tdoa_estimator` is tdoa_est.estimate_tdoas, or patch_module() of it that
+    fixes nothing but the model (`model_builder`, `model_params`, `deg`); None for any other estimator."""
+    if tdoa_estimator is tdoa_est.estimate_tdoas:
+        return {}
+    fixed = getattr(tdoa_estimator, "override", None)
+    if getattr(tdoa_estimator, "module", None) is not tdoa_est.estimate_tdoas or not set(fixed) <= {
+            "model_builder", "model_params", "deg"}:
+        return None
+    model, deg = tdoa_est._model_and_degree(fixed.get("model_builder"), fixed.get("model_params"), fixed.get("deg", 2))
+    return {"tdoa_model": model, "deg": deg}
+
+
 def postdetect(toad, settings, integrator=identify.integrate, matcher=matchmaker.match_toads,
                tdoa_estimator=tdoa_est.estimate_tdoas, pos_estimator=pos_est.solve):
     """Identify, match, estimate TDOAs, estimate positions -> PostdetectResult.  `.txid` of the detections
-    is set in place."""
-    stages = (integrator, matcher, tdoa_estimator, pos_estimator)
-    if stages == (identify.integrate, matchmaker.match_toads, tdoa_est.estimate_tdoas, pos_est.solve):
-        return _fused(list(toad), settings)[0]
+    is set in place.  Another TDOA model is chosen the reference's way and stays ONE device call:
+    `tdoa_estimator=patch_module(tdoa_est.estimate_tdoas, model_builder=tdoa_est.build_model_nearest)`."""
+    fused = _fused_tdoa_options(tdoa_estimator)
+    if fused is not None and (integrator, matcher, pos_estimator) == (identify.integrate, matchmaker.match_toads,
+                                                                      pos_est.solve):
+        return _fused(list(toad), settings, **fused)[0]
     as_arrays = lambda table: {key: np.array(value) for key, value in table.items()}  # noqa: E731
     rx_pos = as_arrays(settings.rx_pos)
     logging.info(" * Integrate")
@@ -188,6 +212,8 @@ _CLI = (
                                    "unit transmission for the former to be used for the latter's TDOA")),
     (("-s", "--sample-rate"), dict(dest="sample_rate", type=float, default=2.4e6,
                                    help="nominal sample rate of receivers")),
+    (("--tdoa-model",), dict(dest="tdoa_model", choices=("poly", "weighted_poly", "nearest", "linear"),
+                             default="poly", help="clock model of the TDOA stage [default: poly]")),
     (("--prefix",), dict(default="data", help="the outputs are PREFIX.toads, .match, .tdoa and .pos [default: data]")),
 )
 
@@ -214,7 +240,8 @@ def _main(argv=None):
     settings = PostdetectSettings(tx_freqs=freqmap, match_window=args.window, tdoa_est_window=args.tdoa_window,
                                   rx_pos=rx_pos, beacon_pos=beacon_pos, sample_rate=args.sample_rate)
     # (tdoa_as_text: `pos` reads its TDOAs from the .tdoa text, nanoseconds; so does the fused call)
-    result, res = _fused(detections, settings, min_match=args.num_matches, tdoa_as_text=True)
+    result, res = _fused(detections, settings, min_match=args.num_matches, tdoa_as_text=True,
+                         tdoa_model=args.tdoa_model)
     with open(args.prefix + ".toads", "w") as out:
         out.write("".join(["# source_files: [%s]\n" % " ".join(filenames)] + [d.serialize() + "\n" for d in result.toads]))
     with open(args.prefix + ".match", "w") as out:

@@ -2,11 +2,18 @@
 """
 Estimate TDOA values of mobile unit transmissions from SOA values.
 
-GPU counterpart of reference thrifty/tdoa_est.py (its default model, `build_model_poly`): beacon
-transmissions synchronise the SoA values of different receivers, and the TDOA of every pair of
-detections of a mobile transmission is read off a polynomial fitted to the beacon detections around it.
-The pair lists, the windows, the outlier mask, the fit and the output orders run on the device
-(`thr_tdoa`, csrc/tdoa.hip); this module keeps the reference's names and the `.tdoa` text format.
+GPU counterpart of reference thrifty/tdoa_est.py: beacon transmissions synchronise the SoA values of
+different receivers, and the TDOA of every pair of detections of a mobile transmission is read off a
+model of the two receivers' clocks built from the beacon detections around it -- a fitted polynomial
+(the default), a weighted one, the nearest beacon transmission, or the line through two of one beacon.
+The pair lists, the windows, the outlier mask, the model and the output orders run on the device
+(`thr_tdoa_model`, csrc/tdoa.hip); this module keeps the reference's names and the `.tdoa` text format.
+
+The four models are chosen the way the reference's callers choose them, `estimate_tdoas(...,
+model_builder=build_model_nearest)`, but `build_model_*` here are SELECTORS of a device model, not
+functions: a host callable cannot run inside the device call.  `nearest` and `linear` reproduce the
+reference's float64 operations in its order, so their TDOAs are its bits; they need one and two kept
+beacon pairs in the window where the polynomial needs `deg + 1`.
 
 What is reproduced, quirks included: the per-receiver-pair beacon lists stay in match order (the
 reference's `sort(cmp=...)` never reorders), the window is Python's bisection on that list whether it
@@ -20,6 +27,9 @@ Deviations from the reference:
   reference dies with KeyError);
 * kept abscissae with fewer than `deg + 1` distinct values are a failure (the reference returns
   LAPACK's minimum-norm solution with a RankWarning);
+* `linear`: two chosen beacon pairs with the same det0 SoA are a failure (the reference dies with
+  ZeroDivisionError); `weighted_poly`: a kept beacon pair whose det0 SoA equals the mobile det0's is a
+  failure (the reference's weights turn inf / NaN and it appends a NaN row);
 * a match with two detections of one receiver raises ValueError before anything is launched (the
   reference hits `assert rxid0 < rxid1`); so does an empty match.  A receiver of any match that
   `rx_pos` lacks raises KeyError up front (the reference raises it when it first needs the position).
@@ -59,6 +69,41 @@ MATRIX_DTYPE = {"names": ("group_id", "timestamp", "tx") + TDOA_DTYPE["names"],
                 "formats": ("i4", "f8", "i4") + TDOA_DTYPE["formats"]}
 
 
+class DeviceModel(object):
+    """Selects one of the TDOA models of `thr_tdoa_model`; stands where the reference has a model builder."""
+
+    def __init__(self, name, code, takes_deg):
+        self.name, self.code, self.takes_deg = name, code, takes_deg
+
+    def __call__(self, *args, **kwargs):
+        raise NotImplementedError(
+            "'%s' runs inside the device call thr_tdoa_model; pass it as estimate_tdoas(..., model_builder=...) "
+            "or tdoa_columns(..., model=...) instead of calling it" % self.name)
+
+    def __repr__(self):
+        return "<device tdoa model %r>" % self.name
+
+
+build_model_poly = DeviceModel("poly", _native.TDOA_MODELS["poly"], True)
+build_model_weighted_poly = DeviceModel("weighted_poly", _native.TDOA_MODELS["weighted_poly"], True)
+build_model_nearest = DeviceModel("nearest", _native.TDOA_MODELS["nearest"], False)
+build_model_linear = DeviceModel("linear", _native.TDOA_MODELS["linear"], False)
+default_model = build_model_poly
+MODELS = {sel.name: sel for sel in (build_model_poly, build_model_weighted_poly, build_model_nearest,
+                                    build_model_linear)}
+
+
+def _model(model):
+    """A selector, or one of the names of MODELS -> the selector."""
+    if isinstance(model, DeviceModel):
+        return model
+    if isinstance(model, str) and model in MODELS:
+        return MODELS[model]
+    raise TypeError("the TDOA model must be one of tdoa_est.build_model_poly, build_model_weighted_poly, "
+                    "build_model_nearest, build_model_linear (or their names %s), not %r: host callables cannot "
+                    "run inside the device call" % (", ".join(sorted(MODELS)), model))
+
+
 def _columns(detections):
     n = len(detections)
     cols = {"rxid": np.empty(n, np.int32), "txid": np.empty(n, np.int32)}
@@ -78,12 +123,17 @@ def _distance(a, b):
     return np.sqrt(np.sum(delta ** 2))
 
 
-def tdoa_columns(cols, match_ptr, match_idx, window_size, beacon_pos, rx_pos, sample_rate, deg=2, device_id=0):
+def tdoa_columns(cols, match_ptr, match_idx, window_size, beacon_pos, rx_pos, sample_rate, deg=2, device_id=0,
+                 model="poly"):
     """TDOAs for detection columns (rxid, txid, timestamp, soa, energy, noise) and matches in CSR form
     (match m is match_idx[match_ptr[m]:match_ptr[m + 1]]) -> dict: `tdoas` (all rows, TDOA_DTYPE, in
     order), `group_id` / `group_ptr` / `timestamp` / `tx` per group (group g holds rows
     group_ptr[g]:group_ptr[g + 1]), `failures` int64[f, 2], and per detection pair of the mobile
-    matches, in order, `n_window` (beacon pairs in its window) and `n_kept` (those the outlier mask kept)."""
+    matches, in order, `n_window` (beacon pairs in its window), `n_kept` (those the outlier mask kept) and
+    `picks` int32[n, 2]: what `model` chose, as positions among the kept pairs -- (idx, -1) for `nearest`,
+    (low, high) for `linear` (low == -1: no earlier pair of the same beacon), (-1, -1) otherwise.
+    `model`: a selector (build_model_*) or its name; `deg` is read by the two polynomials only."""
+    model = _model(model)
     ptr, idx = np.asarray(match_ptr, dtype=np.int64), np.asarray(match_idx, dtype=np.int64)
     rxid, txid = np.asarray(cols["rxid"]), np.asarray(cols["txid"])
     if len(ptr) < 1 or ptr[0] != 0 or ptr[-1] != len(idx) or np.any(np.diff(ptr) < 1):
@@ -103,7 +153,8 @@ def tdoa_columns(cols, match_ptr, match_idx, window_size, beacon_pos, rx_pos, sa
                     dtype=np.float64).reshape(len(receivers), len(beacons))
     dense = np.clip(np.searchsorted(receivers, rxid), 0, max(len(receivers) - 1, 0)).astype(np.int32)
     out = _native.tdoa(dense, cols["timestamp"], cols["soa"], cols["energy"], cols["noise"], ptr, idx, match_beacon,
-                       dist if len(receivers) else np.zeros((1, len(beacons))), window_size, sample_rate, deg, device_id)
+                       dist if len(receivers) else np.zeros((1, len(beacons))), window_size, sample_rate, deg, device_id,
+                       model.code)
     rows = np.zeros(len(out["tdoa"]), dtype=TDOA_DTYPE)
     if len(rows):
         rows["rx0"], rows["rx1"] = receivers[out["row_rx"][:, 0]], receivers[out["row_rx"][:, 1]]
@@ -116,7 +167,7 @@ def tdoa_columns(cols, match_ptr, match_idx, window_size, beacon_pos, rx_pos, sa
     return {"tdoas": rows, "group_id": gid, "group_ptr": out["group_ptr"],
             "timestamp": np.asarray(cols["timestamp"], dtype=np.float64)[idx[ptr[gid]]],
             "tx": txid[np.where(rxid[last_a] <= rxid[last_b], last_a, last_b)],
-            "failures": out["failures"], "n_window": out["n_window"], "n_kept": out["n_kept"]}
+            "failures": out["failures"], "n_window": out["n_window"], "n_kept": out["n_kept"], "picks": out["picks"]}
 
 
 def _groups(res):
@@ -126,13 +177,28 @@ def _groups(res):
                                       ptr[:-1], ptr[1:])]
 
 
-def estimate_tdoas(detections, matches, window_size, beacon_pos, rx_pos, sample_rate, deg=2):
+def _model_and_degree(model_builder, model_params, deg):
+    """estimate_tdoas' model arguments -> (selector, degree); TypeError for what the reference's
+    `model_builder(..., **model_params)` would refuse, and for a builder that is not a selector."""
+    model = _model(default_model if model_builder is None else model_builder)
+    params = dict(model_params or {})
+    if model.takes_deg:
+        deg = params.pop("deg", deg)
+    if params:
+        raise TypeError("build_model_%s() got an unexpected keyword argument %r" % (model.name, sorted(params)[0]))
+    return model, deg
+
+
+def estimate_tdoas(detections, matches, window_size, beacon_pos, rx_pos, sample_rate, deg=2, model_builder=None,
+                   model_params=None):
     """(tdoa_groups, failures): one TdoaGroup per mobile match with at least one TDOA (`tdoas` is a
     TDOA_DTYPE array in combination order) and the (det0_idx, det1_idx) pairs no TDOA could be
-    estimated for, in the order they occurred."""
+    estimated for, in the order they occurred.  `model_builder`: one of this module's build_model_*
+    selectors (None: default_model); `model_params`: {"deg": d} for the two polynomials, overriding `deg`."""
+    model, deg = _model_and_degree(model_builder, model_params, deg)
     ptr = np.cumsum([0] + [len(m) for m in matches]).astype(np.int64)
     idx = np.array([i for m in matches for i in m], dtype=np.int64)
-    res = tdoa_columns(_columns(detections), ptr, idx, window_size, beacon_pos, rx_pos, sample_rate, deg)
+    res = tdoa_columns(_columns(detections), ptr, idx, window_size, beacon_pos, rx_pos, sample_rate, deg, model=model)
     return _groups(res), [tuple(pair) for pair in res["failures"].tolist()]
 
 
@@ -207,6 +273,9 @@ _CLI = (
                                         "estimating the TDOA of the mobile unit transmission")),
     (("-s", "--sample-rate"), dict(dest="sample_rate", type=float, default=2.4e6,
                                    help="nominal sample rate of receivers")),
+    (("--model",), dict(dest="model", choices=("poly", "weighted_poly", "nearest", "linear"), default="poly",
+                        help="clock model built from the beacon transmissions in the window [default: poly]")),
+    (("--deg",), dict(dest="deg", type=int, default=2, help="degree of the two polynomial models (1..3)")),
 )
 
 
@@ -224,7 +293,8 @@ def _main(argv=None):
         matches = matchmaker.load_matches(args.matches)
         rx_pos = load_pos_config(args.rx_pos)
         beacon_pos = load_pos_config(args.beacon_pos)
-        tdoa_groups, failures = estimate_tdoas(toads, matches, args.window_size, beacon_pos, rx_pos, args.sample_rate)
+        tdoa_groups, failures = estimate_tdoas(toads, matches, args.window_size, beacon_pos, rx_pos, args.sample_rate,
+                                               deg=args.deg, model_builder=MODELS[args.model])
         print("Number of TDOA estimations:", len(tdoa_groups))
         print("Number of TDOA estimation failures:", len(failures))
         save_tdoa_groups(args.output, tdoa_groups)
