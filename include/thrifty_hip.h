@@ -72,6 +72,8 @@ extern "C" {
  *      thr_debug_survey_geometry -- capture survey: mean spectrum, byte histogram, per-block byte sums
  *    + thr_chipscan / thr_debug_chipscan_geometry / _budget / _times -- chip-rate scan: blocks x candidate
  *      template lengths (the reference's scripts/chip_rate_search.py as an exhaustive scan)
+ *    + thr_debug_chipscan_fill / _groups -- the scan's cut into groups of consecutive candidates: set the
+ *      workgroups a launch aims at, read the cut (records unchanged)
  *    + thr_toadstats / thr_tstats_fetch / thr_tstats_free / thr_debug_toadstats_times / _geometry -- the
  *      numbers of the reference's `thrifty analyze_toads` (toads_analysis.py): per (rxid, txid) statistics,
  *      histograms and the per-receiver timestamp line
@@ -869,6 +871,11 @@ int thr_debug_survey_geometry(const thr_survey* s, int* tile_blocks, int* workgr
  * (0: they do not).  thr_debug_chipscan_budget: the bank budget in bytes (0: the default, 64 MiB; tests
  * shrink it to meet the chunk seam with few candidates).  thr_debug_chipscan_times: device milliseconds
  * of the last call -- [0] carrier stage, fit and shift, [1] bank kernel, [2] scan and finish kernels.
+ * thr_debug_chipscan_fill: the workgroups a scan launch aims at (0: the default, twice the CUs); it moves
+ * the cut of a chunk's candidates into groups -- one workgroup walks a group -- and no result (tests make
+ * the groups long or short with few candidates).  thr_debug_chipscan_groups: the cut a launch of n_blocks
+ * blocks (one block chunk) x n_cand candidates (one bank chunk) would use -- groups per block, and candidates
+ * per group (the last group may be shorter).  Read-only; either pointer may be NULL.
  */
 typedef struct thr_chip_record {   /* out[block][candidate], 24 bytes */
     int32_t sample;    /* CorrDetectionInfo.sample, -1: block had no carrier */
@@ -883,6 +890,8 @@ int thr_chipscan(thr_handle* h, const void* samples, int format, size_t n_blocks
 int thr_debug_chipscan_geometry(thr_handle* h, size_t n_lengths, int* candidates_per_chunk, int* paired);
 int thr_debug_chipscan_budget(thr_handle* h, size_t bank_bytes);
 int thr_debug_chipscan_times(thr_handle* h, double* ms_out /* [3] */);
+int thr_debug_chipscan_fill(thr_handle* h, size_t workgroups);
+int thr_debug_chipscan_groups(thr_handle* h, size_t n_blocks, size_t n_cand, int* groups, int* per_group);
 
 /* The settings a handle was created with (`templates` is NULL: the array is not retained). */
 int thr_get_settings(const thr_handle* h, thr_settings* out);

@@ -16,7 +16,8 @@ from thrifty_amd.block_data import card_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "chipscan")
-SYMBOLS = ["thr_chipscan", "thr_debug_chipscan_geometry", "thr_debug_chipscan_budget", "thr_debug_chipscan_times"]
+SYMBOLS = ["thr_chipscan", "thr_debug_chipscan_geometry", "thr_debug_chipscan_budget", "thr_debug_chipscan_times",
+           "thr_debug_chipscan_fill", "thr_debug_chipscan_groups"]
 
 
 def test_thr_chipscan_is_declared_listed_and_built():
@@ -28,6 +29,11 @@ def test_thr_chipscan_is_declared_listed_and_built():
     assert re.search(r"\bint thr_chipscan\(thr_handle\* h, const void\* samples, int format, size_t n_blocks,", header)
     assert re.search(r"\bint thr_debug_chipscan_geometry\(thr_handle\* h, size_t n_lengths, int\* candidates_per_chunk, "
                      r"int\* paired\);", header)
+    assert re.search(r"\+ thr_debug_chipscan_fill / _groups", header)
+    assert re.search(r"\bint thr_debug_chipscan_fill\(thr_handle\* h, size_t workgroups\);", header)
+    assert re.search(r"\bint thr_debug_chipscan_groups\(thr_handle\* h, size_t n_blocks, size_t n_cand, int\* groups, "
+                     r"int\* per_group\);", header)
+    assert callable(_native.ChipScan.set_fill) and callable(_native.ChipScan.groups)
     for sym in SYMBOLS:
         assert re.search(r"\b%s\(" % sym, header) and sym in _native.EXPORTS
     assert _native.CHIP_RECORD_DTYPE.itemsize == 24 and callable(_native.ChipScan)
@@ -130,6 +136,32 @@ def test_best_length_scores_at_least_what_nelder_mead_found(golden):
     lo, hi = result.best_interval
     assert lo < result.best_rate <= hi
     assert chip_rate_search.nominal_length(result.sample_rate, result.best_rate, 1023) == 2461
+
+
+def test_the_seam_scenes_are_what_their_docstrings_say():
+    """the float64 figures that tests/test_gpu_chipscan_seams.py rests on (carrier_len 2455)"""
+    n = chipscan_ref.N
+
+    def restate(scene):
+        blocks, chips, lengths = scene()
+        ref = chipscan_ref.scan(blocks, chips, lengths, 2455)
+        ok = (ref["flags"] & 1) != 0
+        return lengths, ref, ok, int((ok & (ref["top2_gap"] < chipscan_ref.TIE)).sum())
+
+    lengths, ref, ok, ties = restate(chipscan_ref.lane_scene)
+    assert ok.all() and ok.size == 51 and ties == 1 and lengths[0] == 2461
+    assert ref["sample"][:, 0].tolist() == chipscan_ref.LANE_LAGS and np.all(ref["offset"][:, 0] != 0)
+    assert 1.05 <= ref["curvature"][:, 0].min() < 1.06 and max(chipscan_ref.LANE_LAGS) == n - 2461 - 1
+    lengths, ref, ok, ties = restate(chipscan_ref.mask_scene)
+    assert ok.all() and ties == 0 and ref["sample"][0].tolist() == [13923, 13922, 13919, 13914, 13108, 12881]
+    assert np.array_equal(ref["sample"][0, :4], n - lengths[:4]) and np.all(ref["offset"][0, :4] == 0)
+    assert ref["top2_gap"][0, :4].min() >= 0.14 and np.all(ref["offset"][0, 4:] != 0)
+    lengths, ref, ok, ties = restate(chipscan_ref.length_scene)
+    assert ok[:, 0].tolist() == [True] * 4 + [False] + [True] * 4 and ok.sum() == 104 and ties == 0
+    assert 4.6e-4 < ref["top2_gap"][ok].min() < 4.7e-4 and lengths[0] == 1 and lengths[-1] == n - 2
+    lengths, ref, ok, ties = restate(chipscan_ref.group_scene)
+    assert ok[:, 0].tolist() == [True] * 4 + [False] + [True] * 11 and ok.sum() == 1050 and ties == 4
+    assert len(lengths) == 70 and ties <= 0.05 * ok.sum()
 
 
 # ------------------------------------------------------------------ the staircase and its arithmetic

@@ -9,22 +9,12 @@ import numpy as np
 import pytest
 
 import chipscan_ref
+from chipscan_ref import REL, compare, engine, same     # (shared with test_gpu_chipscan_seams.py, unchanged)
 from thrifty_amd import _native, chip_rate_search
 
 pytestmark = pytest.mark.gpu
 
 N = 16384
-REL = 1e-4          # energy, noise
-OFFSET_ABS = 1e-3
-TIE = 1e-4          # top-2 gap below which the index is not compared
-CURVATURE = 1e-4    # |2 log b - log a - log c| below which the offset is not compared
-
-
-def engine(carrier_len, max_batch=16, block_len=N, **kw):
-    """an ordinary handle with the tuning tool's carrier setup; its own template is never used by the scan"""
-    own = np.where(np.arange(64) % 3 == 0, 1.0, -1.0)
-    return _native.Engine(block_len, 63, own, chipscan_ref.CARRIER_THRESH, None, (0.0, 0.0, 0.0),
-                          carrier_len=carrier_len, max_batch=max_batch, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -48,35 +38,6 @@ def refs():
         blocks = np.atleast_2d(blocks)
         out[name] = (blocks, chips, lengths, chipscan_ref.scan(blocks, chips, lengths, carrier_len))
     return out
-
-
-def compare(got, ref, what, max_excluded=0.05):
-    """the module docstring's comparison; returns the number of pairs the index comparison left out"""
-    assert got.shape == ref.shape
-    ok = (ref["flags"] & 1) != 0
-    assert np.array_equal((got["flags"] & 1) != 0, ok), what
-    quiet = got[~ok]
-    assert np.all(quiet["sample"] == -1) and np.all(quiet["flags"] == 0) and np.all(quiet["energy"] == 0), what
-    assert np.all(quiet["noise"] == 0) and np.all(quiet["offset"] == 0), what
-    tie = ok & (ref["top2_gap"] < TIE)
-    sure = ok & ~tie
-    e_dev = np.abs(got["energy"][ok] - ref["energy"][ok]) / ref["energy"][ok]
-    n_dev = np.abs(got["noise"][ok] - ref["noise"][ok]) / ref["noise"][ok]
-    smooth = sure & (ref["curvature"] > CURVATURE)
-    o_dev = np.abs(got["offset"][smooth] - ref["offset"][smooth])
-    print("%s: %d pairs, %d ties left out, energy %.2e noise %.2e offset %.2e (over %d)"
-          % (what, ok.sum(), tie.sum(), e_dev.max(initial=0), n_dev.max(initial=0), o_dev.max(initial=0), smooth.sum()))
-    assert tie.sum() <= max_excluded * max(1, ok.sum()), what
-    assert np.array_equal(got["sample"][sure], ref["sample"][sure]), what
-    assert np.array_equal(got["flags"][ok], ref["flags"][ok]), what
-    assert np.all(e_dev <= REL) and np.all(n_dev <= REL), what
-    assert np.all(o_dev <= OFFSET_ABS), what
-    assert np.all(got["offset"][sure & (ref["offset"] == 0)] == 0), what      # (the first and the last lag)
-    return int(tie.sum())
-
-
-def same(a, b):
-    return a.tobytes() == b.tobytes()
 
 
 # ------------------------------------------------------------------ scenes against the restatement

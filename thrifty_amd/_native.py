@@ -47,6 +47,7 @@ EXPORTS = [
     "thr_survey_create", "thr_survey_destroy", "thr_survey_reset", "thr_survey_shift", "thr_survey_pending",
     "thr_survey_feed", "thr_survey_feed_stream", "thr_debug_survey_geometry",
     "thr_chipscan", "thr_debug_chipscan_geometry", "thr_debug_chipscan_budget", "thr_debug_chipscan_times",
+    "thr_debug_chipscan_fill", "thr_debug_chipscan_groups",
     "thr_toadstats", "thr_tstats_fetch", "thr_tstats_free", "thr_debug_toadstats_times", "thr_debug_toadstats_geometry",
     "thr_beaconsync", "thr_bsync_fetch", "thr_bsync_free", "thr_debug_beaconsync_times", "thr_debug_beaconsync_geometry",
     "thr_tdoastats", "thr_tdstats_fetch", "thr_tdstats_free", "thr_debug_tdoastats_times", "thr_debug_tdoastats_geometry",
@@ -356,6 +357,8 @@ def load_library():
     lib.thr_debug_chipscan_geometry.argtypes = [vp, C.c_size_t, ip, ip]
     lib.thr_debug_chipscan_budget.argtypes = [vp, C.c_size_t]
     lib.thr_debug_chipscan_times.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.thr_debug_chipscan_fill.argtypes = [vp, C.c_size_t]
+    lib.thr_debug_chipscan_groups.argtypes = [vp, C.c_size_t, C.c_size_t, ip, ip]
     lib.thr_toadstats.argtypes = ([C.c_int, C.c_size_t] + [vp] * 11 +
                                   [vp, C.c_size_t, C.POINTER(vp), C.POINTER(ThrTstatsCounts)])
     lib.thr_tstats_fetch.argtypes = [vp, C.c_int, vp, C.c_size_t]
@@ -1474,6 +1477,17 @@ class ChipScan(object):
     def set_bank_budget(self, n_bytes):
         """thr_debug_chipscan_budget: bytes of template bank per chunk (0: the default)"""
         _check(self._lib, self._lib.thr_debug_chipscan_budget(self._eng._h, int(n_bytes)))
+
+    def set_fill(self, workgroups):
+        """thr_debug_chipscan_fill: workgroups a scan launch aims at (0: the default, twice the CUs)"""
+        _check(self._lib, self._lib.thr_debug_chipscan_fill(self._eng._h, int(workgroups)))
+
+    def groups(self, n_blocks, n_cand):
+        """thr_debug_chipscan_groups -> (groups per block, candidates per group) of one launch"""
+        groups, per = C.c_int(0), C.c_int(0)
+        _check(self._lib, self._lib.thr_debug_chipscan_groups(self._eng._h, int(n_blocks), int(n_cand),
+                                                              C.byref(groups), C.byref(per)))
+        return groups.value, per.value
 
     def times(self):
         """thr_debug_chipscan_times -> device ms of the last scan: (carrier stage, bank kernel, scan kernels)"""

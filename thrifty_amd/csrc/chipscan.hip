@@ -280,6 +280,20 @@ size_t chip_candidates_per_chunk(const thr_handle* h, size_t n_lengths) {
     return std::min(n_lengths, std::max<size_t>(1, budget / thr::kChipSpectrumBytes));
 }
 
+// How a launch of nb blocks x nk candidates of one chunk is cut: enough workgroups for every CU twice over
+// (or thr_debug_chipscan_fill's target), where the candidates allow; every group but the last walks per_group
+// candidates.  The cut moves no arithmetic: a pair's result does not depend on its place in a group.
+struct ChipGroups {
+    size_t groups, per_group;
+};
+ChipGroups chip_scan_groups(const thr_handle* h, size_t nb, size_t nk) {
+    const size_t fill = h->chip.fill ? h->chip.fill : 2 * size_t(h->n_cu);
+    size_t groups = std::min(nk, std::max<size_t>(1, (fill + nb - 1) / nb));
+    const size_t per_group = (nk + groups - 1) / groups;
+    groups = (nk + per_group - 1) / per_group;
+    return ChipGroups{groups, per_group};
+}
+
 // what a handle must be for the scan; `who` names the entry point in the message
 int chip_handle_ok(const thr_handle* h, const char* who) {
     if (thr_is_gate(h))
@@ -356,13 +370,10 @@ int chipscan_body(thr_handle* h, const void* samples, int format, size_t n_block
                 THR_TRY(timer.end(1));
                 bank_built = ck >= n_lengths;
             }
-            // enough workgroups for every CU twice over, where the candidates allow
-            size_t groups = std::min(nk, std::max<size_t>(1, (2 * size_t(h->n_cu) + nb - 1) / nb));
-            const size_t per_group = (nk + groups - 1) / groups;
-            groups = (nk + per_group - 1) / per_group;
+            const ChipGroups cut = chip_scan_groups(h, nb, nk);
             THR_TRY(timer.begin(2));
-            HIP_TRY(thr::launch_chip_scan(c.d_xhat, c.d_bank, c.d_len + k0, int(nk), int(nb), int(groups),
-                                          int(per_group), h->d_rec, int(T), h->d_tables,
+            HIP_TRY(thr::launch_chip_scan(c.d_xhat, c.d_bank, c.d_len + k0, int(nk), int(nb), int(cut.groups),
+                                          int(cut.per_group), h->d_rec, int(T), h->d_tables,
                                           static_cast<const float2*>(h->dev.gtw), c.d_stats, h->stream));
             HIP_TRY(thr::launch_chip_finish(int(nb), int(nk), int(n_lengths), int(k0), c.d_len + k0, c.d_stats,
                                             h->d_rec, int(T), h->d_corr_stats, c.d_out, h->stream));
@@ -431,6 +442,28 @@ int thr_debug_chipscan_budget(thr_handle* h, size_t bank_bytes) try {
     return THR_OK;
 } catch (...) {
     return thr::on_exception("thr_debug_chipscan_budget");
+}
+
+int thr_debug_chipscan_fill(thr_handle* h, size_t workgroups) try {
+    if (!h) return fail(THR_ERR_ARG, "thr_debug_chipscan_fill: null handle");
+    h->chip.fill = workgroups;
+    return THR_OK;
+} catch (...) {
+    return thr::on_exception("thr_debug_chipscan_fill");
+}
+
+int thr_debug_chipscan_groups(thr_handle* h, size_t n_blocks, size_t n_cand, int* groups, int* per_group) try {
+    if (!h) return fail(THR_ERR_ARG, "thr_debug_chipscan_groups: null handle");
+    THR_TRY(chip_handle_ok(h, "thr_debug_chipscan_groups"));
+    if (n_blocks < 1 || n_cand < 1)
+        return fail(THR_ERR_ARG, "thr_debug_chipscan_groups: needs at least one block and one candidate (got %zu, %zu)",
+                    n_blocks, n_cand);
+    const ChipGroups cut = chip_scan_groups(h, n_blocks, n_cand);
+    if (groups) *groups = int(cut.groups);
+    if (per_group) *per_group = int(cut.per_group);
+    return THR_OK;
+} catch (...) {
+    return thr::on_exception("thr_debug_chipscan_groups");
 }
 
 int thr_debug_chipscan_times(thr_handle* h, double* ms_out) try {

@@ -177,6 +177,7 @@ struct thr_handle {
         Dev<unsigned char> d_chips;     // [n_chips]
         Event ev[6];                    // carrier stage, bank kernel, scan + finish: begin and end
         size_t bank_budget = 0;         // thr_debug_chipscan_budget (0: thr::kChipBankBudget)
+        size_t fill = 0;                // thr_debug_chipscan_fill: workgroups per launch aimed at (0: 2 x CUs)
         double ms[3] = {};              // the last call's device time per stage (thr_debug_chipscan_times)
     } chip;
     // single-chunk staging of the test hooks (lazy)
