@@ -136,6 +136,52 @@ def numbers(block, block_idx, settings, timestamp=0.0):
     return bool(cs.detected), result, x, data
 
 
+def numbers_at(block, record, settings, fit=True):
+    """The `data` dict of `numbers()` at a GIVEN record: carrier bin and offset, correlation sample and offset
+    and both noise values are read from `record` (a mapping or a NumPy record with the fields carrier_bin,
+    carrier_offset, corr_sample, corr_offset, carrier_noise, corr_noise); no detector runs.  Everything else is
+    evaluated at that record's shift with the oracle's own functions.  Fed the oracle's record it returns what
+    `numbers()` returns.  `fit=False` leaves the Dirichlet fit out (NaN) where it is ill conditioned."""
+    block = np.asarray(block)
+    x = onp.iq_u8_to_c64(block) if block.dtype == np.uint8 else block.astype(np.complex64)
+    n, w = settings.block_len, settings.carrier_len
+    cbin, coff = int(record["carrier_bin"]), float(record["carrier_offset"])
+    sample, soff = int(record["corr_sample"]), float(record["corr_offset"])
+    cnoise, xnoise = float(record["carrier_noise"]), float(record["corr_noise"])
+    bank = onp.TemplateBank(np.asarray(settings.template), n, settings.history_len)
+    fft_mag = np.abs(np.fft.fft(x))
+    filtered = filtered_spectrum(fft_mag, n, w)
+    xhat = onp.shift_and_fft(x, -(np.int64(cbin) + coff))
+    corr = onp.despread(xhat, bank)
+    synced = compensate(x, -(cbin + coff))
+    synced_mag = np.abs(xhat)
+    corr_mag = np.abs(corr)
+    want_car, want_cor = bool(settings.carrier_thresh[2]), bool(settings.corr_thresh[2])
+    stds = dict(fft_std=np.std(fft_mag) if want_car else 0.0, synced_fft_std=np.std(synced_mag) if want_car else 0.0,
+                filtered_std=np.std(filtered) if want_car else 0.0, corr_std=np.std(corr_mag) if want_cor else 0.0)
+    fit_valid = 6 <= cbin <= n - 7
+    amp, off = onp.dirichlet_fit(fft_mag, cbin, n, w) if fit_valid and fit else (np.nan, np.nan)
+    start, moved = shifted_peak(corr, sample, soff)
+    shifted = np.zeros(PEAK_WINDOW)
+    shifted[:len(moved)] = moved
+    scalars = dict(rms_unsynced=float(np.sqrt(np.mean(np.abs(x.astype(np.complex128)) ** 2))),
+                   rms_synced=float(np.sqrt(np.mean(np.abs(synced) ** 2))),
+                   carrier_threshold=threshold(settings.carrier_thresh, cnoise, stds["fft_std"]),
+                   corr_threshold=threshold(settings.corr_thresh, xnoise, stds["corr_std"]),
+                   fit_amplitude=float(amp), fit_offset=float(off), fit_valid=int(fit_valid), peak_start=start,
+                   peak_len=len(moved), corr_shifted=shifted, **{k: float(v) for k, v in stds.items()})
+    hist = np.bincount(block, minlength=256) if block.dtype == np.uint8 else np.zeros(256, np.int64)
+    return dict(hist=hist, fft_mag=fft_mag, filtered=filtered, synced=synced, synced_fft_mag=synced_mag, corr=corr,
+                scalars=scalars, autocorr=autocorr(settings.template))
+
+
+def record_of(result):
+    """The record fields `numbers_at` reads, from the DetectionResult `numbers()` returns."""
+    c, x = result.carrier_info, result.corr_info
+    return dict(carrier_bin=c.bin, carrier_offset=c.offset, carrier_noise=c.noise, corr_sample=x.sample,
+                corr_offset=x.offset, corr_noise=x.noise)
+
+
 def dossier(block, block_idx, settings, sample_rate=SAMPLE_RATE, timestamp=0.0):
     """The package's Dossier over the oracle's float64 numbers (None if the block is not detected)."""
     from thrifty_amd.detect_analysis import Dossier

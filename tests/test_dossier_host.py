@@ -80,6 +80,50 @@ def test_compensated_samples_are_the_inverse_transform_of_the_shifted_spectrum()
     assert G.rel_l2(data["synced"], np.fft.ifft(onp.shift_and_fft(x, shift))) < 1e-12
 
 
+@pytest.mark.parametrize("name", ["small", "c2"])
+def test_the_statement_at_the_oracles_own_record_is_the_statement(name):
+    """numbers_at() runs no detector; fed the record numbers() found it must give numbers()'s data: arrays to
+    float64 round-off (1e-12 relative), integers and flags exactly."""
+    settings, ref = G.ref_numbers(name)
+    g = G.load_scene(name)
+    seen = 0
+    for block, (_, result, _, want) in zip(g["blocks"], ref):
+        if want is None:
+            continue
+        got = R.numbers_at(block, R.record_of(result), settings)
+        seen += 1
+        assert sorted(got) == sorted(want)
+        assert np.array_equal(got["hist"], want["hist"]) and np.array_equal(got["autocorr"], want["autocorr"])
+        for key in ("fft_mag", "filtered", "synced", "synced_fft_mag", "corr"):
+            assert got[key].shape == want[key].shape and got[key].dtype == want[key].dtype, key
+            assert np.array_equal(got[key], want[key]) or G.rel_l2(got[key], want[key]) <= 1e-12, key
+        gs, ws = got["scalars"], want["scalars"]
+        assert sorted(gs) == sorted(ws)
+        for key, w in ws.items():
+            if key in ("fit_valid", "peak_start", "peak_len"):
+                assert gs[key] == w and isinstance(gs[key], int), key
+            elif key == "corr_shifted":
+                assert np.array_equal(gs[key], w) or G.rel_l2(gs[key], w) <= 1e-12
+            else:
+                assert gs[key] == w or abs(gs[key] - w) <= 1e-12 * abs(w), key
+    assert seen == int(np.sum(g["carrier_det"]))
+
+
+def test_the_statement_at_a_record_follows_the_record():
+    """... and it is the record's numbers it uses, not a detector's: another bin, sample and noise move the fit's
+    validity, the peak window and the thresholds."""
+    g = G.load_scene("small")
+    settings = R.scene_settings(g)
+    _, result, _, want = R.numbers(g["blocks"][0], int(g["block_idx"][0]), settings)
+    rec = dict(R.record_of(result), carrier_bin=4, corr_sample=2, carrier_noise=2.0, corr_noise=3.0)
+    sc = R.numbers_at(g["blocks"][0], rec, settings)["scalars"]
+    assert sc["fit_valid"] == 0 and np.isnan(sc["fit_offset"]) and (sc["peak_start"], sc["peak_len"]) == (0, 8)
+    assert sc["carrier_threshold"] == np.sqrt(12 * 4.0) and sc["corr_threshold"] == np.sqrt(12 * 9.0)
+    assert sc["rms_unsynced"] == want["scalars"]["rms_unsynced"]
+    off = R.numbers_at(g["blocks"][0], R.record_of(result), settings, fit=False)["scalars"]
+    assert off["fit_valid"] == 1 and np.isnan(off["fit_amplitude"]) and np.isnan(off["fit_offset"])
+
+
 PICK_CASES = [      # scene c2: block_idx 5 + 3 i, blocks 53 56 59 62 not detected
     ("8-20,50-", 6, [8, 11, 14, 17, 20, 50], 6, 0),
     ("47-65", 20, [47, 50, 65], 7, 4),
