@@ -68,7 +68,9 @@ def run_and_check(cols, ptr, idx, deg=2, what="", **kw):
 def test_geometry_is_the_one_the_cases_were_sized_for():
     assert _native.syncstats_geometry("beaconsync") == (T, W) and _native.syncstats_geometry("tdoastats") == (T, W)
     source = open(os.path.join(build.CSRC, "syncstats.hip")).read()
-    assert "constexpr int kTile = %d;" % T in source and "constexpr int kBlock = %d;" % W in source
+    shared = open(os.path.join(build.CSRC, "seg_reduce.hpp")).read()      # the tile and the workgroup are the shared reduction's
+    assert '#include "seg_reduce.hpp"' in source
+    assert "constexpr int kTile = %d;" % T in shared and "constexpr int kBlock = %d;" % W in shared
     assert "constexpr int kMinCut = 8;" in source
 
 

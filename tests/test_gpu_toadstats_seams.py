@@ -53,8 +53,11 @@ def run_and_check(cols, sel=None, what=""):
 
 def test_geometry_is_the_one_the_cases_were_sized_for():
     assert _native.toadstats_geometry() == (T, W)
-    source = open(__import__("os").path.join(__import__("thrifty_amd.build").build.CSRC, "toadstats.hip")).read()
-    assert "constexpr int kTile = %d;" % T in source and "constexpr int kBlock = %d;" % W in source
+    csrc = __import__("thrifty_amd.build").build.CSRC
+    source = open(__import__("os").path.join(csrc, "toadstats.hip")).read()
+    shared = open(__import__("os").path.join(csrc, "seg_reduce.hpp")).read()      # the tile and the workgroup are the shared reduction's
+    assert '#include "seg_reduce.hpp"' in source
+    assert "constexpr int kTile = %d;" % T in shared and "constexpr int kBlock = %d;" % W in shared
 
 
 @pytest.mark.parametrize("n", sorted({1, 2, 63, 64, 65, W - 1, W + 1, T - 1, T, T + 1, 2 * T + 1}))

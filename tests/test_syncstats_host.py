@@ -39,6 +39,10 @@ def test_both_entry_points_are_declared_listed_and_built():
     source = open(os.path.join(build.CSRC, "syncstats.hip")).read()
     assert "#pragma clang fp contract(off)" in source and '#include "post_stages.hpp"' in source
     assert "atomic" not in source.split("#include", 1)[1] and "hipMalloc(" not in source     # partials in a fixed order
+    assert '#include "seg_reduce.hpp"' in source        # the reduction: the same properties hold of its text
+    shared = open(os.path.join(build.CSRC, "seg_reduce.hpp")).read()
+    assert "#pragma clang fp contract(off)" in shared and "atomic" not in shared.split("#include", 1)[1]
+    assert "hipMalloc(" not in shared and not re.search(r"\blog10\(", shared)
     assert "constexpr double kLight = 2.997e8;" in source and R.LIGHT == 2.997e8
 
 

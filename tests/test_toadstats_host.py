@@ -37,6 +37,10 @@ def test_thr_toadstats_is_declared_listed_and_built():
     assert "#pragma clang fp contract(off)" in source and '#include "post_stages.hpp"' in source
     assert len(re.findall(r"\blog10\(", source)) == 2 and "atomicAdd(&" in source
     assert not re.search(r"atomicAdd\([^;]*(double|float)", source) and "hipMalloc(" not in source
+    assert '#include "seg_reduce.hpp"' in source        # the reduction: the same properties hold of its text
+    shared = open(os.path.join(build.CSRC, "seg_reduce.hpp")).read()
+    assert "#pragma clang fp contract(off)" in shared and "atomic" not in shared.split("#include", 1)[1]
+    assert "hipMalloc(" not in shared and not re.search(r"\blog10\(", shared)
     assert "analyze_toads" not in cli.COMMANDS
 
 
@@ -57,6 +61,16 @@ def test_csrc_hash_is_the_recorded_one_and_does_not_see_toadstats(monkeypatch):
     monkeypatch.undo()
     monkeypatch.setattr(build, "UNPROFILED_TOADSTATS", ())
     assert build.csrc_hash() != with_stats
+
+
+def test_csrc_hash_does_not_see_the_shared_reduction(monkeypatch):
+    assert "seg_reduce.hpp" in build.HEADERS and build.UNPROFILED_SEGREDUCE == ("seg_reduce.hpp",)
+    with_header = build.csrc_hash()
+    monkeypatch.setattr(build, "HEADERS", [h for h in build.HEADERS if h != "seg_reduce.hpp"])
+    assert build.csrc_hash() == with_header
+    monkeypatch.undo()
+    monkeypatch.setattr(build, "UNPROFILED_SEGREDUCE", ())
+    assert build.csrc_hash() != with_header
 
 
 # ------------------------------------------------------------------ the restatement against the reference

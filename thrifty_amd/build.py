@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libthriftyhip.so")
 SOURCES = ["handle.hip", "window.hip", "pipeline.hip", "entry.hip", "text.hip", "detect16k.hip", "detect16k_geom0.hip", "detect16k_geom1.hip", "detect16k_geom2.hip", "detect16k_carrier.hip", "detect16k_preshift.hip", "detect16k_sec.hip", "detect_seg.hip", "detect_long.hip", "detect_small.hip", "generic.hip", "card_ingest.hip", "identify.hip", "run_file.hip", "card_gate.hip", "run_gate.hip", "template_extract.hip", "run_extract.hip", "match.hip", "tdoa.hip", "pos.hip", "postdetect.hip", "survey.hip", "chipscan.hip", "toadstats.hip", "syncstats.hip", "dossier.hip"]
-HEADERS = ["host_internal.hpp", "correlate16k.hpp", "correlate16k_geom.hpp", "detect_common.hpp", "fft_regs.hpp", "kernel_util.hpp", "lmdif8.hpp", "passes_w8.hpp", "card_gate.hpp", "template_extract.hpp", "post_stages.hpp", "run_loop.hpp", "hip_own.hpp", "input_window.hpp", "survey.hpp", "chipscan.hpp", "dossier.hpp", os.path.join("..", "..", "include", "thrifty_hip.h")]
+HEADERS = ["host_internal.hpp", "correlate16k.hpp", "correlate16k_geom.hpp", "detect_common.hpp", "fft_regs.hpp", "kernel_util.hpp", "lmdif8.hpp", "passes_w8.hpp", "card_gate.hpp", "template_extract.hpp", "post_stages.hpp", "run_loop.hpp", "hip_own.hpp", "input_window.hpp", "survey.hpp", "chipscan.hpp", "dossier.hpp", "seg_reduce.hpp", os.path.join("..", "..", "include", "thrifty_hip.h")]
 HOST_ONLY = ("handle.hip", "window.hip", "pipeline.hip", "entry.hip", "text.hip", "run_file.hip", "run_gate.hip", "run_extract.hip",
              "host_internal.hpp", "run_loop.hpp", "hip_own.hpp", "input_window.hpp")     # no kernels: csrc_hash() leaves these out
 # kernels that none of the workloads of profiles/hbm_traffic.json launches (the carrier gate's verdict and
@@ -38,6 +38,8 @@ UNPROFILED_CHIPSCAN = ("chipscan.hip", "chipscan.hpp")
 UNPROFILED_TOADSTATS = ("toadstats.hip",)
 # and for the clock-sync and TDOA statistics (thr_beaconsync, thr_tdoastats)
 UNPROFILED_SYNCSTATS = ("syncstats.hip",)
+# and for the segmented reduction those two stages share
+UNPROFILED_SEGREDUCE = ("seg_reduce.hpp",)
 # and for the detection dossiers (thr_dossier_*)
 UNPROFILED_DOSSIER = ("dossier.hip", "dossier.hpp")
 # per-file code-generation flags (measured on MI355X, see csrc/detect16k_carrier.hip)
@@ -91,11 +93,11 @@ def compile_cmd(src, path, obj, extra=()):
 
 def csrc_hash():
     """sha256 (first 16 hex digits) over the kernel sources and headers (everything but the host
-    side, HOST_ONLY, and the kernels no profiled workload launches, UNPROFILED / UNPROFILED_EXTRACT / UNPROFILED_MATCH / UNPROFILED_TDOA / UNPROFILED_POS / UNPROFILED_POST / UNPROFILED_SURVEY / UNPROFILED_CHIPSCAN / UNPROFILED_TOADSTATS / UNPROFILED_SYNCSTATS / UNPROFILED_DOSSIER): profiles/hbm_traffic.json records the hash its counter passes were taken on,
+    side, HOST_ONLY, and the kernels no profiled workload launches, UNPROFILED / UNPROFILED_EXTRACT / UNPROFILED_MATCH / UNPROFILED_TDOA / UNPROFILED_POS / UNPROFILED_POST / UNPROFILED_SURVEY / UNPROFILED_CHIPSCAN / UNPROFILED_TOADSTATS / UNPROFILED_SYNCSTATS / UNPROFILED_SEGREDUCE / UNPROFILED_DOSSIER): profiles/hbm_traffic.json records the hash its counter passes were taken on,
     bench.py flags a mismatch (`traffic_stale`)."""
     import hashlib
     h = hashlib.sha256()
-    skipped = HOST_ONLY + UNPROFILED + UNPROFILED_EXTRACT + UNPROFILED_MATCH + UNPROFILED_TDOA + UNPROFILED_POS + UNPROFILED_POST + UNPROFILED_SURVEY + UNPROFILED_CHIPSCAN + UNPROFILED_TOADSTATS + UNPROFILED_SYNCSTATS + UNPROFILED_DOSSIER
+    skipped = HOST_ONLY + UNPROFILED + UNPROFILED_EXTRACT + UNPROFILED_MATCH + UNPROFILED_TDOA + UNPROFILED_POS + UNPROFILED_POST + UNPROFILED_SURVEY + UNPROFILED_CHIPSCAN + UNPROFILED_TOADSTATS + UNPROFILED_SYNCSTATS + UNPROFILED_SEGREDUCE + UNPROFILED_DOSSIER
     for name in sorted(x for x in SOURCES + HEADERS if not x.startswith("..") and x not in skipped):
         h.update(name.encode())
         with open(os.path.join(CSRC, name), "rb") as f:

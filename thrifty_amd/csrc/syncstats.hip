@@ -23,11 +23,9 @@
 //   stable sort by cell -- give median and MAD, the mask is numpy's three float64 operations, and the same
 //   statistics are taken again over the rows the mask keeps.
 //
-// Every reduction has one form: positions are cut into tiles of kTile; a FRAGMENT is a maximal run of one
-// segment (a cell, or a cut) inside one tile; a workgroup reduces a tile with a segmented Hillis-Steele scan
-// through LDS and the fragment's last position stores its partials to a slab; a second launch combines each
-// segment's fragments in tile order.  No floating-point atomic, nothing depends on the grid: a repeated
-// call returns the same bits.
+// Every reduction is seg_reduce.hpp's: tiles, fragments, a segmented scan through LDS, a slab, a combining
+// launch (the form and why it returns the same bits every time are described there).  This file brings the
+// layouts (build_layout: the fragments of the cells, then of the cuts) and one load functor per reduction.
 //
 // Lifetimes: everything runs on the null stream.  A temporary that a queued kernel may still use is released
 // in two ways only: after an explicit synchronisation (record_times' hipEventSynchronize at the end of a call,
@@ -47,6 +45,7 @@
 
 #include "../../include/thrifty_hip.h"
 #include "post_stages.hpp"
+#include "seg_reduce.hpp"
 
 // the threshold and the outlier mask repeat numpy's float64 operations one by one: no a * b + c may become
 // an fma in this file (the build also passes -ffp-contract=off, thrifty_amd/build.py)
@@ -57,24 +56,11 @@ namespace {
 using thr::DevBuf;
 using thr::Event;
 using thr::with_temp;
+using namespace thr::seg;  // kBlock, kTile, the keys, the reduction, Result and its fetch
 
-constexpr int kBlock = 256;  // workgroup size of every kernel here
-constexpr int kTile = 256;   // positions per tile: one per thread
-constexpr int kChunk = 8;    // slots that go through LDS together
 constexpr int kMinCut = 8;   // a cut with left + kMinCut >= right is not fitted
 constexpr double kLight = 2.997e8;
-static_assert(kTile == kBlock, "one position per thread");
 
-inline dim3 grid_for(size_t n) { return dim3(unsigned((n + kBlock - 1) / kBlock)); }
-
-__device__ __forceinline__ unsigned key_i32(int v) { return unsigned(v) ^ 0x80000000u; }
-__device__ __forceinline__ int unkey_i32(unsigned k) { return int(k ^ 0x80000000u); }
-// numpy's min / max: a NaN wins
-__device__ __forceinline__ double pmin(double a, double b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
-__device__ __forceinline__ double pmax(double a, double b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
-__device__ __forceinline__ double comb(int slot, int n_sum, int n_min, double a, double b) {
-    return slot < n_sum ? a + b : (slot < n_sum + n_min ? pmin(a, b) : pmax(a, b));
-}
 // position of v in the ascending list, -1 when absent; n < 0: no list, every value passes (position 0)
 __device__ __forceinline__ int find_sorted(const int* list, int n, int v) {
     if (n < 0) return 0;
@@ -86,7 +72,7 @@ __device__ __forceinline__ int find_sorted(const int* list, int n, int v) {
     return (lo < n && list[lo] == v) ? lo : -1;
 }
 
-// ------------------------------------------------------------------ segments, fragments, reductions
+// ------------------------------------------------------------------ segments and their fragments
 // seg[p]: the segment of position p, -1 for a position of none.  A segment's positions are contiguous.
 __global__ __launch_bounds__(kBlock) void k_frag_heads(const int* __restrict__ seg, int m, unsigned* __restrict__ head) {
     const int p = blockIdx.x * kBlock + threadIdx.x;
@@ -107,72 +93,6 @@ __global__ __launch_bounds__(kBlock) void k_frag_layout(const int* __restrict__ 
         if (p == 0 || seg[p - 1] != sg) seg_frag[2 * size_t(sg)] = f;
         if (p == m - 1 || seg[p + 1] != sg) seg_frag[2 * size_t(sg) + 1] = f + 1;
     }
-}
-
-// Segmented inclusive scan over the workgroup's kTile positions: after it, v of a position holds the
-// combination of its fragment's positions up to itself.  The tree a fragment is combined in depends on where
-// it lies in its tile and on nothing else.  Two LDS buffers alternate, so one barrier per step is enough.
-template <int K, int NSUM, int NMIN>
-__device__ __forceinline__ void seg_scan(double (&v)[K], int t, int seg_start, double* lds) {
-    int buf = 0;
-#pragma unroll
-    for (int base = 0; base < K; base += kChunk) {
-        for (int d = 1; d < kTile; d <<= 1) {
-            double* b = lds + buf * (kChunk * kTile);
-#pragma unroll
-            for (int k = 0; k < kChunk; ++k)
-                if (base + k < K) b[k * kTile + t] = v[base + k];
-            __syncthreads();
-            if (t - d >= seg_start) {
-#pragma unroll
-                for (int k = 0; k < kChunk; ++k)
-                    if (base + k < K) v[base + k] = comb(base + k, NSUM, NMIN, b[k * kTile + t - d], v[base + k]);
-            }
-            buf ^= 1;
-        }
-    }
-    __syncthreads();  // the next trip starts writing buffer 0 again
-}
-
-// load(p, v) fills the K slots of position p (p < m); the slab gets one row of K per fragment
-template <int K, int NSUM, int NMIN, class Load>
-__global__ __launch_bounds__(kBlock) void k_reduce(Load load, int m, int n_tiles, const int* __restrict__ pos_frag,
-                                                   const int* __restrict__ frag_start, double* __restrict__ slab) {
-    __shared__ double lds[2 * kChunk * kTile];
-    const int t = threadIdx.x;
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int p = tile * kTile + t;
-        const bool live = p < m;
-        int f = 0, seg = t, fend = -1;  // a position past the end is a segment of its own, which nobody reads
-        double v[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) v[k] = 0.0;
-        if (live) {
-            f = pos_frag[p];
-            seg = frag_start[f] - tile * kTile;  // >= 0: every tile starts a fragment
-            fend = frag_start[f + 1];
-            load(p, v);
-        }
-        seg_scan<K, NSUM, NMIN>(v, t, seg, lds);
-        if (live && p + 1 == fend) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) slab[size_t(f) * K + k] = v[k];
-        }
-    }
-}
-// out[s][k] = the slab rows of segment s's fragments combined in order; zeros for a segment without positions
-__global__ __launch_bounds__(kBlock) void k_combine(const double* __restrict__ slab, const int* __restrict__ seg_frag,
-                                                    int n_seg, int K, int n_sum, int n_min, double* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= (long long)n_seg * K) return;
-    const int sg = int(i / K), k = int(i % K);
-    const int a = seg_frag[2 * size_t(sg)], e = seg_frag[2 * size_t(sg) + 1];
-    double acc = 0.0;
-    if (a < e) {
-        acc = slab[size_t(a) * K + k];
-        for (int f = a + 1; f < e; ++f) acc = comb(k, n_sum, n_min, acc, slab[size_t(f) * K + k]);
-    }
-    out[i] = acc;
 }
 
 struct Layout {
@@ -211,23 +131,13 @@ int build_layout(const int* seg, int m, int n_seg, Scratch& w, Layout& L, hipStr
 // out[n_seg][K] (device) = the reduction of load() over every segment of L; slab holds nf * K doubles
 template <int K, int NSUM, int NMIN, class Load>
 int reduce(const Load& load, const Layout& L, double* slab, double* out, hipStream_t s) {
-    const int n_tiles = (L.m + kTile - 1) / kTile;
-    const dim3 grid(unsigned(n_tiles < 2048 ? n_tiles : 2048));
-    k_reduce<K, NSUM, NMIN, Load><<<grid, dim3(kBlock), 0, s>>>(load, L.m, n_tiles, L.pos_frag.as<int>(),
-                                                                 L.frag_start.as<int>(), slab);
-    THR_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_combine, grid_for(size_t(L.n_seg) * K), dim3(kBlock), 0, s, (const double*)slab,
-                       (const int*)L.seg_frag.as<int>(), L.n_seg, K, NSUM, NMIN, out);
-    THR_HIP_TRY(hipGetLastError());
-    return THR_OK;
+    if (const int rc = launch_reduce<K, NSUM, NMIN>(load, L.m, L.pos_frag.as<int>(), L.frag_start.as<int>(), slab, s)) return rc;
+    const int* seg_frag = L.seg_frag.as<int>();
+    return launch_combine(slab, seg_frag, seg_frag + 1, 2, L.n_seg, K, NSUM, NMIN, out, s);
 }
 
 // ------------------------------------------------------------------ sorting rows into cells
 // key_hi / key_lo of row j; the rows end up ordered by (hi, lo), rows of equal keys in their first order
-__global__ __launch_bounds__(kBlock) void k_iota(unsigned* __restrict__ a, int m) {
-    const int j = blockIdx.x * kBlock + threadIdx.x;
-    if (j < m) a[j] = unsigned(j);
-}
 __global__ __launch_bounds__(kBlock) void k_gather_u64(const unsigned long long* __restrict__ src,
                                                        const unsigned* __restrict__ perm, int m,
                                                        unsigned long long* __restrict__ dst) {
@@ -830,56 +740,6 @@ int sort_by_cell_value(const double* vals, const int* pos_cell, int m, int nc, S
 thread_local double g_bsync_ms[5] = {0, 0, 0, 0, 0};
 thread_local double g_tdstats_ms[5] = {0, 0, 0, 0, 0};
 
-constexpr int kMaxOutputs = THR_BSYNC_N_OUTPUTS > THR_TDSTATS_N_OUTPUTS ? THR_BSYNC_N_OUTPUTS : THR_TDSTATS_N_OUTPUTS;
-struct Result {
-    int device = 0, n_out = 0;
-    DevBuf out[kMaxOutputs];
-    size_t bytes[kMaxOutputs] = {};
-    Event ev[2];
-    virtual ~Result() = default;
-};
-struct ResultGuard {  // frees the result unless it is handed to the caller
-    Result* r;
-    ~ResultGuard() { delete r; }
-};
-
-int fetch(const char* who, Result* R, int which, void* dst, size_t dst_bytes, double* ms_out) {
-    if (!R || which < 0 || which >= R->n_out) return thr::fail_msg(THR_ERR_ARG, "%s: no such result or output (%d)", who, which);
-    const size_t bytes = R->bytes[which];
-    if (dst_bytes != bytes)
-        return thr::fail_msg(THR_ERR_ARG, "%s: output %d holds %zu bytes, not %zu", who, which, bytes, dst_bytes);
-    if (bytes == 0) return THR_OK;
-    if (!dst) return thr::fail_msg(THR_ERR_ARG, "%s: null argument", who);
-    THR_HIP_TRY(hipSetDevice(R->device));
-    THR_HIP_TRY(hipEventRecord(R->ev[0].e, nullptr));
-    THR_HIP_TRY(hipMemcpy(dst, R->out[which].p, bytes, hipMemcpyDeviceToHost));
-    THR_HIP_TRY(hipEventRecord(R->ev[1].e, nullptr));
-    THR_HIP_TRY(hipEventSynchronize(R->ev[1].e));
-    float ms = 0;
-    THR_HIP_TRY(hipEventElapsedTime(&ms, R->ev[0].e, R->ev[1].e));
-    *ms_out += ms;
-    return THR_OK;
-}
-
-int pick_device(int device_id) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return thr::fail_msg(THR_ERR_DEVICE, "no HIP device available (this engine has no CPU fallback)");
-    if (device_id < 0 || device_id >= ndev) return thr::fail_msg(THR_ERR_ARG, "bad device_id %d", device_id);
-    THR_HIP_TRY(hipSetDevice(device_id));
-    return THR_OK;
-}
-
-int record_times(Event (&ev)[5], double* ms_out) {
-    THR_HIP_TRY(hipEventSynchronize(ev[4].e));
-    for (int i = 0; i < 4; ++i) {
-        float ms = 0;
-        THR_HIP_TRY(hipEventElapsedTime(&ms, ev[i].e, ev[i + 1].e));
-        ms_out[i] = ms;
-    }
-    return THR_OK;
-}
-
 // an ascending copy of a list without repeats, on the device; n_out = -1 when there is no list
 int upload_list(const int32_t* list, size_t n, DevBuf& d, int& n_out) {
     n_out = -1;
@@ -895,8 +755,8 @@ int upload_list(const int32_t* list, size_t n, DevBuf& d, int& n_out) {
 
 }  // namespace
 
-struct thr_bsync : Result {};
-struct thr_tdstats : Result {};
+struct thr_bsync : thr::seg::Result {};
+struct thr_tdstats : thr::seg::Result {};
 
 extern "C" int thr_beaconsync(int device_id, size_t n_det, const int32_t* rxid, const int32_t* txid, const double* soa,
                               const double* energy, const double* noise, const int64_t* idx, size_t n_matches,

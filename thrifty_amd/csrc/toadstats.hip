@@ -7,13 +7,11 @@
 //                       selection index); head flags of cells, receivers and FRAGMENTS, one inclusive scan of
 //                       the three; the eleven columns are gathered into sorted order once (k_gather, which
 //                       also makes the two dB columns: log10 appears there and nowhere else);
-//   2. tiles            the sorted order is cut into tiles of kTile positions; a fragment is a maximal run of
-//                       one cell inside one tile, so a tile holds one fragment of a big cell or many whole
-//                       small cells.  A workgroup reduces one tile per loop trip with a segmented
-//                       Hillis-Steele scan through LDS (segment start = the fragment's first position); the
-//                       fragment's last position stores the partials to a slab with plain stores.  A second
-//                       launch (k_combine) sums each cell's fragments in tile order, a third each receiver's
-//                       cells in cell order.  Nothing depends on the grid: a repeated call gives the same bits.
+//   2. tiles            every reduction is seg_reduce.hpp's: tiles of kTile positions, fragments, a segmented scan
+//                       through LDS, a slab, a combining launch (the form and why it returns the same bits every
+//                       time are described there).  A tile holds one fragment of a big cell or many whole small
+//                       cells; one combining launch sums each cell's fragments in tile order, another each
+//                       receiver's cells in cell order;
 //   3. pass 1           sum, min, max of the nine quantities, of timestamp and soa;
 //   4. pass 2           sum (x - mean)^2, the fit's centred moments in u = (soa - mean) / max|soa - mean|, the
 //                       three histograms: a tile that is one fragment of a cell counts in LDS when the cell's
@@ -34,6 +32,7 @@
 
 #include "../../include/thrifty_hip.h"
 #include "post_stages.hpp"
+#include "seg_reduce.hpp"
 
 // the histogram edges and bin indices repeat numpy's float64 operations one by one: no a * b + c may
 // become an fma in this file (the build also passes -ffp-contract=off, thrifty_amd/build.py)
@@ -44,14 +43,11 @@ namespace {
 using thr::DevBuf;
 using thr::Event;
 using thr::with_temp;
+using namespace thr::seg;  // kBlock, kTile (_native.TOADSTATS_WORKGROUP, _TILE), the keys, the reduction, Result
 
-constexpr int kBlock = 256;   // workgroup size of every kernel here (_native.TOADSTATS_WORKGROUP)
-constexpr int kTile = 256;    // positions per tile: one per thread (_native.TOADSTATS_TILE)
-constexpr int kChunk = 8;     // slots that go through LDS together
 constexpr int kHist = 4096;   // LDS histogram counters of pass 2
 constexpr int kQ = 9;         // quantities per cell
 constexpr long long kMaxBins = 1ll << 26;
-static_assert(kTile == kBlock, "one position per thread");
 
 // pass 1 slots: sums (9 quantities, timestamp, soa), mins (9 quantities, soa), maxs (9 quantities, timestamp, soa)
 constexpr int kK1 = 32, kS1 = 11, kM1 = 10;
@@ -76,15 +72,6 @@ struct TripSum {
         return Trip{a.c + b.c, a.f + b.f, a.r + b.r};
     }
 };
-
-__device__ __forceinline__ unsigned key_i32(int v) { return unsigned(v) ^ 0x80000000u; }
-__device__ __forceinline__ int unkey_i32(unsigned k) { return int(k ^ 0x80000000u); }
-// numpy's min / max: a NaN wins
-__device__ __forceinline__ double pmin(double a, double b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
-__device__ __forceinline__ double pmax(double a, double b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
-__device__ __forceinline__ double comb(int slot, int n_sum, int n_min, double a, double b) {
-    return slot < n_sum ? a + b : (slot < n_sum + n_min ? pmin(a, b) : pmax(a, b));
-}
 
 __global__ __launch_bounds__(kBlock) void k_keys(Cols c, int m, unsigned long long* __restrict__ keys,
                                                  unsigned* __restrict__ idx) {
@@ -171,97 +158,26 @@ __global__ __launch_bounds__(kBlock) void k_gather(Cols c, const unsigned* __res
     snr_db[2 * size_t(j) + 1] = db;
 }
 
-// Segmented inclusive scan over the workgroup's kTile positions: after it, v of a position holds the
-// combination of its fragment's positions up to itself.  The tree a fragment is summed in depends on where
-// it lies in its tile and on nothing else.  Two LDS buffers alternate, so one barrier per step is enough:
-// the buffer written in step i + 2 was last read in step i, before the barrier of step i + 1.
-template <int K, int NSUM, int NMIN>
-__device__ __forceinline__ void seg_scan(double (&v)[K], int t, int seg_start, double* lds) {
-    int buf = 0;
+// pass 1: sums, minima and maxima of the sorted columns (the slots of kK1)
+struct LoadPass1 {
+    const double* S;
+    size_t M;
+    __device__ void operator()(int p, double (&v)[kK1]) const {
 #pragma unroll
-    for (int base = 0; base < K; base += kChunk) {
-        for (int d = 1; d < kTile; d <<= 1) {
-            double* b = lds + buf * (kChunk * kTile);
-#pragma unroll
-            for (int k = 0; k < kChunk; ++k)
-                if (base + k < K) b[k * kTile + t] = v[base + k];
-            __syncthreads();
-            if (t - d >= seg_start) {
-#pragma unroll
-                for (int k = 0; k < kChunk; ++k)
-                    if (base + k < K) v[base + k] = comb(base + k, NSUM, NMIN, b[k * kTile + t - d], v[base + k]);
-            }
-            buf ^= 1;
+        for (int q = 0; q < kQ; ++q) {
+            const double a = S[q * M + p];
+            v[q] = a;
+            v[kMinQ + q] = a;
+            v[kMaxQ + q] = a;
         }
+        const double ts = S[kColTs * M + p], soa = S[kColSoa * M + p];
+        v[kSumTs] = ts;
+        v[kMaxTs] = ts;
+        v[kSumSoa] = soa;
+        v[kMinSoa] = soa;
+        v[kMaxSoa] = soa;
     }
-    __syncthreads();  // the next trip starts writing buffer 0 again
-}
-
-struct TilePos {
-    int p, f, seg, fend;
-    bool live;
 };
-__device__ __forceinline__ TilePos tile_pos(int tile, int t, int m, const int* pos_frag, const int* frag_start) {
-    TilePos x;
-    x.p = tile * kTile + t;
-    x.live = x.p < m;
-    x.f = 0;
-    x.seg = t;  // a position past the end is a segment of its own, which nobody reads
-    x.fend = -1;
-    if (x.live) {
-        x.f = pos_frag[x.p];
-        x.seg = frag_start[x.f] - tile * kTile;  // >= 0: every tile starts a fragment
-        x.fend = frag_start[x.f + 1];
-    }
-    return x;
-}
-
-__global__ __launch_bounds__(kBlock) void k_pass1(const double* __restrict__ S, int m, int n_tiles,
-                                                  const int* __restrict__ pos_frag,
-                                                  const int* __restrict__ frag_start, double* __restrict__ slab) {
-    __shared__ double lds[2 * kChunk * kTile];
-    const int t = threadIdx.x;
-    const size_t M = size_t(m);
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const TilePos x = tile_pos(tile, t, m, pos_frag, frag_start);
-        double v[kK1];
-#pragma unroll
-        for (int k = 0; k < kK1; ++k) v[k] = 0.0;
-        if (x.live) {
-#pragma unroll
-            for (int q = 0; q < kQ; ++q) {
-                const double a = S[q * M + x.p];
-                v[q] = a;
-                v[kMinQ + q] = a;
-                v[kMaxQ + q] = a;
-            }
-            const double ts = S[kColTs * M + x.p], soa = S[kColSoa * M + x.p];
-            v[kSumTs] = ts;
-            v[kMaxTs] = ts;
-            v[kSumSoa] = soa;
-            v[kMinSoa] = soa;
-            v[kMaxSoa] = soa;
-        }
-        seg_scan<kK1, kS1, kM1>(v, t, x.seg, lds);
-        if (x.live && x.p + 1 == x.fend) {
-#pragma unroll
-            for (int k = 0; k < kK1; ++k) slab[size_t(x.f) * kK1 + k] = v[k];
-        }
-    }
-}
-
-// out[o][k] = in[first[o]][k] (+) in[first[o] + 1][k] (+) ... in list order; slot k's operation as in comb()
-__global__ __launch_bounds__(kBlock) void k_combine(const double* __restrict__ in, const int* __restrict__ first,
-                                                    int n_out, int K, int n_sum, int n_min,
-                                                    double* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= (long long)n_out * K) return;
-    const int o = int(i / K), k = int(i % K);
-    const int a = first[o], e = first[o + 1];  // e > a: every cell has a fragment, every receiver a cell
-    double acc = in[size_t(a) * K + k];
-    for (int s = a + 1; s < e; ++s) acc = comb(k, n_sum, n_min, acc, in[size_t(s) * K + k]);
-    out[i] = acc;
-}
 
 // after pass 1, per cell: mean, min, max; the histogram lengths; the offset histogram's edges (numpy's
 // linspace(first, last, 11): i * step + first, the last edge set to `last`)
@@ -337,7 +253,7 @@ __global__ __launch_bounds__(kBlock) void k_pass2(
     const int* __restrict__ flags, const long long* __restrict__ minute_ptr, const long long* __restrict__ bin_ptr,
     unsigned long long* minute_hist, unsigned long long* bin_hist, unsigned long long* offset_hist,
     double* __restrict__ slab) {
-    __shared__ double lds[2 * kChunk * kTile];
+    __shared__ double lds[kScanLds];
     __shared__ unsigned hist[kHist];
     __shared__ int s_minute[2];  // the tile's smallest and largest minute
     const int t = threadIdx.x;
@@ -452,34 +368,24 @@ __global__ __launch_bounds__(kBlock) void k_fit_rx(const double* __restrict__ rv
     rx_fit[size_t(r) * 4 + 1] = (mean_ts + c0) - a * mean_soa;
 }
 
-__global__ __launch_bounds__(kBlock) void k_pass3(const double* __restrict__ S, int m, int n_tiles,
-                                                  const int* __restrict__ pos_frag, const int* __restrict__ frag_start,
-                                                  const int* __restrict__ pos_cell, const int* __restrict__ cell_rxi,
-                                                  const double* __restrict__ rxp, const double* __restrict__ line,
-                                                  const unsigned* __restrict__ perm, double* __restrict__ residual,
-                                                  double* __restrict__ slab) {
-    __shared__ double lds[2 * kChunk * kTile];
-    const int t = threadIdx.x;
-    const size_t M = size_t(m);
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const TilePos x = tile_pos(tile, t, m, pos_frag, frag_start);
-        double v[kK3] = {0.0, 0.0};
-        if (x.live) {
-            const int r = cell_rxi[pos_cell[x.p]];
-            const double* rp = rxp + size_t(r) * 3;
-            const double u = (S[kColSoa * M + x.p] - rp[0]) / rp[2], w = S[kColTs * M + x.p] - rp[1];
-            const double res = (line[size_t(r) * 2] + line[size_t(r) * 2 + 1] * u) - w;  // a * soa + b - timestamp
-            residual[perm[x.p]] = res;
-            v[0] = res * res;
-            v[1] = fabs(res);
-        }
-        seg_scan<kK3, 1, 0>(v, t, x.seg, lds);
-        if (x.live && x.p + 1 == x.fend) {
-            slab[size_t(x.f) * kK3] = v[0];
-            slab[size_t(x.f) * kK3 + 1] = v[1];
-        }
+// pass 3: the residual of a position, scattered to selection order; its square and its magnitude (the slots of kK3)
+struct LoadPass3 {
+    const double* S;
+    size_t M;
+    const int *pos_cell, *cell_rxi;
+    const double *rxp, *line;
+    const unsigned* perm;
+    double* residual;
+    __device__ void operator()(int p, double (&v)[kK3]) const {
+        const int r = cell_rxi[pos_cell[p]];
+        const double* rp = rxp + size_t(r) * 3;
+        const double u = (S[kColSoa * M + p] - rp[0]) / rp[2], w = S[kColTs * M + p] - rp[1];
+        const double res = (line[size_t(r) * 2] + line[size_t(r) * 2 + 1] * u) - w;  // a * soa + b - timestamp
+        residual[perm[p]] = res;
+        v[0] = res * res;
+        v[1] = fabs(res);
     }
-}
+};
 __global__ __launch_bounds__(kBlock) void k_fin_rx(const double* __restrict__ rv3, const long long* __restrict__ rx_count,
                                                    int nr, double* __restrict__ rx_fit) {
     const int r = blockIdx.x * kBlock + threadIdx.x;
@@ -491,32 +397,17 @@ __global__ __launch_bounds__(kBlock) void k_fin_rx(const double* __restrict__ rv
 // last thr_toadstats of this thread: copies in, sort and cells, reductions and histograms, fit, copies out
 thread_local double g_times_ms[5] = {0, 0, 0, 0, 0};
 
-inline dim3 grid_for(size_t n) { return dim3(unsigned((n + kBlock - 1) / kBlock)); }
-
 }  // namespace
 
-struct thr_tstats {
-    int device = 0;
-    DevBuf out[THR_TSTATS_N_OUTPUTS];
-    size_t bytes[THR_TSTATS_N_OUTPUTS] = {};
-    Event ev[2];
-};
+struct thr_tstats : thr::seg::Result {};
 
 namespace {
-
-struct StatsGuard {  // frees the result unless it is handed to the caller
-    thr_tstats* r;
-    ~StatsGuard() { delete r; }
-};
 
 // sums cells' fragments, then receivers' cells
 int combine2(const double* slab, const int* cell_frag, int nc, const int* rx_cell, int nr, int K, int n_sum, int n_min,
              double* cv, double* rv, hipStream_t s) {
-    hipLaunchKernelGGL(k_combine, grid_for(size_t(nc) * K), dim3(kBlock), 0, s, slab, cell_frag, nc, K, n_sum, n_min, cv);
-    hipLaunchKernelGGL(k_combine, grid_for(size_t(nr) * K), dim3(kBlock), 0, s, (const double*)cv, rx_cell, nr, K, n_sum,
-                       n_min, rv);
-    THR_HIP_TRY(hipGetLastError());
-    return THR_OK;
+    if (const int rc = launch_combine(slab, cell_frag, cell_frag + 1, 1, nc, K, n_sum, n_min, cv, s)) return rc;
+    return launch_combine(cv, rx_cell, rx_cell + 1, 1, nr, K, n_sum, n_min, rv, s);
 }
 
 }  // namespace
@@ -558,14 +449,11 @@ extern "C" int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const
         return thr::fail_msg(THR_ERR_ARG, "thr_toadstats: the histograms would exceed 2^26 bins (timestamps span %g s)",
                              t_max - time0);
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return thr::fail_msg(THR_ERR_DEVICE, "no HIP device available (this engine has no CPU fallback)");
-    if (device_id < 0 || device_id >= ndev) return thr::fail_msg(THR_ERR_ARG, "bad device_id %d", device_id);
-    THR_HIP_TRY(hipSetDevice(device_id));
+    if (const int rc = pick_device(device_id)) return rc;
     thr_tstats* R = new thr_tstats;
-    StatsGuard guard{R};
+    ResultGuard guard{R};
     R->device = device_id;
+    R->n_out = THR_TSTATS_N_OUTPUTS;
     hipStream_t s = nullptr;
     const dim3 blk(kBlock);
     Event ev[5];
@@ -624,7 +512,7 @@ extern "C" int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const
     Trip total;
     THR_HIP_TRY(hipMemcpy(&total, d_tincl.as<Trip>() + (m - 1), sizeof(Trip), hipMemcpyDeviceToHost));
     const int nc = int(total.c), nf = int(total.f), nr = int(total.r);
-    const int n_tiles = (m + kTile - 1) / kTile;
+    const int n_tiles = tiles_of(m);
 
     DevBuf* O = R->out;
     DevBuf d_cell_frag, d_cell_rxi, d_rx_cell, d_rx_ptr, d_frag_start, d_pos_frag, d_pos_cell, d_S;
@@ -658,7 +546,6 @@ extern "C" int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const
     THR_HIP_TRY(hipEventRecord(ev[2].e, s));
 
     // ---- 2. pass 1 and what follows from it
-    const dim3 tile_grid(unsigned(n_tiles < 2048 ? n_tiles : 2048));
     DevBuf d_slab, d_cv, d_rv, d_rxp, d_mlen, d_blen;
     THR_HIP_TRY(d_slab.alloc(size_t(nf) * kK1 * 8));
     THR_HIP_TRY(d_cv.alloc(size_t(nc) * kK1 * 8));
@@ -678,8 +565,8 @@ extern "C" int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const
     THR_HIP_TRY(O[THR_TSTATS_RESIDUAL].alloc(size_t(m) * 8));
     double* stats = O[THR_TSTATS_STATS].as<double>();
     long long *minute_ptr = O[THR_TSTATS_MINUTE_PTR].as<long long>(), *bin_ptr = O[THR_TSTATS_BIN_PTR].as<long long>();
-    hipLaunchKernelGGL(k_pass1, tile_grid, blk, 0, s, S, m, n_tiles, pos_frag, frag_start, d_slab.as<double>());
-    THR_HIP_TRY(hipGetLastError());
+    if (const int rc = launch_reduce<kK1, kS1, kM1>(LoadPass1{S, size_t(m)}, m, pos_frag, frag_start, d_slab.as<double>(), s))
+        return rc;
     if (const int rc = combine2(d_slab.as<double>(), cell_frag, nc, rx_cell, nr, kK1, kS1, kM1, d_cv.as<double>(),
                                 d_rv.as<double>(), s))
         return rc;
@@ -711,8 +598,8 @@ extern "C" int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const
     THR_HIP_TRY(hipMemsetAsync(O[THR_TSTATS_MINUTE_HIST].p, 0, size_t(n_minute) * 8, s));
     THR_HIP_TRY(hipMemsetAsync(O[THR_TSTATS_BIN_HIST].p, 0, size_t(n_bin) * 8, s));
     THR_HIP_TRY(hipMemsetAsync(O[THR_TSTATS_OFFSET_HIST].p, 0, size_t(nc) * 10 * 8, s));
-    hipLaunchKernelGGL(k_pass2, tile_grid, blk, 0, s, S, m, n_tiles, pos_frag, frag_start, pos_cell, (const double*)stats,
-                       cell_rxi, (const double*)d_rxp.as<double>(), (const long long*)d_blen.as<long long>(), (const int*)O[THR_TSTATS_BIN_FIRST].as<int>(),
+    hipLaunchKernelGGL(k_pass2, tile_grid(n_tiles), blk, 0, s, S, m, n_tiles, pos_frag, frag_start, pos_cell,
+                       (const double*)stats, cell_rxi, (const double*)d_rxp.as<double>(), (const long long*)d_blen.as<long long>(), (const int*)O[THR_TSTATS_BIN_FIRST].as<int>(),
                        (const double*)O[THR_TSTATS_OFFSET_EDGES].as<double>(),
                        (const int*)O[THR_TSTATS_CELL_FLAGS].as<int>(), (const long long*)minute_ptr,
                        (const long long*)bin_ptr, O[THR_TSTATS_MINUTE_HIST].as<unsigned long long>(),
@@ -733,10 +620,11 @@ extern "C" int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const
     hipLaunchKernelGGL(k_fit_rx, grid_for(nr), blk, 0, s, (const double*)d_rv.as<double>(),
                        (const long long*)O[THR_TSTATS_RX_COUNT].as<long long>(), (const double*)d_rxp.as<double>(), nr,
                        d_line.as<double>(), O[THR_TSTATS_RX_FIT].as<double>());
-    hipLaunchKernelGGL(k_pass3, tile_grid, blk, 0, s, S, m, n_tiles, pos_frag, frag_start, pos_cell, cell_rxi,
-                       (const double*)d_rxp.as<double>(), (const double*)d_line.as<double>(), (const unsigned*)perm,
-                       O[THR_TSTATS_RESIDUAL].as<double>(), d_slab.as<double>());
     THR_HIP_TRY(hipGetLastError());
+    if (const int rc = launch_reduce<kK3, 1, 0>(LoadPass3{S, size_t(m), pos_cell, cell_rxi, d_rxp.as<double>(), d_line.as<double>(),
+                                                           perm, O[THR_TSTATS_RESIDUAL].as<double>()},
+                                                m, pos_frag, frag_start, d_slab.as<double>(), s))
+        return rc;
     if (const int rc = combine2(d_slab.as<double>(), cell_frag, nc, rx_cell, nr, kK3, 1, 0, d_cv.as<double>(),
                                 d_rv.as<double>(), s))
         return rc;
@@ -744,12 +632,7 @@ extern "C" int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const
                        (const long long*)O[THR_TSTATS_RX_COUNT].as<long long>(), nr, O[THR_TSTATS_RX_FIT].as<double>());
     THR_HIP_TRY(hipGetLastError());
     THR_HIP_TRY(hipEventRecord(ev[4].e, s));
-    THR_HIP_TRY(hipEventSynchronize(ev[4].e));  // the temporaries go out of scope
-    for (int i = 0; i < 4; ++i) {
-        float ms = 0;
-        THR_HIP_TRY(hipEventElapsedTime(&ms, ev[i].e, ev[i + 1].e));
-        g_times_ms[i] = ms;
-    }
+    if (const int rc = record_times(ev, g_times_ms)) return rc;  // synchronises: the temporaries go out of scope
 
     size_t* B = R->bytes;
     B[THR_TSTATS_CELL_RX] = B[THR_TSTATS_CELL_TX] = B[THR_TSTATS_BIN_FIRST] = B[THR_TSTATS_CELL_FLAGS] = size_t(nc) * 4;
@@ -781,22 +664,7 @@ extern "C" int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const
 }
 
 extern "C" int thr_tstats_fetch(thr_tstats* R, int which, void* dst, size_t dst_bytes) try {
-    if (!R || which < 0 || which >= THR_TSTATS_N_OUTPUTS)
-        return thr::fail_msg(THR_ERR_ARG, "thr_tstats_fetch: no such result or output (%d)", which);
-    const size_t bytes = R->bytes[which];
-    if (dst_bytes != bytes)
-        return thr::fail_msg(THR_ERR_ARG, "thr_tstats_fetch: output %d holds %zu bytes, not %zu", which, bytes, dst_bytes);
-    if (bytes == 0) return THR_OK;
-    if (!dst) return thr::fail_msg(THR_ERR_ARG, "thr_tstats_fetch: null argument");
-    THR_HIP_TRY(hipSetDevice(R->device));
-    THR_HIP_TRY(hipEventRecord(R->ev[0].e, nullptr));
-    THR_HIP_TRY(hipMemcpy(dst, R->out[which].p, bytes, hipMemcpyDeviceToHost));
-    THR_HIP_TRY(hipEventRecord(R->ev[1].e, nullptr));
-    THR_HIP_TRY(hipEventSynchronize(R->ev[1].e));
-    float ms = 0;
-    THR_HIP_TRY(hipEventElapsedTime(&ms, R->ev[0].e, R->ev[1].e));
-    g_times_ms[4] += ms;
-    return THR_OK;
+    return fetch("thr_tstats_fetch", R, which, dst, dst_bytes, &g_times_ms[4]);
 } catch (...) {
     return thr::on_exception("thr_tstats_fetch");
 }
