@@ -86,7 +86,10 @@ extern "C" {
  *      numbers of the reference's `thrifty analyze_detect` (detect_analysis.py): the first detected blocks
  *      inside a list of index ranges, kept on the device, and per kept block what its plots are drawn from
  *    + thr_tdoa_model and THR_TDOA_* -- thr_tdoa with the reference's weighted, nearest and linear models
- *      (tdoa_est.py:108-222); thr_post_settings.reserved (always 0) is now .tdoa_model, 0 = the polynomial */
+ *      (tdoa_est.py:108-222); thr_post_settings.reserved (always 0) is now .tdoa_model, 0 = the polynomial
+ *    + thr_reldist / thr_reldist_fetch / thr_reldist_free / thr_debug_reldist_times / _geometry -- the numbers
+ *      of the reference's scripts/reldist_nearest.py (position along a baseline relative to a beacon, speed,
+ *      carrier Doppler, both smoothed) for every (mobile, beacon, rx0 < rx1) cell in one call */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -1422,6 +1425,104 @@ void thr_tdstats_free(thr_tdstats* result);
 /* {copies in, selection and cells, statistics, the robust part, copies out} of the thread's last thr_tdoastats */
 int thr_debug_tdoastats_times(double* ms_out /* [5] */);
 int thr_debug_tdoastats_geometry(int* tile_len, int* workgroup);
+
+/* ---- Relative distance, speed and Doppler (the reference's scripts/reldist_nearest.py) for every cell at once.
+ * A CELL is (mobile, beacon, rx0 < rx1), cells ordered by that key (signed).  Its rows are the matches of the
+ * mobile that hold both receivers, in match order, as (detection at rx0, detection at rx1); the beacon's rows
+ * are the same for the beacon, built once per (beacon, rx0, rx1).  Everything is float64, operation for
+ * operation (t: the mobile's row, b: the beacon's rows, nb of them, 0/1: the receiver):
+ *   hi      = the first beacon row with b_soa0 >= t_soa0 (np.searchsorted, side='left');
+ *   nearest = hi - 1 if hi > 0 and (hi == nb or |t_soa0 - b_soa0[hi-1]| < |t_soa0 - b_soa0[hi]|), else hi;
+ *   raw     NEAREST: (t_soa1 - b_soa1[n]) - (t_soa0 - b_soa0[n]);
+ *           LINPOL, 1 <= hi <= nb - 1: w = (t_soa0 - b_soa0[hi-1]) / (b_soa0[hi] - b_soa0[hi-1]),
+ *           t_soa1 - (b_soa1[hi-1] * (1 - w) + b_soa1[hi] * w); outside the beacon's span the end row is held,
+ *           t_soa1 - b_soa1[0] or t_soa1 - b_soa1[nb-1], and the row has THR_RELDIST_ROW_HELD;
+ *   x       = (raw + d_beacon + dist_rx) / 2.0 - dist_beacon, with the geometry of the cell's (beacon, rx0, rx1);
+ *   mask 1  stat_tools.is_outlier(x, thresh) per cell (as thr_tdoastats, but for one-row cells too);
+ *   stats   over the rows mask 1 keeps, times s2m = 2.997e8 / sample_rate: count, mean, population std (two
+ *           passes), min, max, and the number of kept rows inside [mean - std, mean + std];
+ *   speed   over the kept rows in order: diff(x) / diff(t_soa1) * s2m * sample_rate (m/s), at the rx1 timestamp
+ *           of the later row minus the cell's first rx0 timestamp; mask 2 on the speeds;
+ *   doppler ((ft0 - ft1) - (fb0[n] - fb1[n])) / 2.0 * (sample_rate / block_len) * 3e8 / carrier_hz * 3.6 (km/h)
+ *           with f = carrier_bin + carrier_offset, at the rx0 timestamp minus the cell's first; mask 3 on it;
+ *   smooth  the speeds mask 2 keeps and the dopplers mask 3 keeps, each by a local linear regression (LOWESS
+ *           without a robustness iteration): with m points, k = max(2, min(m, int(smooth_frac * m + 1e-10)));
+ *           the window of point i starts at the smallest L in [0, m - k] for which NOT (L + k < m and
+ *           x[L+k] - x[i] < x[i] - x[L]) -- the k consecutive points nearest in abscissa, the lowest window on
+ *           ties; h = the largest |x[j] - x[i]| in it; weights (1 - (|D|/h)^3)^3 (all 1 when h is not
+ *           positive); the value is the intercept (Swdd Swy - Swd Swdy) / det of the weighted line in
+ *           D = x[j] - x[i], det = Sw Swdd - Swd Swd, and Swy / Sw where det <= 1e-12 * Sw * Swdd (singular);
+ *           m < 2 or smooth_frac == 0: the values as they are.  One wave takes a point: lane l sums the terms
+ *           l, l + 64, ... in order, the 64 partial sums are combined by a butterfly.
+ * `idx` (the detections' ids) is taken with the other columns, as thr_beaconsync takes it, and not read: rows
+ * name detections by their position in the columns.
+ * A cell whose beacon rows are not non-decreasing in soa at rx0 (or, while smoothing, whose own rows are not in
+ * the timestamp at rx0) has THR_RELDIST_CELL_UNSORTED, one without beacon rows THR_RELDIST_CELL_NO_BEACON: raw
+ * is NaN there, and what follows from it.
+ * Errors (THR_ERR_ARG): a null pointer, a CSR that is not one, a match with two detections of one receiver, more
+ * than 2^28 detections, matches or rows (2^20 list or table entries), a method that is none, smooth_frac
+ * outside [0, 1], no row left. */
+#define THR_RELDIST_NEAREST 0
+#define THR_RELDIST_LINPOL 1
+typedef struct thr_reldist_geom { /* one (beacon, rx0, rx1): the three distances in samples */
+    int32_t beacon, rx0, rx1, reserved;
+    double d_beacon, dist_rx, dist_beacon;
+} thr_reldist_geom;
+typedef struct thr_reldist_opts {
+    int32_t method, reserved;
+    double sample_rate, block_len, carrier_hz, thresh, smooth_frac;
+    const thr_reldist_geom* geometry; /* NULL or n_geometry rows; a key that is not listed gets zeros */
+    size_t n_geometry;
+} thr_reldist_opts;
+typedef struct thr_reldist_counts {
+    size_t rows, cells, speeds, speed_points, dop_points;
+} thr_reldist_counts;
+typedef struct thr_reldist_result thr_reldist_result; /* the handle: thr_reldist is the call */
+#define THR_RELDIST_ROW_HELD 1
+#define THR_RELDIST_CELL_UNSORTED 1
+#define THR_RELDIST_CELL_NO_BEACON 2
+/* what thr_reldist_fetch copies, in terms of thr_reldist_counts */
+#define THR_RELDIST_CELL_KEY 0         /* int32[cells][4]: mobile, beacon, rx0, rx1 */
+#define THR_RELDIST_CELL_PTR 1         /* int64[cells + 1] into the rows */
+#define THR_RELDIST_ROW_DET 2          /* int64[rows][2]: detection at rx0, at rx1 (positions in the columns) */
+#define THR_RELDIST_ROW_MATCH 3        /* int64[rows]: the match the row came from */
+#define THR_RELDIST_NEAREST_IDX 4      /* int32[rows]: the nearest beacon row of the cell (-1 without one) */
+#define THR_RELDIST_HI 5               /* int32[rows] */
+#define THR_RELDIST_ROW_FLAGS 6        /* int32[rows], THR_RELDIST_ROW_* */
+#define THR_RELDIST_RAW 7              /* float64[rows], samples */
+#define THR_RELDIST_X 8                /* float64[rows], samples */
+#define THR_RELDIST_MASK1 9            /* uint8[rows]: 1 = outlier */
+#define THR_RELDIST_CELL_STATS 10      /* float64[cells][6]: count, mean, std, min, max (metres), rows within one std */
+#define THR_RELDIST_CELL_COUNTS 11     /* int64[cells][5]: rows, beacon rows, kept rows, kept speeds, kept dopplers */
+#define THR_RELDIST_SPEED_PTR 12       /* int64[cells + 1] into the speeds */
+#define THR_RELDIST_SPEED_X 13         /* float64[speeds], seconds */
+#define THR_RELDIST_SPEED 14           /* float64[speeds], m/s */
+#define THR_RELDIST_MASK2 15           /* uint8[speeds] */
+#define THR_RELDIST_SPEED_SMOOTH_PTR 16 /* int64[cells + 1] into the speed points (the speeds mask 2 keeps) */
+#define THR_RELDIST_SPEED_SMOOTH_X 17  /* float64[speed_points] */
+#define THR_RELDIST_SPEED_SMOOTH 18    /* float64[speed_points], m/s */
+#define THR_RELDIST_DOP 19             /* float64[rows], km/h */
+#define THR_RELDIST_MASK3 20           /* uint8[rows] */
+#define THR_RELDIST_DOP_SMOOTH_PTR 21  /* int64[cells + 1] into the doppler points (the rows mask 3 keeps) */
+#define THR_RELDIST_DOP_SMOOTH_X 22    /* float64[dop_points], seconds */
+#define THR_RELDIST_DOP_SMOOTH 23      /* float64[dop_points], km/h */
+#define THR_RELDIST_MEDIANS 24         /* float64[cells][6]: median and MAD of x, of the speeds, of the dopplers */
+#define THR_RELDIST_CELL_FLAGS 25      /* int32[cells], THR_RELDIST_CELL_* */
+#define THR_RELDIST_N_OUTPUTS 26
+int thr_reldist(int device_id, size_t n_det, const int32_t* rxid, const int32_t* txid, const double* soa,
+                const double* timestamp, const double* carrier_bin, const double* carrier_offset, const int64_t* idx,
+                size_t n_matches, const int64_t* match_ptr, const int64_t* match_idx, const int32_t* beacons,
+                size_t n_beacons, const int32_t* mobiles /* NULL: every txid that is no beacon */, size_t n_mobiles,
+                const int32_t* receivers /* NULL: all */, size_t n_receivers, const thr_reldist_opts* opts,
+                thr_reldist_result** result_out, thr_reldist_counts* counts_out);
+/* `which` is a THR_RELDIST_* index; dst_bytes must be the size given there */
+int thr_reldist_fetch(thr_reldist_result* result, int which, void* dst, size_t dst_bytes);
+void thr_reldist_free(thr_reldist_result* result);
+/* Milliseconds of the calling thread's last thr_reldist: {copies in, rows and cells, distances masks and
+ * statistics, the two smoothers, copies out (summed over the fetches)} */
+int thr_debug_reldist_times(double* ms_out /* [5] */);
+/* tile length of the reductions, workgroup size, lanes that share one smoothed point */
+int thr_debug_reldist_geometry(int* tile_len, int* workgroup, int* point_lanes);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,7 @@ EXPORTS = [
     "thr_tdoastats", "thr_tdstats_fetch", "thr_tdstats_free", "thr_debug_tdoastats_times", "thr_debug_tdoastats_geometry",
     "thr_dossier_create", "thr_dossier_destroy", "thr_dossier_reset", "thr_dossier_feed", "thr_dossier_feed_card",
     "thr_dossier_feed_stream", "thr_dossier_result", "thr_dossier_geometry",
+    "thr_reldist", "thr_reldist_fetch", "thr_reldist_free", "thr_debug_reldist_times", "thr_debug_reldist_geometry",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -65,6 +66,7 @@ CARD_HEADER_MAX = 48    # THR_CARD_HEADER_MAX
 
 BSYNC_COUNTS = ("rows", "cells", "discontinuities", "cuts")
 TDSTATS_COUNTS = ("rows", "cells", "robust")
+RELDIST_COUNTS = ("rows", "cells", "speeds", "speed_points", "dop_points")
 
 
 class ThrBsyncCounts(C.Structure):        # thr_bsync_counts
@@ -73,6 +75,21 @@ class ThrBsyncCounts(C.Structure):        # thr_bsync_counts
 
 class ThrTdstatsCounts(C.Structure):      # thr_tdstats_counts
     _fields_ = [(name, C.c_size_t) for name in TDSTATS_COUNTS]
+
+
+class ThrReldistCounts(C.Structure):      # thr_reldist_counts
+    _fields_ = [(name, C.c_size_t) for name in RELDIST_COUNTS]
+
+
+class ThrReldistGeom(C.Structure):        # thr_reldist_geom
+    _fields_ = [("beacon", C.c_int32), ("rx0", C.c_int32), ("rx1", C.c_int32), ("reserved", C.c_int32),
+                ("d_beacon", C.c_double), ("dist_rx", C.c_double), ("dist_beacon", C.c_double)]
+
+
+class ThrReldistOpts(C.Structure):        # thr_reldist_opts
+    _fields_ = [("method", C.c_int32), ("reserved", C.c_int32), ("sample_rate", C.c_double), ("block_len", C.c_double),
+                ("carrier_hz", C.c_double), ("thresh", C.c_double), ("smooth_frac", C.c_double),
+                ("geometry", C.POINTER(ThrReldistGeom)), ("n_geometry", C.c_size_t)]
 
 
 class ThrSettings(C.Structure):
@@ -370,7 +387,11 @@ def load_library():
                                    vp, C.c_size_t, C.POINTER(vp), C.POINTER(ThrBsyncCounts)])
     lib.thr_tdoastats.argtypes = ([C.c_int, C.c_size_t] + [vp] * 7 + [vp, vp, C.c_int, C.POINTER(vp),
                                   C.POINTER(ThrTdstatsCounts)])
-    for stem in ("bsync", "tdstats"):
+    lib.thr_reldist.argtypes = ([C.c_int, C.c_size_t] + [vp] * 7 + [C.c_size_t, vp, vp] + [vp, C.c_size_t] * 3 +
+                                [C.POINTER(ThrReldistOpts), C.POINTER(vp), C.POINTER(ThrReldistCounts)])
+    lib.thr_debug_reldist_times.argtypes = [C.POINTER(C.c_double)]
+    lib.thr_debug_reldist_geometry.argtypes = [ip, ip, ip]
+    for stem in ("bsync", "tdstats", "reldist"):
         getattr(lib, "thr_%s_fetch" % stem).argtypes = [vp, C.c_int, vp, C.c_size_t]
         getattr(lib, "thr_%s_free" % stem).argtypes = [vp]
         getattr(lib, "thr_%s_free" % stem).restype = None
@@ -1918,3 +1939,95 @@ def syncstats_geometry(which):
     t, w = C.c_int(), C.c_int()
     _check(lib, getattr(lib, "thr_debug_%s_geometry" % which)(C.byref(t), C.byref(w)))
     return t.value, w.value
+
+
+# the detection columns of thr_reldist, in its argument order
+RELDIST_COLUMNS = (("rxid", np.int32), ("txid", np.int32), ("soa", np.float64), ("timestamp", np.float64),
+                   ("carrier_bin", np.float64), ("carrier_offset", np.float64), ("idx", np.int64))
+RELDIST_METHODS = {"nearest": 0, "linpol": 1}                                 # THR_RELDIST_NEAREST, THR_RELDIST_LINPOL
+RELDIST_ROW_HELD, RELDIST_CELL_UNSORTED, RELDIST_CELL_NO_BEACON = 1, 1, 2     # THR_RELDIST_ROW_*, THR_RELDIST_CELL_*
+# THR_RELDIST_*: name -> (index, dtype, shape as a function of the counts)
+RELDIST_OUTPUTS = {
+    "cell_key": (0, np.int32, lambda c: (c["cells"], 4)),
+    "cell_ptr": (1, np.int64, lambda c: (c["cells"] + 1,)),
+    "row_det": (2, np.int64, lambda c: (c["rows"], 2)),
+    "row_match": (3, np.int64, lambda c: (c["rows"],)),
+    "nearest_idx": (4, np.int32, lambda c: (c["rows"],)),
+    "hi": (5, np.int32, lambda c: (c["rows"],)),
+    "row_flags": (6, np.int32, lambda c: (c["rows"],)),
+    "raw": (7, np.float64, lambda c: (c["rows"],)),
+    "x": (8, np.float64, lambda c: (c["rows"],)),
+    "mask1": (9, np.uint8, lambda c: (c["rows"],)),
+    "cell_stats": (10, np.float64, lambda c: (c["cells"], 6)),
+    "cell_counts": (11, np.int64, lambda c: (c["cells"], 5)),
+    "speed_ptr": (12, np.int64, lambda c: (c["cells"] + 1,)),
+    "speed_x": (13, np.float64, lambda c: (c["speeds"],)),
+    "speed": (14, np.float64, lambda c: (c["speeds"],)),
+    "mask2": (15, np.uint8, lambda c: (c["speeds"],)),
+    "speed_smooth_ptr": (16, np.int64, lambda c: (c["cells"] + 1,)),
+    "speed_smooth_x": (17, np.float64, lambda c: (c["speed_points"],)),
+    "speed_smooth": (18, np.float64, lambda c: (c["speed_points"],)),
+    "dop": (19, np.float64, lambda c: (c["rows"],)),
+    "mask3": (20, np.uint8, lambda c: (c["rows"],)),
+    "dop_smooth_ptr": (21, np.int64, lambda c: (c["cells"] + 1,)),
+    "dop_smooth_x": (22, np.float64, lambda c: (c["dop_points"],)),
+    "dop_smooth": (23, np.float64, lambda c: (c["dop_points"],)),
+    "medians": (24, np.float64, lambda c: (c["cells"], 6)),
+    "cell_flags": (25, np.int32, lambda c: (c["cells"],)),
+}
+
+
+def reldist(columns, match_ptr, match_idx, beacons, mobiles=None, receivers=None, method="linpol", sample_rate=2.4e6,
+            block_len=16384, carrier_hz=433e6, thresh=3.5, smooth_frac=0.025, geometry=None, outputs=None, device_id=0):
+    """thr_reldist on the seven detection columns (a mapping with the names of RELDIST_COLUMNS) and the matches as
+    CSR -> (counts dict, {name: array}) with every output of RELDIST_OUTPUTS (or those named in `outputs`) fetched.
+    `geometry`: rows (beacon, rx0, rx1, d_beacon, dist_rx, dist_beacon), the distances in samples; a cell whose key
+    is not listed gets zeros.  ValueError for what thr_reldist refuses."""
+    lib = load_library()
+    cols = _columns(columns, RELDIST_COLUMNS, "reldist")
+    n = len(cols[0])
+    ptr = np.ascontiguousarray(match_ptr, dtype=np.int64)
+    idx = np.ascontiguousarray(match_idx, dtype=np.int64)
+    if ptr.ndim != 1 or idx.ndim != 1 or len(ptr) < 1 or (ptr[-1] != len(idx) if len(ptr) else True):
+        raise ValueError("reldist: match_ptr and match_idx are not a CSR pair")
+    if method not in RELDIST_METHODS:
+        raise ValueError("reldist: method must be 'nearest' or 'linpol', not %r" % (method,))
+    if beacons is None:
+        raise ValueError("reldist: a list of beacons is needed")
+    lists = [None if v is None else np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (beacons, mobiles, receivers)]
+    keep = np.zeros(1, dtype=np.int64)      # an empty array still needs a pointer that is not NULL
+    geometry = [] if geometry is None else list(geometry)
+    table = (ThrReldistGeom * max(1, len(geometry)))()
+    for row, (b, r0, r1, d_beacon, dist_rx, dist_beacon) in zip(table, geometry):
+        row.beacon, row.rx0, row.rx1 = int(b), int(r0), int(r1)
+        row.d_beacon, row.dist_rx, row.dist_beacon = float(d_beacon), float(dist_rx), float(dist_beacon)
+    opts = ThrReldistOpts(RELDIST_METHODS[method], 0, float(sample_rate), float(block_len), float(carrier_hz), float(thresh),
+                          float(smooth_frac), table, len(geometry))
+    args = []
+    for v in lists:
+        args += [None if v is None else (v.ctypes.data if len(v) else keep.ctypes.data), 0 if v is None else len(v)]
+    handle, counts = C.c_void_p(), ThrReldistCounts()
+    rc = lib.thr_reldist(int(device_id), n, *[col.ctypes.data if n else None for col in cols], len(ptr) - 1, ptr.ctypes.data,
+                         idx.ctypes.data if len(idx) else keep.ctypes.data, *args, C.byref(opts), C.byref(handle), C.byref(counts))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    c = {name: int(getattr(counts, name)) for name in RELDIST_COUNTS}
+    return c, _fetch_all(lib, "reldist", handle, c, RELDIST_OUTPUTS, outputs)
+
+
+def reldist_times():
+    """Milliseconds (HIP events) of this thread's last reldist(): copies in, rows and cells, distances masks and
+    statistics, the two smoothers, copies out."""
+    lib = load_library()
+    ms = (C.c_double * 5)()
+    _check(lib, lib.thr_debug_reldist_times(ms))
+    return tuple(ms)
+
+
+def reldist_geometry():
+    """thr_debug_reldist_geometry -> (tile length T, workgroup size W, lanes that share one smoothed point)."""
+    lib = load_library()
+    t, w, lanes = C.c_int(), C.c_int(), C.c_int()
+    _check(lib, lib.thr_debug_reldist_geometry(C.byref(t), C.byref(w), C.byref(lanes)))
+    return t.value, w.value, lanes.value

@@ -1,5 +1,5 @@
-// The segmented reduction of the statistics stages (toadstats.hip, syncstats.hip), and the host side those
-// stages share: the result handle with its fetch, the device pick, the time record.
+// The segmented reduction of the statistics stages (toadstats.hip, syncstats.hip, reldist.hip), and the host side
+// those stages share: the result handle with its fetch, the device pick, the time record.
 //
 // Every reduction has one form: positions are cut into tiles of kTile; a FRAGMENT is a maximal run of one
 // segment (a cell, a cut, a receiver's cells) inside one tile; a workgroup reduces a tile with a segmented
@@ -13,7 +13,7 @@
 // the maximum.  A kernel that needs more around the load than a functor can hold (toadstats' pass 2) is built
 // from tile_pos and seg_scan directly.
 //
-// Everything here is a template, inline, or static: both translation units include it.
+// Everything here is a template, inline, or static: every translation unit of a stage includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,7 +29,7 @@
 namespace thr {
 namespace seg {
 
-constexpr int kBlock = 256;  // workgroup size of every kernel of the two stages
+constexpr int kBlock = 256;  // workgroup size of every kernel of these stages
 constexpr int kTile = 256;   // positions per tile: one per thread
 constexpr int kChunk = 8;    // slots that go through LDS together
 constexpr int kScanLds = 2 * kChunk * kTile;  // doubles of LDS that seg_scan alternates between
@@ -155,10 +155,10 @@ inline int launch_combine(const double* in, const int* begin, const int* end, in
 }
 
 // ------------------------------------------------------------------ the host side of a stage
-constexpr int kMaxOutputs = THR_TSTATS_N_OUTPUTS > THR_BSYNC_N_OUTPUTS
-                                ? (THR_TSTATS_N_OUTPUTS > THR_TDSTATS_N_OUTPUTS ? THR_TSTATS_N_OUTPUTS : THR_TDSTATS_N_OUTPUTS)
-                                : (THR_BSYNC_N_OUTPUTS > THR_TDSTATS_N_OUTPUTS ? THR_BSYNC_N_OUTPUTS : THR_TDSTATS_N_OUTPUTS);
-struct Result {  // what a call leaves on the device; thr_tstats, thr_bsync and thr_tdstats are this
+constexpr int max_of(int a, int b) { return a > b ? a : b; }
+constexpr int kMaxOutputs =
+    max_of(max_of(THR_TSTATS_N_OUTPUTS, THR_BSYNC_N_OUTPUTS), max_of(THR_TDSTATS_N_OUTPUTS, THR_RELDIST_N_OUTPUTS));
+struct Result {  // what a call leaves on the device; thr_tstats, thr_bsync, thr_tdstats and thr_reldist are this
     int device = 0, n_out = 0;
     DevBuf out[kMaxOutputs];
     size_t bytes[kMaxOutputs] = {};
