@@ -3,7 +3,8 @@
 workgroup W and the tile T; a cell of several fragments, a cell per row pair, a cell that starts on a tile's last
 position; cuts of exactly 9 and 10 rows; discontinuities at the first and last dsdoa, on both sides of a tile
 boundary, and next to each other; a cell of one row; degenerate cuts; filters; for the TDOA statistics cells of
-1, 2, 3 and 4 T rows, a constant cell, a far outlier, NaN, and the range filters on and off their bounds."""
+1, 2, 3 and 4 T rows, a constant cell, a far outlier, NaN, cells of one row that hold a number, a NaN and the two
+infinities, and the range filters on and off their bounds."""
 import os
 
 import numpy as np
@@ -212,6 +213,27 @@ def test_tdoa_constant_cell_far_outlier_and_nan():
     assert out["median"][0].tolist() == [1.251e-7 * R.LIGHT, 0.0] and out["stats"][0, 1] == 0.0
     assert out["median"][3, 1] == 0.0 and out["robust_stats"][3, 1] == 0.0
     assert np.isnan(out["stats"][2]).all() and np.isnan(out["median"][2]).all() and np.isnan(out["robust_stats"][2]).all()
+
+
+def test_tdoa_cells_of_one_row_are_never_masked():
+    """The shared mask kernel has no case for a cell of one row: its deviation and its MAD are the same number
+    (0, or NaN for a value that is not finite), so z is 0 / 0 or NaN and nothing exceeds the threshold."""
+    cols = tdoa_scene([1, 1, 1, 1, T + 1], seed=12)
+    key = cols["rx0"].astype(np.int64) * 100 + cols["rx1"] * 10 + cols["tx"]
+    kinds, rows = np.unique(key, return_counts=True)
+    single = kinds[rows == 1]
+    assert len(single) == 4                                             # the first keeps its finite value
+    for k, v in zip(single[1:], (np.nan, np.inf, -np.inf)):
+        cols["tdoa"][key == k] = v
+    counts, out = run_tdoa(cols, "cells of one row", robust=True)       # median and mask equal the reference's, NaNs included
+    sizes = np.diff(out["cell_ptr"])
+    assert sorted(sizes.tolist()) == [1, 1, 1, 1, T + 1]
+    first = out["cell_ptr"][:-1][sizes == 1]
+    assert not out["mask"][first].any() and np.array_equal(out["robust_count"], sizes)
+    x = cols["tdoa"][out["order"][first]] * R.LIGHT
+    assert np.array_equal(out["median"][sizes == 1, 0], x, equal_nan=True)      # one value is its own median
+    assert np.isfinite(x).sum() == 1 and np.isnan(x).sum() == 1 and sorted(x[np.isinf(x)].tolist()) == [-np.inf, np.inf]
+    assert np.array_equal(np.isnan(out["median"][sizes == 1, 1]), ~np.isfinite(x))      # MAD 0 for the finite one, else NaN
 
 
 def test_tdoa_range_filters_on_and_off_their_bounds():

@@ -44,6 +44,18 @@ def test_both_entry_points_are_declared_listed_and_built():
     assert "#pragma clang fp contract(off)" in shared and "atomic" not in shared.split("#include", 1)[1]
     assert "hipMalloc(" not in shared and not re.search(r"\blog10\(", shared)
     assert "constexpr double kLight = 2.997e8;" in source and R.LIGHT == 2.997e8
+    # what this file shares with reldist.hip stands once, in seg_cells.hpp: neither defines those kernels itself,
+    # one inclusive sum of flags serves both, and every launch of the statistics stages is seg_reduce.hpp's
+    cells = open(os.path.join(build.CSRC, "seg_cells.hpp")).read()
+    other = open(os.path.join(build.CSRC, "reldist.hip")).read()
+    assert "atomic" not in cells.split("#include", 1)[1] and "hipMalloc(" not in cells
+    for kernel in ("k_pairs", "k_median", "k_td_median", "k_dev", "k_td_dev", "k_mask", "k_td_mask"):
+        assert not re.search(r"\bvoid %s\(" % kernel, source + other), kernel
+        assert kernel.startswith("k_td_") or len(re.findall(r"\bvoid %s\(" % kernel, cells)) == 1, kernel
+    assert (source + other + cells + shared).count("hipcub::DeviceScan::InclusiveSum") == 1
+    five = source + other + cells + shared + open(os.path.join(build.CSRC, "toadstats.hip")).read()
+    assert five.count("hipLaunchKernelGGL") == 1 and "<<<" not in five
+    assert "hipLaunchKernelGGL(k, grid, dim3(kBlock), 0, s, static_cast<P>(a)...);" in shared
 
 
 def test_the_built_library_exports_both():

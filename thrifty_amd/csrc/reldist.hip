@@ -2,8 +2,9 @@
 // for EVERY (mobile, beacon, rx0 < rx1) cell of a deployment in one call (thr_reldist; the formulas are in
 // include/thrifty_hip.h, operation for operation).
 //
-//   1. groups    one thread per match counts and then emits the detection pairs it holds; seg_cells.hpp's two
-//                stable radix sorts leave them grouped by (txid, rx0, rx1) in match order.  One reduction per
+//   1. groups    seg_cells.hpp's front end (check_matches, pair_rows with this file's selector): one thread per
+//                match counts and then emits the detection pairs it holds, two stable radix sorts leave them
+//                grouped by (txid, rx0, rx1) in match order.  One reduction per
 //                group counts the places where soa (and the timestamp) at rx0 decreases.  A GROUP is the row
 //                list of one transmitter at one pair: a beacon's group serves every mobile of that pair.
 //   2. cells     the group table is a few dozen entries: the host reads it, pairs every mobile group with every
@@ -11,8 +12,8 @@
 //                the geometry up and sends the cell table back.  A cell's rows are its mobile group's.
 //   3. rows      one thread per row: bisection in the beacon's soa at rx0 (numpy's order: a NaN is last), the
 //                nearest row, raw by either method, x, the doppler.
-//   4. masks     stat_tools.is_outlier per cell: median and MAD from two sorts by (cell, value)
-//                (sort_by_cell_value), as thr_tdoastats takes them; statistics over the kept rows by tiled
+//   4. masks     stat_tools.is_outlier per cell is seg_cells.hpp's outlier_mask, the one thr_tdoastats calls:
+//                median and MAD from two sorts by (cell, value); statistics over the kept rows by tiled
 //                segmented reductions (seg_reduce.hpp); the speeds are one scan (which kept row is whose
 //                predecessor) and one thread per kept row; masks 2 and 3 the same way on speeds and dopplers.
 //   5. smoother  the kept speeds and the kept dopplers as two point lists; k_smooth gives ONE WAVE to a point:
@@ -25,7 +26,6 @@
 // No floating-point atomic; every sum has one order.  Lifetimes as in syncstats.hip: the null stream, and a
 // temporary leaves scope only after a synchronisation (record_times, a read-back hipMemcpy) or through hipFree.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -47,7 +47,6 @@ namespace {
 
 using thr::DevBuf;
 using thr::Event;
-using thr::with_temp;
 using namespace thr::seg;
 
 constexpr double kLight = 2.997e8;
@@ -64,46 +63,16 @@ struct Dets {
     const int *beacons, *mobiles, *receivers;
     int n_beacons, n_mobiles, n_receivers;  // -1: no list
 };
-// The host has checked: 0 <= mptr[i] <= mptr[i + 1], every midx inside the detections, no receiver twice in
-// a match.  EMIT = false counts the match's rows, EMIT = true writes them from offset incl[i] - count[i].
-template <bool EMIT>
-__global__ __launch_bounds__(kBlock) void k_pairs(Dets d, int n_matches, unsigned* __restrict__ count,
-                                                  const unsigned* __restrict__ incl, unsigned long long* __restrict__ key_hi,
-                                                  unsigned* __restrict__ key_lo, long long* __restrict__ det,
-                                                  long long* __restrict__ match) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n_matches) return;
-    const long long a0 = d.mptr[i], a1 = d.mptr[i + 1];
-    unsigned n = 0, at = 0;
-    if (EMIT) at = incl[i] - count[i];
-    const int tx = a1 > a0 ? d.tx[d.midx[a0]] : 0;
+struct TxPairs {  // k_pairs' selector: matches of the beacons and the mobiles, pairs of listed receivers
+    Dets d;
     // without a list of mobiles every transmitter is a beacon or a mobile
-    const bool wanted = a1 > a0 && (d.n_mobiles < 0 || find_sorted(d.beacons, d.n_beacons, tx) >= 0 ||
-                                    find_sorted(d.mobiles, d.n_mobiles, tx) >= 0);
-    if (wanted) {
-        for (long long a = a0; a < a1; ++a)
-            for (long long b = a + 1; b < a1; ++b) {
-                long long da = d.midx[a], db = d.midx[b];
-                if (find_sorted(d.receivers, d.n_receivers, d.rx[da]) < 0 || find_sorted(d.receivers, d.n_receivers, d.rx[db]) < 0)
-                    continue;
-                if (EMIT) {
-                    if (d.rx[db] < d.rx[da]) {
-                        const long long t = da;
-                        da = db;
-                        db = t;
-                    }
-                    const size_t j = size_t(at) + n;
-                    key_hi[j] = ((unsigned long long)key_i32(tx) << 32) | key_i32(d.rx[da]);
-                    key_lo[j] = key_i32(d.rx[db]);
-                    det[2 * j] = da;
-                    det[2 * j + 1] = db;
-                    match[j] = i;
-                }
-                ++n;
-            }
+    __device__ bool wanted(int tx) const {
+        return d.n_mobiles < 0 || find_sorted(d.beacons, d.n_beacons, tx) >= 0 || find_sorted(d.mobiles, d.n_mobiles, tx) >= 0;
     }
-    if (!EMIT) count[i] = n;
-}
+    __device__ bool kept(long long da, long long db) const {
+        return find_sorted(d.receivers, d.n_receivers, d.rx[da]) >= 0 && find_sorted(d.receivers, d.n_receivers, d.rx[db]) >= 0;
+    }
+};
 
 struct Src {  // the rows of all groups, in group order
     long long *det, *match;
@@ -224,99 +193,14 @@ struct LoadMax {  // K = 1, no sum, no minimum: a cell's largest value, NaN when
     const double* v;
     __device__ void operator()(int p, double (&o)[1]) const { o[0] = v[p]; }
 };
-// the median of each cell from its values in ascending order: the mean of the two middle ones; NaN when the
-// cell holds a NaN (probe: its max, which a NaN wins) or nothing
-__global__ __launch_bounds__(kBlock) void k_median(const double* __restrict__ sorted, const long long* __restrict__ ptr,
-                                                   const double* __restrict__ probe, int nc, double* __restrict__ out,
-                                                   int out_stride) {
-    const int c = blockIdx.x * kBlock + threadIdx.x;
-    if (c >= nc) return;
-    const long long a = ptr[c], n = ptr[c + 1] - a;
-    double med = NAN;
-    if (n > 0 && probe[c] == probe[c]) med = (sorted[a + (n - 1) / 2] + sorted[a + n / 2]) / 2.0;
-    out[size_t(c) * out_stride] = med;
+// med[c * 6], med[c * 6 + 1] = median, MAD of the cell's values; mask[p] = is_outlier.  The NaN probe is the cell's
+// max, reduced here into probe[nc] through the stage's slab.
+int masked(const double* vals, const Series& S, double thresh, Work& k, double* slab, double* probe, double* med,
+           unsigned char* mask, hipStream_t s) {
+    if (S.n) THR_TRY((reduce<1, 0, 0>(LoadMax{vals}, S.L, slab, probe, s)));
+    return outlier_mask(vals, S, probe, 1, thresh, k, med, 6, mask, s);
 }
-// numpy: diff = sqrt(sum((points - median)**2, axis=-1)), one column
-__global__ __launch_bounds__(kBlock) void k_dev(const double* __restrict__ v, const int* __restrict__ pos_cell,
-                                                const double* __restrict__ med, int stride, int n, double* __restrict__ dev) {
-    const int p = blockIdx.x * kBlock + threadIdx.x;
-    if (p >= n) return;
-    const double d = v[p] - med[size_t(pos_cell[p]) * stride];
-    dev[p] = sqrt(d * d);
-}
-// numpy: 0.6745 * diff / med_abs_deviation > thresh
-__global__ __launch_bounds__(kBlock) void k_mask(const double* __restrict__ dev, const int* __restrict__ pos_cell,
-                                                 const double* __restrict__ mad, int stride, double thresh, int n,
-                                                 unsigned char* __restrict__ mask) {
-    const int p = blockIdx.x * kBlock + threadIdx.x;
-    if (p >= n) return;
-    const double z = (0.6745 * dev[p]) / mad[size_t(pos_cell[p]) * stride];
-    mask[p] = z > thresh ? 1 : 0;
-}
-__global__ __launch_bounds__(kBlock) void k_fill_nan(double* __restrict__ out, int stride, int n) {
-    const int c = blockIdx.x * kBlock + threadIdx.x;
-    if (c < n) out[size_t(c) * stride] = out[size_t(c) * stride + 1] = NAN;
-}
-
-struct Series {  // n positions in nc cells: per position its cell, the cells' CSR, the fragments
-    int n = 0, nc = 0;
-    const int* pos_cell = nullptr;
-    const long long* ptr = nullptr;
-    Layout L;
-};
-struct Work {
-    Scratch w;
-    DevBuf sorted, dev, slab, probe;  // sized for the rows, the largest series
-};
-// med[c * 6], med[c * 6 + 1] = median, MAD of the cell's values; mask[p] = is_outlier
-int outlier_mask(const double* vals, const Series& S, double thresh, Work& k, double* med, unsigned char* mask, hipStream_t s) {
-    if (S.n == 0) {
-        hipLaunchKernelGGL(k_fill_nan, grid_for(S.nc), dim3(kBlock), 0, s, med, 6, S.nc);
-        THR_HIP_TRY(hipGetLastError());
-        return THR_OK;
-    }
-    const double* probe = k.probe.as<double>();
-    if (const int rc = reduce<1, 0, 0>(LoadMax{vals}, S.L, k.slab.as<double>(), k.probe.as<double>(), s)) return rc;
-    for (int pass = 0; pass < 2; ++pass) {
-        const double* v = pass ? k.dev.as<double>() : vals;
-        if (const int rc = sort_by_cell_value(v, S.pos_cell, S.n, S.nc, k.w, k.sorted, s)) return rc;
-        hipLaunchKernelGGL(k_median, grid_for(S.nc), dim3(kBlock), 0, s, (const double*)k.sorted.as<double>(), S.ptr, probe, S.nc,
-                           med + pass, 6);
-        THR_HIP_TRY(hipGetLastError());
-        if (pass == 0) {
-            hipLaunchKernelGGL(k_dev, grid_for(S.n), dim3(kBlock), 0, s, vals, S.pos_cell, (const double*)med, 6, S.n,
-                               k.dev.as<double>());
-            THR_HIP_TRY(hipGetLastError());
-        }
-    }
-    hipLaunchKernelGGL(k_mask, grid_for(S.n), dim3(kBlock), 0, s, (const double*)k.dev.as<double>(), S.pos_cell,
-                       (const double*)(med + 1), 6, thresh, S.n, mask);
-    THR_HIP_TRY(hipGetLastError());
-    return THR_OK;
-}
-
-struct LoadSt1 {  // over the kept rows: count and sum of x, min, max
-    const double* x;
-    const unsigned char* mask;
-    __device__ void operator()(int p, double (&v)[4]) const {
-        v[2] = INFINITY;
-        v[3] = -INFINITY;
-        if (mask[p]) return;
-        v[0] = 1.0;
-        v[1] = v[2] = v[3] = x[p];
-    }
-};
-struct LoadSt2 {  // (x - mean)^2; cv: LoadSt1's four values per cell
-    const double *x, *cv;
-    const unsigned char* mask;
-    const int* pos_cell;
-    __device__ void operator()(int p, double (&v)[1]) const {
-        if (mask[p]) return;
-        const double* c = cv + 4 * size_t(pos_cell[p]);
-        const double d = x[p] - c[1] / c[0];
-        v[0] = d * d;
-    }
-};
+// cv: LoadKept1<false>'s count, sum, min, max of the kept rows per cell; cv2: LoadKept2<false>'s
 __global__ __launch_bounds__(kBlock) void k_mean_std(const double* __restrict__ cv, const double* __restrict__ cv2, int nc,
                                                      double* __restrict__ ms) {
     const int c = blockIdx.x * kBlock + threadIdx.x;
@@ -483,43 +367,25 @@ __global__ __launch_bounds__(kBlock) void k_smooth(const double* __restrict__ px
     }
 }
 
-int scan(const unsigned* flag, unsigned* incl, int n, Scratch& w, hipStream_t s, unsigned* total) {
-    *total = 0;
-    if (n == 0) return THR_OK;
-    THR_HIP_TRY(with_temp(w.tmp, w.tmp_bytes,
-                          [&](void* t, size_t& b) { return hipcub::DeviceScan::InclusiveSum(t, b, flag, incl, n, s); }));
-    THR_HIP_TRY(hipMemcpy(total, incl + (n - 1), 4, hipMemcpyDeviceToHost));
-    return THR_OK;
-}
-
 // the values a mask keeps as a point list (ptr, x, y into the three outputs), smoothed into `smooth`
 int smooth_kept(const unsigned char* mask, const double* xs, const double* ys, const Series& S, double frac, Work& k,
                 DevBuf& flag, DevBuf& incl, DevBuf& o_ptr, DevBuf& o_x, DevBuf& o_smooth, size_t* n_out, hipStream_t s) {
     unsigned n_pts = 0;
-    if (S.n) {
-        hipLaunchKernelGGL(k_keep, grid_for(S.n), dim3(kBlock), 0, s, mask, S.n, flag.as<unsigned>());
-        THR_HIP_TRY(hipGetLastError());
-    }
-    if (const int rc = scan(flag.as<unsigned>(), incl.as<unsigned>(), S.n, k.w, s, &n_pts)) return rc;
+    THR_TRY(launch(k_keep, S.n, s, mask, S.n, flag.as<unsigned>()));
+    THR_TRY(scan(flag.as<unsigned>(), incl.as<unsigned>(), S.n, k.w, s, &n_pts));
     DevBuf pcell, o_y;
     THR_HIP_TRY(pcell.alloc(size_t(n_pts) * 4));
     THR_HIP_TRY(o_ptr.alloc((size_t(S.nc) + 1) * 8));
     THR_HIP_TRY(o_x.alloc(size_t(n_pts) * 8));
     THR_HIP_TRY(o_y.alloc(size_t(n_pts) * 8));
     THR_HIP_TRY(o_smooth.alloc(size_t(n_pts) * 8));
-    hipLaunchKernelGGL(k_ptr, grid_for(S.nc + 1), dim3(kBlock), 0, s, S.ptr, (const unsigned*)incl.as<unsigned>(), S.nc, S.n,
-                       o_ptr.as<long long>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_ptr, S.nc + 1, s, S.ptr, incl.as<unsigned>(), S.nc, S.n, o_ptr.as<long long>()));
     if (n_pts) {
-        hipLaunchKernelGGL(k_points, grid_for(S.n), dim3(kBlock), 0, s, (const unsigned*)flag.as<unsigned>(),
-                           (const unsigned*)incl.as<unsigned>(), xs, ys, S.pos_cell, S.n, o_x.as<double>(), o_y.as<double>(),
-                           pcell.as<int>());
-        THR_HIP_TRY(hipGetLastError());
+        THR_TRY(launch(k_points, S.n, s, flag.as<unsigned>(), incl.as<unsigned>(), xs, ys, S.pos_cell, S.n, o_x.as<double>(),
+                       o_y.as<double>(), pcell.as<int>()));
         const size_t groups = (size_t(n_pts) + kBlock / kPointLanes - 1) / (kBlock / kPointLanes);
-        hipLaunchKernelGGL(k_smooth, dim3(unsigned(groups < kMaxSmoothGrid ? groups : kMaxSmoothGrid)), dim3(kBlock), 0, s,
-                           (const double*)o_x.as<double>(), (const double*)o_y.as<double>(), (const int*)pcell.as<int>(),
-                           (const long long*)o_ptr.as<long long>(), int(n_pts), frac, o_smooth.as<double>());
-        THR_HIP_TRY(hipGetLastError());
+        THR_TRY(launch_grid(k_smooth, dim3(unsigned(groups < kMaxSmoothGrid ? groups : kMaxSmoothGrid)), s, o_x.as<double>(),
+                            o_y.as<double>(), pcell.as<int>(), o_ptr.as<long long>(), int(n_pts), frac, o_smooth.as<double>()));
     }
     THR_HIP_TRY(hipStreamSynchronize(s));  // pcell and o_y go out of scope here
     *n_out = n_pts;
@@ -557,34 +423,16 @@ extern "C" int thr_reldist(int device_id, size_t n_det, const int32_t* rxid, con
         return thr::fail_msg(THR_ERR_ARG, "thr_reldist: smooth_frac must lie in [0, 1], not %g", opts->smooth_frac);
     if (!positive(opts->sample_rate) || !positive(opts->block_len) || !positive(opts->carrier_hz) || opts->thresh != opts->thresh)
         return thr::fail_msg(THR_ERR_ARG, "thr_reldist: sample_rate, block_len and carrier_hz must be positive, thresh a number");
-    // ---- the host pass over the matches
-    if (match_ptr[0] != 0) return thr::fail_msg(THR_ERR_ARG, "thr_reldist: match_ptr[0] must be 0");
     uint64_t n_pairs = 0;
-    for (size_t m = 0; m < n_matches; ++m) {
-        const int64_t a = match_ptr[m], e = match_ptr[m + 1];
-        if (e < a) return thr::fail_msg(THR_ERR_ARG, "thr_reldist: match_ptr decreases at match %zu", m);
-        for (int64_t i = a; i < e; ++i) {
-            const int64_t d = match_idx[i];
-            if (d < 0 || uint64_t(d) >= n_det)
-                return thr::fail_msg(THR_ERR_ARG, "thr_reldist: match %zu holds detection %lld of %zu", m, (long long)d, n_det);
-            for (int64_t k = a; k < i; ++k)
-                if (rxid[match_idx[k]] == rxid[d])
-                    return thr::fail_msg(THR_ERR_ARG, "thr_reldist: match %zu holds two detections of one receiver (detection %lld)",
-                                         m, (long long)d);
-        }
-        n_pairs += uint64_t(e - a) * uint64_t(e - a > 0 ? e - a - 1 : 0) / 2;
-    }
-    if (n_pairs > (uint64_t(1) << 28)) return thr::fail_msg(THR_ERR_ARG, "thr_reldist: too many detection pairs");
-    if (n_matches == 0 || n_pairs == 0) return thr::fail_msg(THR_ERR_ARG, "thr_reldist: the selection is empty");
+    THR_TRY(check_matches("thr_reldist", n_det, rxid, n_matches, match_ptr, match_idx, &n_pairs));
     const size_t n_entries = size_t(match_ptr[n_matches]);
 
-    if (const int rc = pick_device(device_id)) return rc;
+    THR_TRY(pick_device(device_id));
     thr_reldist_result* R = new thr_reldist_result;
     ResultGuard guard{R};
     R->device = device_id;
     R->n_out = THR_RELDIST_N_OUTPUTS;
     hipStream_t s = nullptr;
-    const dim3 blk(kBlock);
     Event ev[5];
     for (Event& e : ev) THR_HIP_TRY(e.create());
     for (Event& e : R->ev) THR_HIP_TRY(e.create());
@@ -604,9 +452,9 @@ extern "C" int thr_reldist(int device_id, size_t n_det, const int32_t* rxid, con
     for (int k = 0; k < 4; ++k) THR_HIP_TRY(hipMemcpy(d_f64[k].p, h_f64[k], n_det * 8, hipMemcpyHostToDevice));
     THR_HIP_TRY(hipMemcpy(d_mptr.p, match_ptr, (n_matches + 1) * 8, hipMemcpyHostToDevice));
     THR_HIP_TRY(hipMemcpy(d_midx.p, match_idx, n_entries * 8, hipMemcpyHostToDevice));
-    if (const int rc = upload_list(beacons, n_beacons, d_bl, D.n_beacons)) return rc;
-    if (const int rc = upload_list(mobiles, n_mobiles, d_ml, D.n_mobiles)) return rc;
-    if (const int rc = upload_list(receivers, n_receivers, d_rl, D.n_receivers)) return rc;
+    THR_TRY(upload_list(beacons, n_beacons, d_bl, D.n_beacons));
+    THR_TRY(upload_list(mobiles, n_mobiles, d_ml, D.n_mobiles));
+    THR_TRY(upload_list(receivers, n_receivers, d_rl, D.n_receivers));
     THR_HIP_TRY(hipEventRecord(ev[1].e, s));
     D.rx = d_rx.as<int>();
     D.tx = d_tx.as<int>();
@@ -629,52 +477,31 @@ extern "C" int thr_reldist(int device_id, size_t n_det, const int32_t* rxid, con
     K.frac = opts->smooth_frac;
 
     // ---- 1. groups
-    const int nm = int(n_matches);
-    Work W;
-    Scratch& w = W.w;
-    DevBuf d_cnt, d_cincl;
-    THR_HIP_TRY(d_cnt.alloc(size_t(nm) * 4));
-    THR_HIP_TRY(d_cincl.alloc(size_t(nm) * 4));
-    hipLaunchKernelGGL(k_pairs<false>, grid_for(nm), blk, 0, s, D, nm, d_cnt.as<unsigned>(), (const unsigned*)nullptr,
-                       (unsigned long long*)nullptr, (unsigned*)nullptr, (long long*)nullptr, (long long*)nullptr);
-    THR_HIP_TRY(hipGetLastError());
-    unsigned n_src = 0;
-    if (const int rc = scan(d_cnt.as<unsigned>(), d_cincl.as<unsigned>(), nm, w, s, &n_src)) return rc;
-    if (n_src == 0) return thr::fail_msg(THR_ERR_ARG, "thr_reldist: the selection is empty");
-    const int ns = int(n_src);
-    DevBuf d_khi, d_klo, d_det, d_match, d_gptr, d_gkey, d_src_i64[2], d_src_f64[5];
-    THR_HIP_TRY(d_khi.alloc(size_t(ns) * 8));
-    THR_HIP_TRY(d_klo.alloc(size_t(ns) * 4));
-    THR_HIP_TRY(d_det.alloc(size_t(ns) * 16));
-    THR_HIP_TRY(d_match.alloc(size_t(ns) * 8));
-    THR_HIP_TRY(w.head.alloc(size_t(ns) * 4));
-    THR_HIP_TRY(w.incl.alloc(size_t(ns) * 4));
-    hipLaunchKernelGGL(k_pairs<true>, grid_for(nm), blk, 0, s, D, nm, d_cnt.as<unsigned>(), (const unsigned*)d_cincl.as<unsigned>(),
-                       d_khi.as<unsigned long long>(), d_klo.as<unsigned>(), d_det.as<long long>(), d_match.as<long long>());
-    THR_HIP_TRY(hipGetLastError());
-    Cells groups;
-    if (const int rc = sort_cells(d_khi, d_klo, ns, w, groups, d_gptr, d_gkey, s)) return rc;
+    Scratch w;
+    Work W{w};
+    PairRows src;
+    DevBuf d_gptr, d_gkey, d_src_i64[2], d_src_f64[5];
+    THR_TRY(pair_rows(TxPairs{D}, int(n_matches), w, src, d_gptr, d_gkey, s));
+    if (src.m == 0) return thr::fail_msg(THR_ERR_ARG, "thr_reldist: the selection is empty");
+    const int ns = src.m;
+    const Cells& groups = src.cells;
     const int ng = groups.nc;
     THR_HIP_TRY(d_src_i64[0].alloc(size_t(ns) * 16));
     THR_HIP_TRY(d_src_i64[1].alloc(size_t(ns) * 8));
     for (DevBuf& b : d_src_f64) THR_HIP_TRY(b.alloc(size_t(ns) * 8));
     Src G{d_src_i64[0].as<long long>(), d_src_i64[1].as<long long>(), d_src_f64[0].as<double>(), d_src_f64[1].as<double>(),
           d_src_f64[2].as<double>(),    d_src_f64[3].as<double>(),    d_src_f64[4].as<double>()};
-    hipLaunchKernelGGL(k_src, grid_for(ns), blk, 0, s, D, (const unsigned*)groups.perm.as<unsigned>(),
-                       (const long long*)d_det.as<long long>(), (const long long*)d_match.as<long long>(), ns, G);
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_src, ns, s, D, groups.perm.as<unsigned>(), src.det.as<long long>(), src.match.as<long long>(), ns, G));
     std::vector<int32_t> h_gkey(size_t(ng) * 3);
     std::vector<long long> h_gptr(size_t(ng) + 1);
     std::vector<double> h_gbad(size_t(ng) * 2);
     {
         Layout LG;
         DevBuf d_gslab, d_gbad;
-        if (const int rc = build_layout(groups.pos_cell.as<int>(), ns, ng, w, LG, s)) return rc;
+        THR_TRY(build_layout(groups.pos_cell.as<int>(), ns, ng, w, LG, s));
         THR_HIP_TRY(d_gslab.alloc(size_t(LG.nf) * 2 * 8));
         THR_HIP_TRY(d_gbad.alloc(size_t(ng) * 2 * 8));
-        if (const int rc = reduce<2, 2, 0>(LoadOrder{G.s0, G.t0, groups.pos_cell.as<int>(), ns}, LG, d_gslab.as<double>(),
-                                           d_gbad.as<double>(), s))
-            return rc;
+        THR_TRY((reduce<2, 2, 0>(LoadOrder{G.s0, G.t0, groups.pos_cell.as<int>(), ns}, LG, d_gslab.as<double>(), d_gbad.as<double>(), s)));
         THR_HIP_TRY(hipMemcpy(h_gbad.data(), d_gbad.p, h_gbad.size() * 8, hipMemcpyDeviceToHost));  // synchronises
         THR_HIP_TRY(hipMemcpy(h_gkey.data(), d_gkey.p, h_gkey.size() * 4, hipMemcpyDeviceToHost));
         THR_HIP_TRY(hipMemcpy(h_gptr.data(), d_gptr.p, h_gptr.size() * 8, hipMemcpyDeviceToHost));
@@ -753,11 +580,9 @@ extern "C" int thr_reldist(int device_id, size_t n_det, const int32_t* rxid, con
     const Cell* dc = d_cells.as<Cell>();
     const int* pos_cell = d_pos_cell.as<int>();
     const long long* cell_ptr = O[THR_RELDIST_CELL_PTR].as<long long>();
-    hipLaunchKernelGGL(k_pos_cell, grid_for(m), blk, 0, s, dc, nc, m, d_pos_cell.as<int>());
-    THR_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_cell_out, grid_for(nc), blk, 0, s, dc, nc, m, O[THR_RELDIST_CELL_KEY].as<int>(),
-                       O[THR_RELDIST_CELL_PTR].as<long long>(), O[THR_RELDIST_CELL_FLAGS].as<int>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_pos_cell, m, s, dc, nc, m, d_pos_cell.as<int>()));
+    THR_TRY(launch(k_cell_out, nc, s, dc, nc, m, O[THR_RELDIST_CELL_KEY].as<int>(), O[THR_RELDIST_CELL_PTR].as<long long>(),
+                   O[THR_RELDIST_CELL_FLAGS].as<int>()));
     THR_HIP_TRY(hipEventRecord(ev[2].e, s));
 
     // ---- 3. rows
@@ -771,8 +596,7 @@ extern "C" int thr_reldist(int device_id, size_t n_det, const int32_t* rxid, con
             O[THR_RELDIST_HI].as<int>(),            O[THR_RELDIST_ROW_FLAGS].as<int>(),       O[THR_RELDIST_RAW].as<double>(),
             O[THR_RELDIST_X].as<double>(),          O[THR_RELDIST_DOP].as<double>(),          d_s1.as<double>(),
             d_t0rel.as<double>(),                   d_t1rel.as<double>()};
-    hipLaunchKernelGGL(k_rel, grid_for(m), blk, 0, s, dc, pos_cell, G, K, m, Rw);
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_rel, m, s, dc, pos_cell, G, K, m, Rw));
 
     // ---- 4. mask 1, the statistics, the speeds, masks 2 and 3
     if (ns < m) {  // every beacon repeats a mobile's rows: head and incl hold the larger count
@@ -784,12 +608,12 @@ extern "C" int thr_reldist(int device_id, size_t n_det, const int32_t* rxid, con
     SR.nc = nc;
     SR.pos_cell = pos_cell;
     SR.ptr = cell_ptr;
-    if (const int rc = build_layout(pos_cell, m, nc, w, SR.L, s)) return rc;
-    DevBuf d_cv, d_cv2, d_ms, d_within, d_keep, d_kincl, d_sec, d_sincl, d_kept, d_kptr, d_scell, d_flag, d_fincl;
+    THR_TRY(build_layout(pos_cell, m, nc, w, SR.L, s));
+    DevBuf d_cv, d_cv2, d_ms, d_within, d_keep, d_kincl, d_sec, d_sincl, d_kept, d_kptr, d_scell, d_flag, d_fincl, d_slab, d_probe;
     THR_HIP_TRY(W.sorted.alloc(size_t(m) * 8));
     THR_HIP_TRY(W.dev.alloc(size_t(m) * 8));
-    THR_HIP_TRY(W.slab.alloc(size_t(tiles_of(m) + nc) * 4 * 8));  // no layout of at most m positions has more fragments
-    THR_HIP_TRY(W.probe.alloc(size_t(nc) * 8));
+    THR_HIP_TRY(d_slab.alloc(size_t(tiles_of(m) + nc) * 4 * 8));  // no layout of at most m positions has more fragments
+    THR_HIP_TRY(d_probe.alloc(size_t(nc) * 8));
     THR_HIP_TRY(d_cv.alloc(size_t(nc) * 4 * 8));
     THR_HIP_TRY(d_cv2.alloc(size_t(nc) * 8));
     THR_HIP_TRY(d_ms.alloc(size_t(nc) * 2 * 8));
@@ -800,71 +624,52 @@ extern "C" int thr_reldist(int device_id, size_t n_det, const int32_t* rxid, con
     THR_HIP_TRY(O[THR_RELDIST_CELL_STATS].alloc(size_t(nc) * 6 * 8));
     THR_HIP_TRY(O[THR_RELDIST_CELL_COUNTS].alloc(size_t(nc) * 5 * 8));
     THR_HIP_TRY(O[THR_RELDIST_SPEED_PTR].alloc((size_t(nc) + 1) * 8));
-    double* med = O[THR_RELDIST_MEDIANS].as<double>();
+    double *med = O[THR_RELDIST_MEDIANS].as<double>(), *slab = d_slab.as<double>();
     const double* x = O[THR_RELDIST_X].as<double>();
     const unsigned char* mask1 = O[THR_RELDIST_MASK1].as<unsigned char>();
-    if (const int rc = outlier_mask(x, SR, K.thresh, W, med, O[THR_RELDIST_MASK1].as<unsigned char>(), s)) return rc;
+    THR_TRY(masked(x, SR, K.thresh, W, slab, d_probe.as<double>(), med, O[THR_RELDIST_MASK1].as<unsigned char>(), s));
     const double *cv = d_cv.as<double>(), *ms = d_ms.as<double>();
-    if (const int rc = reduce<4, 2, 1>(LoadSt1{x, mask1}, SR.L, W.slab.as<double>(), d_cv.as<double>(), s)) return rc;
-    if (const int rc = reduce<1, 1, 0>(LoadSt2{x, cv, mask1, pos_cell}, SR.L, W.slab.as<double>(), d_cv2.as<double>(), s)) return rc;
-    hipLaunchKernelGGL(k_mean_std, grid_for(nc), blk, 0, s, cv, (const double*)d_cv2.as<double>(), nc, d_ms.as<double>());
-    THR_HIP_TRY(hipGetLastError());
-    if (const int rc = reduce<1, 1, 0>(LoadSt3{x, ms, mask1, pos_cell}, SR.L, W.slab.as<double>(), d_within.as<double>(), s)) return rc;
-    hipLaunchKernelGGL(k_stat_fin, grid_for(nc), blk, 0, s, cv, ms, (const double*)d_within.as<double>(), K.s2m, nc,
-                       O[THR_RELDIST_CELL_STATS].as<double>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY((reduce<4, 2, 1>(LoadKept1<false>{x, mask1}, SR.L, slab, d_cv.as<double>(), s)));
+    THR_TRY((reduce<1, 1, 0>(LoadKept2<false>{x, cv, mask1, pos_cell}, SR.L, slab, d_cv2.as<double>(), s)));
+    THR_TRY(launch(k_mean_std, nc, s, cv, d_cv2.as<double>(), nc, d_ms.as<double>()));
+    THR_TRY((reduce<1, 1, 0>(LoadSt3{x, ms, mask1, pos_cell}, SR.L, slab, d_within.as<double>(), s)));
+    THR_TRY(launch(k_stat_fin, nc, s, cv, ms, d_within.as<double>(), K.s2m, nc, O[THR_RELDIST_CELL_STATS].as<double>()));
     // the speeds: one per kept row that has a kept row before it in its cell
     unsigned n_kept = 0, n_speed = 0;
-    hipLaunchKernelGGL(k_keep, grid_for(m), blk, 0, s, mask1, m, d_keep.as<unsigned>());
-    THR_HIP_TRY(hipGetLastError());
-    if (const int rc = scan(d_keep.as<unsigned>(), d_kincl.as<unsigned>(), m, w, s, &n_kept)) return rc;
-    hipLaunchKernelGGL(k_ptr, grid_for(nc + 1), blk, 0, s, cell_ptr, (const unsigned*)d_kincl.as<unsigned>(), nc, m,
-                       d_kptr.as<long long>());
-    THR_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_kept, grid_for(m), blk, 0, s, (const unsigned*)d_keep.as<unsigned>(), (const unsigned*)d_kincl.as<unsigned>(),
-                       pos_cell, (const long long*)d_kptr.as<long long>(), m, d_kept.as<unsigned>(), d_sec.as<unsigned>());
-    THR_HIP_TRY(hipGetLastError());
-    if (const int rc = scan(d_sec.as<unsigned>(), d_sincl.as<unsigned>(), m, w, s, &n_speed)) return rc;
-    hipLaunchKernelGGL(k_ptr, grid_for(nc + 1), blk, 0, s, cell_ptr, (const unsigned*)d_sincl.as<unsigned>(), nc, m,
-                       O[THR_RELDIST_SPEED_PTR].as<long long>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_keep, m, s, mask1, m, d_keep.as<unsigned>()));
+    THR_TRY(scan(d_keep.as<unsigned>(), d_kincl.as<unsigned>(), m, w, s, &n_kept));
+    THR_TRY(launch(k_ptr, nc + 1, s, cell_ptr, d_kincl.as<unsigned>(), nc, m, d_kptr.as<long long>()));
+    THR_TRY(launch(k_kept, m, s, d_keep.as<unsigned>(), d_kincl.as<unsigned>(), pos_cell, d_kptr.as<long long>(), m,
+                   d_kept.as<unsigned>(), d_sec.as<unsigned>()));
+    THR_TRY(scan(d_sec.as<unsigned>(), d_sincl.as<unsigned>(), m, w, s, &n_speed));
+    THR_TRY(launch(k_ptr, nc + 1, s, cell_ptr, d_sincl.as<unsigned>(), nc, m, O[THR_RELDIST_SPEED_PTR].as<long long>()));
     THR_HIP_TRY(O[THR_RELDIST_SPEED_X].alloc(size_t(n_speed) * 8));
     THR_HIP_TRY(O[THR_RELDIST_SPEED].alloc(size_t(n_speed) * 8));
     THR_HIP_TRY(O[THR_RELDIST_MASK2].alloc(size_t(n_speed)));
     THR_HIP_TRY(d_scell.alloc(size_t(n_speed) * 4));
-    hipLaunchKernelGGL(k_speed, grid_for(m), blk, 0, s, (const unsigned*)d_sec.as<unsigned>(), (const unsigned*)d_kincl.as<unsigned>(),
-                       (const unsigned*)d_sincl.as<unsigned>(), (const unsigned*)d_kept.as<unsigned>(), pos_cell, Rw, K, m,
-                       O[THR_RELDIST_SPEED_X].as<double>(), O[THR_RELDIST_SPEED].as<double>(), d_scell.as<int>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_speed, m, s, d_sec.as<unsigned>(), d_kincl.as<unsigned>(), d_sincl.as<unsigned>(), d_kept.as<unsigned>(),
+                   pos_cell, Rw, K, m, O[THR_RELDIST_SPEED_X].as<double>(), O[THR_RELDIST_SPEED].as<double>(), d_scell.as<int>()));
     Series SS;
     SS.n = int(n_speed);
     SS.nc = nc;
     SS.pos_cell = d_scell.as<int>();
     SS.ptr = O[THR_RELDIST_SPEED_PTR].as<long long>();
-    if (SS.n)
-        if (const int rc = build_layout(SS.pos_cell, SS.n, nc, w, SS.L, s)) return rc;
-    if (const int rc = outlier_mask(O[THR_RELDIST_SPEED].as<double>(), SS, K.thresh, W, med + 2, O[THR_RELDIST_MASK2].as<unsigned char>(), s))
-        return rc;
-    if (const int rc = outlier_mask(O[THR_RELDIST_DOP].as<double>(), SR, K.thresh, W, med + 4, O[THR_RELDIST_MASK3].as<unsigned char>(), s))
-        return rc;
+    if (SS.n) THR_TRY(build_layout(SS.pos_cell, SS.n, nc, w, SS.L, s));
+    THR_TRY(masked(O[THR_RELDIST_SPEED].as<double>(), SS, K.thresh, W, slab, d_probe.as<double>(), med + 2, O[THR_RELDIST_MASK2].as<unsigned char>(), s));
+    THR_TRY(masked(O[THR_RELDIST_DOP].as<double>(), SR, K.thresh, W, slab, d_probe.as<double>(), med + 4, O[THR_RELDIST_MASK3].as<unsigned char>(), s));
     THR_HIP_TRY(hipEventRecord(ev[3].e, s));
 
     // ---- 5. the smoothers
     size_t n_sp = 0, n_dp = 0;
-    if (const int rc = smooth_kept(O[THR_RELDIST_MASK2].as<unsigned char>(), O[THR_RELDIST_SPEED_X].as<double>(),
-                                   O[THR_RELDIST_SPEED].as<double>(), SS, K.frac, W, d_flag, d_fincl, O[THR_RELDIST_SPEED_SMOOTH_PTR],
-                                   O[THR_RELDIST_SPEED_SMOOTH_X], O[THR_RELDIST_SPEED_SMOOTH], &n_sp, s))
-        return rc;
-    if (const int rc = smooth_kept(O[THR_RELDIST_MASK3].as<unsigned char>(), d_t0rel.as<double>(), O[THR_RELDIST_DOP].as<double>(), SR,
-                                   K.frac, W, d_flag, d_fincl, O[THR_RELDIST_DOP_SMOOTH_PTR], O[THR_RELDIST_DOP_SMOOTH_X],
-                                   O[THR_RELDIST_DOP_SMOOTH], &n_dp, s))
-        return rc;
-    hipLaunchKernelGGL(k_counts, grid_for(nc), blk, 0, s, dc, (const double*)O[THR_RELDIST_CELL_STATS].as<double>(),
-                       (const long long*)O[THR_RELDIST_SPEED_SMOOTH_PTR].as<long long>(),
-                       (const long long*)O[THR_RELDIST_DOP_SMOOTH_PTR].as<long long>(), nc, O[THR_RELDIST_CELL_COUNTS].as<long long>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(smooth_kept(O[THR_RELDIST_MASK2].as<unsigned char>(), O[THR_RELDIST_SPEED_X].as<double>(), O[THR_RELDIST_SPEED].as<double>(),
+                        SS, K.frac, W, d_flag, d_fincl, O[THR_RELDIST_SPEED_SMOOTH_PTR], O[THR_RELDIST_SPEED_SMOOTH_X],
+                        O[THR_RELDIST_SPEED_SMOOTH], &n_sp, s));
+    THR_TRY(smooth_kept(O[THR_RELDIST_MASK3].as<unsigned char>(), d_t0rel.as<double>(), O[THR_RELDIST_DOP].as<double>(), SR, K.frac, W,
+                        d_flag, d_fincl, O[THR_RELDIST_DOP_SMOOTH_PTR], O[THR_RELDIST_DOP_SMOOTH_X], O[THR_RELDIST_DOP_SMOOTH], &n_dp, s));
+    THR_TRY(launch(k_counts, nc, s, dc, O[THR_RELDIST_CELL_STATS].as<double>(), O[THR_RELDIST_SPEED_SMOOTH_PTR].as<long long>(),
+                   O[THR_RELDIST_DOP_SMOOTH_PTR].as<long long>(), nc, O[THR_RELDIST_CELL_COUNTS].as<long long>()));
     THR_HIP_TRY(hipEventRecord(ev[4].e, s));
-    if (const int rc = record_times(ev, g_reldist_ms)) return rc;  // synchronises: the temporaries go out of scope
+    THR_TRY(record_times(ev, g_reldist_ms));  // synchronises: the temporaries go out of scope
 
     size_t* B = R->bytes;
     B[THR_RELDIST_CELL_KEY] = size_t(nc) * 16;
@@ -901,26 +706,16 @@ extern "C" int thr_reldist_fetch(thr_reldist_result* R, int which, void* dst, si
     return thr::on_exception("thr_reldist_fetch");
 }
 
-extern "C" void thr_reldist_free(thr_reldist_result* R) {
-    if (!R) return;
-    (void)hipSetDevice(R->device);  // the buffers are freed on the device they were taken from
-    delete R;
-}
+extern "C" void thr_reldist_free(thr_reldist_result* R) { free_result(R); }
 
 extern "C" int thr_debug_reldist_times(double* ms_out) try {
-    if (!ms_out) return thr::fail_msg(THR_ERR_ARG, "thr_debug_reldist_times: null argument");
-    for (int i = 0; i < 5; ++i) ms_out[i] = g_reldist_ms[i];
-    return THR_OK;
+    return copy_times("thr_debug_reldist_times", g_reldist_ms, ms_out);
 } catch (...) {
     return thr::on_exception("thr_debug_reldist_times");
 }
 
 extern "C" int thr_debug_reldist_geometry(int* tile_len, int* workgroup, int* point_lanes) try {
-    if (!tile_len || !workgroup || !point_lanes) return thr::fail_msg(THR_ERR_ARG, "thr_debug_reldist_geometry: null argument");
-    *tile_len = kTile;
-    *workgroup = kBlock;
-    *point_lanes = kPointLanes;
-    return THR_OK;
+    return geometry("thr_debug_reldist_geometry", tile_len, workgroup, point_lanes, kPointLanes);
 } catch (...) {
     return thr::on_exception("thr_debug_reldist_geometry");
 }

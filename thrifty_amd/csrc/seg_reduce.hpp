@@ -13,6 +13,9 @@
 // the maximum.  A kernel that needs more around the load than a functor can hold (toadstats' pass 2) is built
 // from tile_pos and seg_scan directly.
 //
+// Every launch of these stages goes through launch() / launch_grid(), which take the parameter types from the
+// kernel; the tail every stage ends in (free, the five times, the geometry) stands once beside fetch().
+//
 // Everything here is a template, inline, or static: every translation unit of a stage includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -39,6 +42,28 @@ static_assert(kTile == kBlock, "one position per thread");
 inline dim3 grid_for(size_t n) { return dim3(unsigned((n + kBlock - 1) / kBlock)); }
 inline int tiles_of(int m) { return (m + kTile - 1) / kTile; }
 inline dim3 tile_grid(int n_tiles) { return dim3(unsigned(n_tiles < kMaxTileGrid ? n_tiles : kMaxTileGrid)); }
+
+// a step that returns THR_OK or an error which is already worded
+#define THR_TRY(expr)                           \
+    do {                                        \
+        if (const int rc_ = (expr)) return rc_; \
+    } while (0)
+
+// k on `grid` workgroups of kBlock.  The parameter types are the kernel's own, so the arguments convert as in
+// a plain call: buf.as<unsigned>() to const unsigned*, nullptr to any pointer.
+template <class... P, class... A>
+int launch_grid(void (*k)(P...), dim3 grid, hipStream_t s, A&&... a) {
+    static_assert(sizeof...(P) == sizeof...(A), "one argument per parameter of the kernel");
+    hipLaunchKernelGGL(k, grid, dim3(kBlock), 0, s, static_cast<P>(a)...);
+    THR_HIP_TRY(hipGetLastError());
+    return THR_OK;
+}
+// one thread for each of n items; nothing is launched for none
+template <class... P, class... A>
+int launch(void (*k)(P...), size_t n, hipStream_t s, A&&... a) {
+    if (n == 0) return THR_OK;
+    return launch_grid(k, grid_for(n), s, static_cast<A&&>(a)...);
+}
 
 // order-preserving map of int32 onto unsigned, for the radix sorts' keys
 __device__ __forceinline__ unsigned key_i32(int v) { return unsigned(v) ^ 0x80000000u; }
@@ -142,16 +167,11 @@ static __global__ __launch_bounds__(kBlock) void k_iota(unsigned* __restrict__ a
 template <int K, int NSUM, int NMIN, class Load>
 int launch_reduce(const Load& load, int m, const int* pos_frag, const int* frag_start, double* slab, hipStream_t s) {
     const int n_tiles = tiles_of(m);
-    k_reduce<K, NSUM, NMIN, Load><<<tile_grid(n_tiles), dim3(kBlock), 0, s>>>(load, m, n_tiles, pos_frag, frag_start, slab);
-    THR_HIP_TRY(hipGetLastError());
-    return THR_OK;
+    return launch_grid(k_reduce<K, NSUM, NMIN, Load>, tile_grid(n_tiles), s, load, m, n_tiles, pos_frag, frag_start, slab);
 }
 inline int launch_combine(const double* in, const int* begin, const int* end, int stride, int n_out, int K, int n_sum,
                           int n_min, double* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_combine, grid_for(size_t(n_out) * K), dim3(kBlock), 0, s, in, begin, end, stride, n_out, K, n_sum,
-                       n_min, out);
-    THR_HIP_TRY(hipGetLastError());
-    return THR_OK;
+    return launch(k_combine, size_t(n_out) * K, s, in, begin, end, stride, n_out, K, n_sum, n_min, out);
 }
 
 // ------------------------------------------------------------------ the host side of a stage
@@ -187,6 +207,29 @@ inline int fetch(const char* who, Result* R, int which, void* dst, size_t dst_by
     THR_HIP_TRY(hipEventElapsedTime(&ms, R->ev[0].e, R->ev[1].e));
     *ms_out += ms;
     return THR_OK;
+}
+
+// the tail of a stage: thr_*_free, thr_debug_*_times and thr_debug_*_geometry are one call of these each
+inline void free_result(Result* R) {
+    if (!R) return;
+    (void)hipSetDevice(R->device);  // the buffers are freed on the device they were taken from
+    delete R;
+}
+inline int copy_times(const char* who, const double (&ms)[5], double* ms_out) {
+    if (!ms_out) return thr::fail_msg(THR_ERR_ARG, "%s: null argument", who);
+    for (int i = 0; i < 5; ++i) ms_out[i] = ms[i];
+    return THR_OK;
+}
+inline int geometry(const char* who, int* tile_len, int* workgroup, int* third, int third_value) {
+    if (!tile_len || !workgroup || !third) return thr::fail_msg(THR_ERR_ARG, "%s: null argument", who);
+    *tile_len = kTile;
+    *workgroup = kBlock;
+    *third = third_value;
+    return THR_OK;
+}
+inline int geometry(const char* who, int* tile_len, int* workgroup) {
+    int none;
+    return geometry(who, tile_len, workgroup, &none, 0);
 }
 
 inline int pick_device(int device_id) {

@@ -24,9 +24,11 @@
 //   statistics are taken again over the rows the mask keeps.
 //
 // Every reduction is seg_reduce.hpp's: tiles, fragments, a segmented scan through LDS, a slab, a combining
-// launch (the form and why it returns the same bits every time are described there).  The row sorts and the
-// layouts (build_layout: the fragments of the cells, then of the cuts) are seg_cells.hpp's, which reldist.hip
-// uses too; this file brings one load functor per reduction.
+// launch (the form and why it returns the same bits every time are described there).  What reldist.hip needs
+// too is seg_cells.hpp's: the host pass over the matches and the rows of detection pairs (check_matches,
+// pair_rows: this file brings the selector), the row sorts, the layouts (build_layout: the fragments of the
+// cells, then of the cuts), the outlier mask and the statistics of the rows it keeps.  This file brings one
+// load functor per reduction of its own.
 //
 // Lifetimes: everything runs on the null stream.  A temporary that a queued kernel may still use is released
 // in two ways only: after an explicit synchronisation (record_times' hipEventSynchronize at the end of a call,
@@ -35,7 +37,6 @@
 // and so does an early error return.  The buffers of the repeated sorts live in Scratch, so that the robust
 // part does not pay that wait once per sort.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -57,7 +58,6 @@ namespace {
 
 using thr::DevBuf;
 using thr::Event;
-using thr::with_temp;
 using namespace thr::seg;  // kBlock, kTile, the keys, the reduction, Result and its fetch
 
 constexpr int kMinCut = 8;   // a cut with left + kMinCut >= right is not fitted
@@ -73,50 +73,17 @@ struct Dets {
     int has_range;
     long long lo, hi;
 };
-__device__ __forceinline__ bool pair_kept(const Dets& d, long long da, long long db) {
-    if (find_sorted(d.receivers, d.n_receivers, d.rx[da]) < 0 || find_sorted(d.receivers, d.n_receivers, d.rx[db]) < 0)
-        return false;
-    if (!d.has_range) return true;
-    const long long ia = d.id[da], ib = d.id[db];
-    return ia >= d.lo && ia <= d.hi && ib >= d.lo && ib <= d.hi;
-}
-// The host has checked: 0 <= mptr[i] <= mptr[i + 1], every midx inside the detections, no receiver twice in
-// a match.  EMIT = false counts the match's rows, EMIT = true writes them from offset incl[i] - count[i].
-template <bool EMIT>
-__global__ __launch_bounds__(kBlock) void k_pairs(Dets d, int n_matches, unsigned* __restrict__ count,
-                                                  const unsigned* __restrict__ incl, unsigned long long* __restrict__ key_hi,
-                                                  unsigned* __restrict__ key_lo, long long* __restrict__ det,
-                                                  long long* __restrict__ match) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n_matches) return;
-    const long long a0 = d.mptr[i], a1 = d.mptr[i + 1];
-    unsigned n = 0, at = 0;
-    if (EMIT) at = incl[i] - count[i];
-    const int tx = a1 > a0 ? d.tx[d.midx[a0]] : 0;
-    if (a1 > a0 && find_sorted(d.beacons, d.n_beacons, tx) >= 0) {
-        for (long long a = a0; a < a1; ++a)
-            for (long long b = a + 1; b < a1; ++b) {
-                long long da = d.midx[a], db = d.midx[b];
-                if (!pair_kept(d, da, db)) continue;
-                if (EMIT) {
-                    if (d.rx[db] < d.rx[da]) {
-                        const long long t = da;
-                        da = db;
-                        db = t;
-                    }
-                    const size_t j = size_t(at) + n;
-                    key_hi[j] = ((unsigned long long)key_i32(tx) << 32) | key_i32(d.rx[da]);
-                    key_lo[j] = key_i32(d.rx[db]);
-                    det[2 * j] = da;
-                    det[2 * j + 1] = db;
-                    match[j] = i;
-                }
-                ++n;
-            }
+struct BeaconPairs {  // k_pairs' selector: matches of the listed beacons, pairs of listed receivers inside the id range
+    Dets d;
+    __device__ bool wanted(int tx) const { return find_sorted(d.beacons, d.n_beacons, tx) >= 0; }
+    __device__ bool kept(long long da, long long db) const {
+        if (find_sorted(d.receivers, d.n_receivers, d.rx[da]) < 0 || find_sorted(d.receivers, d.n_receivers, d.rx[db]) < 0)
+            return false;
+        if (!d.has_range) return true;
+        const long long ia = d.id[da], ib = d.id[db];
+        return ia >= d.lo && ia <= d.hi && ib >= d.lo && ib <= d.hi;
     }
-    if (!EMIT) count[i] = n;
-}
-
+};
 // per position: the row's detections and match, sdoa, soa at rx0, the two detections' energy^2 / noise^2 summed
 __global__ __launch_bounds__(kBlock) void k_rows(Dets d, const unsigned* __restrict__ perm, const long long* __restrict__ det,
                                                  const long long* __restrict__ match, int m, long long* __restrict__ row_det,
@@ -467,62 +434,7 @@ __global__ __launch_bounds__(kBlock) void k_td_fin(const double* __restrict__ cv
     s[3] = cv[4 * size_t(c) + 2];
     s[4] = cv[4 * size_t(c) + 3];
 }
-// the median of each cell from its values in ascending order: the mean of the two middle ones (the same one
-// twice for an odd count); NaN when the cell holds a NaN (has_nan: its max, which a NaN wins)
-__global__ __launch_bounds__(kBlock) void k_td_median(const double* __restrict__ sorted, const long long* __restrict__ cell_ptr,
-                                                      const double* __restrict__ nan_probe, int probe_stride, int nc,
-                                                      double* __restrict__ out, int out_stride) {
-    const int c = blockIdx.x * kBlock + threadIdx.x;
-    if (c >= nc) return;
-    const long long a = cell_ptr[c], n = cell_ptr[c + 1] - a;
-    const double probe = nan_probe[size_t(c) * probe_stride];
-    const double lo = sorted[a + (n - 1) / 2], hi = sorted[a + n / 2];
-    out[size_t(c) * out_stride] = probe != probe ? NAN : (lo + hi) / 2.0;
-}
-// numpy: diff = sqrt(sum((points - median)**2, axis=-1)), one column
-__global__ __launch_bounds__(kBlock) void k_td_dev(const double* __restrict__ x, const int* __restrict__ pos_cell,
-                                                   const double* __restrict__ med, int m, double* __restrict__ dev) {
-    const int p = blockIdx.x * kBlock + threadIdx.x;
-    if (p >= m) return;
-    const double d = x[p] - med[2 * size_t(pos_cell[p])];
-    dev[p] = sqrt(d * d);
-}
-// numpy: 0.6745 * diff / med_abs_deviation > 3.5, applied to cells of more than one row
-__global__ __launch_bounds__(kBlock) void k_td_mask(const double* __restrict__ dev, const int* __restrict__ pos_cell,
-                                                    const long long* __restrict__ cell_ptr, const double* __restrict__ med,
-                                                    int m, unsigned char* __restrict__ mask) {
-    const int p = blockIdx.x * kBlock + threadIdx.x;
-    if (p >= m) return;
-    const int c = pos_cell[p];
-    const double z = (0.6745 * dev[p]) / med[2 * size_t(c) + 1];
-    mask[p] = (cell_ptr[c + 1] - cell_ptr[c] > 1 && z > 3.5) ? 1 : 0;
-}
-struct LoadRb1 {  // over the kept rows: count, sums of x and x^2, min, max
-    const double* x;
-    const unsigned char* mask;
-    __device__ void operator()(int p, double (&v)[5]) const {
-        v[3] = INFINITY;
-        v[4] = -INFINITY;
-        if (mask[p]) return;
-        const double a = x[p];
-        v[0] = 1.0;
-        v[1] = a;
-        v[2] = a * a;
-        v[3] = a;
-        v[4] = a;
-    }
-};
-struct LoadRb2 {
-    const double *x, *cv;
-    const unsigned char* mask;
-    const int* pos_cell;
-    __device__ void operator()(int p, double (&v)[1]) const {
-        if (mask[p]) return;
-        const int c = pos_cell[p];
-        const double d = x[p] - cv[5 * size_t(c) + 1] / cv[5 * size_t(c)];
-        v[0] = d * d;
-    }
-};
+// over the kept rows (LoadKept1<true>: count, sums of x and x^2, min, max): stats[c] as k_td_fin, and the count
 __global__ __launch_bounds__(kBlock) void k_rb_fin(const double* __restrict__ cv, const double* __restrict__ cv2, int nc,
                                                    double* __restrict__ stats, long long* __restrict__ count) {
     const int c = blockIdx.x * kBlock + threadIdx.x;
@@ -567,35 +479,16 @@ extern "C" int thr_beaconsync(int device_id, size_t n_det, const int32_t* rxid, 
     if (id_range && id_range[0] > id_range[1])
         return thr::fail_msg(THR_ERR_ARG, "thr_beaconsync: the id range %lld-%lld is empty", (long long)id_range[0],
                              (long long)id_range[1]);
-    // ---- the host pass over the matches
-    if (match_ptr[0] != 0) return thr::fail_msg(THR_ERR_ARG, "thr_beaconsync: match_ptr[0] must be 0");
     uint64_t n_pairs = 0;
-    for (size_t m = 0; m < n_matches; ++m) {
-        const int64_t a = match_ptr[m], e = match_ptr[m + 1];
-        if (e < a) return thr::fail_msg(THR_ERR_ARG, "thr_beaconsync: match_ptr decreases at match %zu", m);
-        for (int64_t i = a; i < e; ++i) {
-            const int64_t d = match_idx[i];
-            if (d < 0 || uint64_t(d) >= n_det)
-                return thr::fail_msg(THR_ERR_ARG, "thr_beaconsync: match %zu holds detection %lld of %zu", m, (long long)d, n_det);
-            for (int64_t k = a; k < i; ++k)
-                if (rxid[match_idx[k]] == rxid[d])
-                    return thr::fail_msg(THR_ERR_ARG,
-                                         "thr_beaconsync: match %zu holds two detections of one receiver (detection %lld)", m,
-                                         (long long)d);
-        }
-        n_pairs += uint64_t(e - a) * uint64_t(e - a > 0 ? e - a - 1 : 0) / 2;
-    }
-    if (n_pairs > (uint64_t(1) << 28)) return thr::fail_msg(THR_ERR_ARG, "thr_beaconsync: too many detection pairs");
-    if (n_matches == 0 || n_pairs == 0) return thr::fail_msg(THR_ERR_ARG, "thr_beaconsync: the selection is empty");
+    THR_TRY(check_matches("thr_beaconsync", n_det, rxid, n_matches, match_ptr, match_idx, &n_pairs));
     const size_t n_entries = size_t(match_ptr[n_matches]);
 
-    if (const int rc = pick_device(device_id)) return rc;
+    THR_TRY(pick_device(device_id));
     thr_bsync* R = new thr_bsync;
     ResultGuard guard{R};
     R->device = device_id;
     R->n_out = THR_BSYNC_N_OUTPUTS;
     hipStream_t s = nullptr;
-    const dim3 blk(kBlock);
     Event ev[5];
     for (Event& e : ev) THR_HIP_TRY(e.create());
     for (Event& e : R->ev) THR_HIP_TRY(e.create());
@@ -620,8 +513,8 @@ extern "C" int thr_beaconsync(int device_id, size_t n_det, const int32_t* rxid, 
     THR_HIP_TRY(hipMemcpy(d_id.p, idx, n_det * 8, hipMemcpyHostToDevice));
     THR_HIP_TRY(hipMemcpy(d_mptr.p, match_ptr, (n_matches + 1) * 8, hipMemcpyHostToDevice));
     THR_HIP_TRY(hipMemcpy(d_midx.p, match_idx, n_entries * 8, hipMemcpyHostToDevice));
-    if (const int rc = upload_list(beacons, n_beacons, d_bl, D.n_beacons)) return rc;
-    if (const int rc = upload_list(receivers, n_receivers, d_rl, D.n_receivers)) return rc;
+    THR_TRY(upload_list(beacons, n_beacons, d_bl, D.n_beacons));
+    THR_TRY(upload_list(receivers, n_receivers, d_rl, D.n_receivers));
     THR_HIP_TRY(hipEventRecord(ev[1].e, s));
     D.rx = d_rx.as<int>();
     D.tx = d_tx.as<int>();
@@ -638,35 +531,13 @@ extern "C" int thr_beaconsync(int device_id, size_t n_det, const int32_t* rxid, 
     D.hi = id_range ? id_range[1] : 0;
 
     // ---- 1. rows and cells
-    const int nm = int(n_matches);
     Scratch w;
-    DevBuf d_cnt, d_cincl;
-    THR_HIP_TRY(d_cnt.alloc(size_t(nm) * 4));
-    THR_HIP_TRY(d_cincl.alloc(size_t(nm) * 4));
-    hipLaunchKernelGGL(k_pairs<false>, grid_for(nm), blk, 0, s, D, nm, d_cnt.as<unsigned>(), (const unsigned*)nullptr,
-                       (unsigned long long*)nullptr, (unsigned*)nullptr, (long long*)nullptr, (long long*)nullptr);
-    THR_HIP_TRY(hipGetLastError());
-    THR_HIP_TRY(with_temp(w.tmp, w.tmp_bytes, [&](void* t, size_t& b) {
-        return hipcub::DeviceScan::InclusiveSum(t, b, d_cnt.as<unsigned>(), d_cincl.as<unsigned>(), nm, s);
-    }));
-    unsigned n_rows = 0;
-    THR_HIP_TRY(hipMemcpy(&n_rows, d_cincl.as<unsigned>() + (nm - 1), 4, hipMemcpyDeviceToHost));
-    if (n_rows == 0) return thr::fail_msg(THR_ERR_ARG, "thr_beaconsync: the selection is empty");
-    const int m = int(n_rows);
-    DevBuf d_khi, d_klo, d_det, d_match;
-    THR_HIP_TRY(d_khi.alloc(size_t(m) * 8));
-    THR_HIP_TRY(d_klo.alloc(size_t(m) * 4));
-    THR_HIP_TRY(d_det.alloc(size_t(m) * 16));
-    THR_HIP_TRY(d_match.alloc(size_t(m) * 8));
-    THR_HIP_TRY(w.head.alloc(size_t(m) * 4));
-    THR_HIP_TRY(w.incl.alloc(size_t(m) * 4));
-    hipLaunchKernelGGL(k_pairs<true>, grid_for(nm), blk, 0, s, D, nm, d_cnt.as<unsigned>(),
-                       (const unsigned*)d_cincl.as<unsigned>(), d_khi.as<unsigned long long>(), d_klo.as<unsigned>(),
-                       d_det.as<long long>(), d_match.as<long long>());
-    THR_HIP_TRY(hipGetLastError());
+    PairRows rows;
     DevBuf* O = R->out;
-    Cells cells;
-    if (const int rc = sort_cells(d_khi, d_klo, m, w, cells, O[THR_BSYNC_CELL_PTR], O[THR_BSYNC_CELL_KEY], s)) return rc;
+    THR_TRY(pair_rows(BeaconPairs{D}, int(n_matches), w, rows, O[THR_BSYNC_CELL_PTR], O[THR_BSYNC_CELL_KEY], s));
+    if (rows.m == 0) return thr::fail_msg(THR_ERR_ARG, "thr_beaconsync: the selection is empty");
+    const int m = rows.m;
+    const Cells& cells = rows.cells;
     const int nc = cells.nc;
     const int* pos_cell = cells.pos_cell.as<int>();
     const long long* cell_ptr = O[THR_BSYNC_CELL_PTR].as<long long>();
@@ -677,16 +548,14 @@ extern "C" int thr_beaconsync(int device_id, size_t n_det, const int32_t* rxid, 
     THR_HIP_TRY(d_soa0.alloc(size_t(m) * 8));
     THR_HIP_TRY(d_snr2.alloc(size_t(m) * 8));
     const double *sdoa = O[THR_BSYNC_SDOA].as<double>(), *soa0 = d_soa0.as<double>(), *snr2 = d_snr2.as<double>();
-    hipLaunchKernelGGL(k_rows, grid_for(m), blk, 0, s, D, (const unsigned*)cells.perm.as<unsigned>(),
-                       (const long long*)d_det.as<long long>(), (const long long*)d_match.as<long long>(), m,
-                       O[THR_BSYNC_ROW_DET].as<long long>(), O[THR_BSYNC_ROW_MATCH].as<long long>(),
-                       O[THR_BSYNC_SDOA].as<double>(), d_soa0.as<double>(), d_snr2.as<double>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_rows, m, s, D, cells.perm.as<unsigned>(), rows.det.as<long long>(), rows.match.as<long long>(), m,
+                   O[THR_BSYNC_ROW_DET].as<long long>(), O[THR_BSYNC_ROW_MATCH].as<long long>(), O[THR_BSYNC_SDOA].as<double>(),
+                   d_soa0.as<double>(), d_snr2.as<double>()));
     THR_HIP_TRY(hipEventRecord(ev[2].e, s));
 
     // ---- 2. discontinuities and cuts
     Layout LC;
-    if (const int rc = build_layout(pos_cell, m, nc, w, LC, s)) return rc;
+    THR_TRY(build_layout(pos_cell, m, nc, w, LC, s));
     DevBuf d_slab, d_cv, d_cv2, d_flag, d_cutseg;
     THR_HIP_TRY(d_slab.alloc(size_t(LC.nf) * 5 * 8));
     THR_HIP_TRY(d_cv.alloc(size_t(nc) * 5 * 8));
@@ -696,21 +565,16 @@ extern "C" int thr_beaconsync(int device_id, size_t n_det, const int32_t* rxid, 
     THR_HIP_TRY(O[THR_BSYNC_CELL_STATS].alloc(size_t(nc) * 4 * 8));
     THR_HIP_TRY(O[THR_BSYNC_DISC_PTR].alloc((size_t(nc) + 1) * 8));
     THR_HIP_TRY(O[THR_BSYNC_CUT_PTR].alloc((size_t(nc) + 1) * 8));
-    if (const int rc = reduce<1, 1, 0>(LoadDsdoa{sdoa, pos_cell, m}, LC, d_slab.as<double>(), d_cv.as<double>(), s)) return rc;
-    hipLaunchKernelGGL(k_disc_flags, grid_for(m), blk, 0, s, sdoa, pos_cell, cell_ptr, (const double*)d_cv.as<double>(), m,
-                       d_flag.as<unsigned>(), O[THR_BSYNC_CELL_STATS].as<double>());
-    THR_HIP_TRY(hipGetLastError());
-    THR_HIP_TRY(with_temp(w.tmp, w.tmp_bytes, [&](void* t, size_t& b) {
-        return hipcub::DeviceScan::InclusiveSum(t, b, d_flag.as<unsigned>(), w.incl.as<unsigned>(), m, s);
-    }));
+    THR_TRY((reduce<1, 1, 0>(LoadDsdoa{sdoa, pos_cell, m}, LC, d_slab.as<double>(), d_cv.as<double>(), s)));
+    THR_TRY(launch(k_disc_flags, m, s, sdoa, pos_cell, cell_ptr, d_cv.as<double>(), m, d_flag.as<unsigned>(),
+                   O[THR_BSYNC_CELL_STATS].as<double>()));
     unsigned n_disc = 0;
-    THR_HIP_TRY(hipMemcpy(&n_disc, w.incl.as<unsigned>() + (m - 1), 4, hipMemcpyDeviceToHost));
+    THR_TRY(scan(d_flag.as<unsigned>(), w.incl.as<unsigned>(), m, w, s, &n_disc));
     const int n_cuts = int(n_disc) + nc;
     THR_HIP_TRY(O[THR_BSYNC_DISC_IDX].alloc(size_t(n_disc) * 8));
-    hipLaunchKernelGGL(k_disc_layout, grid_for(m), blk, 0, s, (const unsigned*)d_flag.as<unsigned>(),
-                       (const unsigned*)w.incl.as<unsigned>(), pos_cell, cell_ptr, m, nc, O[THR_BSYNC_DISC_PTR].as<long long>(),
-                       O[THR_BSYNC_DISC_IDX].as<long long>(), O[THR_BSYNC_CUT_PTR].as<long long>(), d_cutseg.as<int>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_disc_layout, m, s, d_flag.as<unsigned>(), w.incl.as<unsigned>(), pos_cell, cell_ptr, m, nc,
+                   O[THR_BSYNC_DISC_PTR].as<long long>(), O[THR_BSYNC_DISC_IDX].as<long long>(),
+                   O[THR_BSYNC_CUT_PTR].as<long long>(), d_cutseg.as<int>()));
     const int* cut_seg = d_cutseg.as<int>();
     DevBuf d_cutcell, d_cutv, d_cutpar, d_cutc;
     THR_HIP_TRY(d_cutcell.alloc(size_t(n_cuts) * 4));
@@ -725,52 +589,38 @@ extern "C" int thr_beaconsync(int device_id, size_t n_det, const int32_t* rxid, 
     THR_HIP_TRY(O[THR_BSYNC_CUT_DISC_SOA].alloc(size_t(n_cuts) * 8));
     const long long *left = O[THR_BSYNC_CUT_LEFT].as<long long>(), *right = O[THR_BSYNC_CUT_RIGHT].as<long long>();
     const int* cut_flags = O[THR_BSYNC_CUT_FLAGS].as<int>();
-    hipLaunchKernelGGL(k_cuts, grid_for(n_cuts), blk, 0, s, (const long long*)O[THR_BSYNC_CUT_PTR].as<long long>(),
-                       (const long long*)O[THR_BSYNC_DISC_PTR].as<long long>(),
-                       (const long long*)O[THR_BSYNC_DISC_IDX].as<long long>(), cell_ptr, nc, n_cuts, d_cutcell.as<int>(),
-                       O[THR_BSYNC_CUT_LEFT].as<long long>(), O[THR_BSYNC_CUT_RIGHT].as<long long>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_cuts, n_cuts, s, O[THR_BSYNC_CUT_PTR].as<long long>(), O[THR_BSYNC_DISC_PTR].as<long long>(),
+                   O[THR_BSYNC_DISC_IDX].as<long long>(), cell_ptr, nc, n_cuts, d_cutcell.as<int>(),
+                   O[THR_BSYNC_CUT_LEFT].as<long long>(), O[THR_BSYNC_CUT_RIGHT].as<long long>()));
     THR_HIP_TRY(hipEventRecord(ev[3].e, s));
 
     // ---- 3. fits and residuals, 4. the summary
     Layout LU;
-    if (const int rc = build_layout(cut_seg, m, n_cuts, w, LU, s)) return rc;
+    THR_TRY(build_layout(cut_seg, m, n_cuts, w, LU, s));
     DevBuf d_slab2;
     THR_HIP_TRY(d_slab2.alloc(size_t(LU.nf) * 10 * 8));
     THR_HIP_TRY(O[THR_BSYNC_RESIDUAL].alloc(size_t(m) * 8));
     THR_HIP_TRY(O[THR_BSYNC_CELL_COUNTS].alloc(size_t(nc) * 3 * 8));
     THR_HIP_TRY(O[THR_BSYNC_CELL_FLAGS].alloc(size_t(nc) * 4));
-    if (const int rc = reduce<5, 3, 1>(LoadCut1{soa0, sdoa, snr2}, LU, d_slab2.as<double>(), d_cutv.as<double>(), s)) return rc;
-    hipLaunchKernelGGL(k_cut_mid, grid_for(n_cuts), blk, 0, s, (const double*)d_cutv.as<double>(), left, right, n_cuts,
-                       d_cutpar.as<double>(), O[THR_BSYNC_CUT_SNR].as<double>(), O[THR_BSYNC_CUT_FLAGS].as<int>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY((reduce<5, 3, 1>(LoadCut1{soa0, sdoa, snr2}, LU, d_slab2.as<double>(), d_cutv.as<double>(), s)));
+    THR_TRY(launch(k_cut_mid, n_cuts, s, d_cutv.as<double>(), left, right, n_cuts, d_cutpar.as<double>(),
+                   O[THR_BSYNC_CUT_SNR].as<double>(), O[THR_BSYNC_CUT_FLAGS].as<int>()));
     const double* cut_par = d_cutpar.as<double>();
-    if (const int rc = reduce<10, 10, 0>(LoadCut2{soa0, sdoa, cut_par, cut_seg, cut_flags}, LU, d_slab2.as<double>(),
-                                         d_cutv.as<double>(), s))
-        return rc;
-    hipLaunchKernelGGL(k_cut_fit, grid_for(n_cuts), blk, 0, s, (const double*)d_cutv.as<double>(), cut_par, left, right,
-                       (const int*)d_cutcell.as<int>(), cell_ptr, soa0, deg, n_cuts, O[THR_BSYNC_CUT_FLAGS].as<int>(),
-                       d_cutc.as<double>(), O[THR_BSYNC_CUT_FIT].as<double>(), O[THR_BSYNC_CUT_SNR].as<double>(),
-                       O[THR_BSYNC_CUT_DISC_SOA].as<double>());
-    THR_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_residual, grid_for(m), blk, 0, s, soa0, sdoa, cut_seg, cut_flags, cut_par,
-                       (const double*)d_cutc.as<double>(), m, O[THR_BSYNC_RESIDUAL].as<double>());
-    THR_HIP_TRY(hipGetLastError());
-    const double* residual = O[THR_BSYNC_RESIDUAL].as<double>();
-    if (const int rc = reduce<5, 4, 0>(LoadSum1{residual, (const double*)O[THR_BSYNC_CUT_SNR].as<double>(), cut_seg, cut_flags,
-                                                pos_cell, left, cell_ptr},
-                                       LC, d_slab.as<double>(), d_cv.as<double>(), s))
-        return rc;
-    if (const int rc = reduce<1, 1, 0>(LoadSum2{residual, (const double*)d_cv.as<double>(), cut_seg, cut_flags, pos_cell}, LC, d_slab.as<double>(),
-                                       d_cv2.as<double>(), s))
-        return rc;
-    hipLaunchKernelGGL(k_cell_fin, grid_for(nc), blk, 0, s, (const double*)d_cv.as<double>(), (const double*)d_cv2.as<double>(),
-                       cell_ptr, (const long long*)O[THR_BSYNC_DISC_PTR].as<long long>(), nc,
-                       O[THR_BSYNC_CELL_STATS].as<double>(), O[THR_BSYNC_CELL_COUNTS].as<long long>(),
-                       O[THR_BSYNC_CELL_FLAGS].as<int>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY((reduce<10, 10, 0>(LoadCut2{soa0, sdoa, cut_par, cut_seg, cut_flags}, LU, d_slab2.as<double>(), d_cutv.as<double>(), s)));
+    THR_TRY(launch(k_cut_fit, n_cuts, s, d_cutv.as<double>(), cut_par, left, right, d_cutcell.as<int>(), cell_ptr, soa0, deg, n_cuts,
+                   O[THR_BSYNC_CUT_FLAGS].as<int>(), d_cutc.as<double>(), O[THR_BSYNC_CUT_FIT].as<double>(),
+                   O[THR_BSYNC_CUT_SNR].as<double>(), O[THR_BSYNC_CUT_DISC_SOA].as<double>()));
+    THR_TRY(launch(k_residual, m, s, soa0, sdoa, cut_seg, cut_flags, cut_par, d_cutc.as<double>(), m,
+                   O[THR_BSYNC_RESIDUAL].as<double>()));
+    const double *residual = O[THR_BSYNC_RESIDUAL].as<double>(), *cv = d_cv.as<double>();
+    THR_TRY((reduce<5, 4, 0>(LoadSum1{residual, O[THR_BSYNC_CUT_SNR].as<double>(), cut_seg, cut_flags, pos_cell, left, cell_ptr}, LC,
+                             d_slab.as<double>(), d_cv.as<double>(), s)));
+    THR_TRY((reduce<1, 1, 0>(LoadSum2{residual, cv, cut_seg, cut_flags, pos_cell}, LC, d_slab.as<double>(), d_cv2.as<double>(), s)));
+    THR_TRY(launch(k_cell_fin, nc, s, cv, d_cv2.as<double>(), cell_ptr, O[THR_BSYNC_DISC_PTR].as<long long>(), nc,
+                   O[THR_BSYNC_CELL_STATS].as<double>(), O[THR_BSYNC_CELL_COUNTS].as<long long>(),
+                   O[THR_BSYNC_CELL_FLAGS].as<int>()));
     THR_HIP_TRY(hipEventRecord(ev[4].e, s));
-    if (const int rc = record_times(ev, g_bsync_ms)) return rc;  // synchronises: the temporaries go out of scope
+    THR_TRY(record_times(ev, g_bsync_ms));  // synchronises: the temporaries go out of scope
 
     size_t* B = R->bytes;
     B[THR_BSYNC_CELL_KEY] = size_t(nc) * 12;
@@ -803,11 +653,7 @@ extern "C" int thr_bsync_fetch(thr_bsync* R, int which, void* dst, size_t dst_by
     return thr::on_exception("thr_bsync_fetch");
 }
 
-extern "C" void thr_bsync_free(thr_bsync* R) {
-    if (!R) return;
-    (void)hipSetDevice(R->device);  // the buffers are freed on the device they were taken from
-    delete R;
-}
+extern "C" void thr_bsync_free(thr_bsync* R) { free_result(R); }
 
 extern "C" int thr_tdoastats(int device_id, size_t n, const int32_t* rx0, const int32_t* rx1, const int32_t* tx,
                              const double* timestamp, const int64_t* det0_idx, const int64_t* det1_idx, const double* tdoa,
@@ -824,13 +670,12 @@ extern "C" int thr_tdoastats(int device_id, size_t n, const int32_t* rx0, const 
     if (ts_range && !(ts_range[0] <= ts_range[1])) return thr::fail_msg(THR_ERR_ARG, "thr_tdoastats: the timestamp range is empty");
     if (det_range && det_range[0] > det_range[1]) return thr::fail_msg(THR_ERR_ARG, "thr_tdoastats: the detection id range is empty");
 
-    if (const int rc = pick_device(device_id)) return rc;
+    THR_TRY(pick_device(device_id));
     thr_tdstats* R = new thr_tdstats;
     ResultGuard guard{R};
     R->device = device_id;
     R->n_out = THR_TDSTATS_N_OUTPUTS;
     hipStream_t s = nullptr;
-    const dim3 blk(kBlock);
     Event ev[5];
     for (Event& e : ev) THR_HIP_TRY(e.create());
     for (Event& e : R->ev) THR_HIP_TRY(e.create());
@@ -870,13 +715,9 @@ extern "C" int thr_tdoastats(int device_id, size_t n, const int32_t* rx0, const 
     THR_HIP_TRY(d_keep.alloc(n * 4));
     THR_HIP_TRY(w.head.alloc(n * 4));
     THR_HIP_TRY(w.incl.alloc(n * 4));
-    hipLaunchKernelGGL(k_td_keep, grid_for(n), blk, 0, s, D, nn, d_keep.as<unsigned>());
-    THR_HIP_TRY(hipGetLastError());
-    THR_HIP_TRY(with_temp(w.tmp, w.tmp_bytes, [&](void* t, size_t& b) {
-        return hipcub::DeviceScan::InclusiveSum(t, b, d_keep.as<unsigned>(), w.incl.as<unsigned>(), nn, s);
-    }));
+    THR_TRY(launch(k_td_keep, n, s, D, nn, d_keep.as<unsigned>()));
     unsigned n_sel = 0;
-    THR_HIP_TRY(hipMemcpy(&n_sel, w.incl.as<unsigned>() + (nn - 1), 4, hipMemcpyDeviceToHost));
+    THR_TRY(scan(d_keep.as<unsigned>(), w.incl.as<unsigned>(), nn, w, s, &n_sel));
     if (n_sel == 0) return thr::fail_msg(THR_ERR_ARG, "thr_tdoastats: the selection is empty");
     const int m = int(n_sel);
     DevBuf d_khi, d_klo, d_sel, d_x;
@@ -884,75 +725,58 @@ extern "C" int thr_tdoastats(int device_id, size_t n, const int32_t* rx0, const 
     THR_HIP_TRY(d_klo.alloc(size_t(m) * 4));
     THR_HIP_TRY(d_sel.alloc(size_t(m) * 4));
     THR_HIP_TRY(d_x.alloc(size_t(m) * 8));
-    hipLaunchKernelGGL(k_td_keys, grid_for(n), blk, 0, s, D, nn, (const unsigned*)d_keep.as<unsigned>(),
-                       (const unsigned*)w.incl.as<unsigned>(), d_khi.as<unsigned long long>(), d_klo.as<unsigned>(),
-                       d_sel.as<unsigned>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_td_keys, n, s, D, nn, d_keep.as<unsigned>(), w.incl.as<unsigned>(), d_khi.as<unsigned long long>(),
+                   d_klo.as<unsigned>(), d_sel.as<unsigned>()));
     DevBuf* O = R->out;
     Cells cells;
-    if (const int rc = sort_cells(d_khi, d_klo, m, w, cells, O[THR_TDSTATS_CELL_PTR], O[THR_TDSTATS_CELL_KEY], s)) return rc;
+    THR_TRY(sort_cells(d_khi, d_klo, m, w, cells, O[THR_TDSTATS_CELL_PTR], O[THR_TDSTATS_CELL_KEY], s));
     const int nc = cells.nc;
     const int* pos_cell = cells.pos_cell.as<int>();
     const long long* cell_ptr = O[THR_TDSTATS_CELL_PTR].as<long long>();
     const double* x = d_x.as<double>();
     THR_HIP_TRY(O[THR_TDSTATS_ORDER].alloc(size_t(m) * 8));
     THR_HIP_TRY(O[THR_TDSTATS_STATS].alloc(size_t(nc) * 5 * 8));
-    hipLaunchKernelGGL(k_td_rows, grid_for(m), blk, 0, s, D, (const unsigned*)cells.perm.as<unsigned>(),
-                       (const unsigned*)d_sel.as<unsigned>(), m, O[THR_TDSTATS_ORDER].as<long long>(), d_x.as<double>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_td_rows, m, s, D, cells.perm.as<unsigned>(), d_sel.as<unsigned>(), m, O[THR_TDSTATS_ORDER].as<long long>(),
+                   d_x.as<double>()));
     THR_HIP_TRY(hipEventRecord(ev[2].e, s));
 
     // ---- 2. the statistics of every row
     Layout LC;
-    if (const int rc = build_layout(pos_cell, m, nc, w, LC, s)) return rc;
+    THR_TRY(build_layout(pos_cell, m, nc, w, LC, s));
     DevBuf d_slab, d_cv, d_cv2;
     THR_HIP_TRY(d_slab.alloc(size_t(LC.nf) * 5 * 8));
     THR_HIP_TRY(d_cv.alloc(size_t(nc) * 5 * 8));
     THR_HIP_TRY(d_cv2.alloc(size_t(nc) * 8));
-    if (const int rc = reduce<4, 2, 1>(LoadTd1{x}, LC, d_slab.as<double>(), d_cv.as<double>(), s)) return rc;
-    if (const int rc = reduce<1, 1, 0>(LoadTd2{x, (const double*)d_cv.as<double>(), pos_cell, cell_ptr}, LC, d_slab.as<double>(),
-                                       d_cv2.as<double>(), s))
-        return rc;
-    hipLaunchKernelGGL(k_td_fin, grid_for(nc), blk, 0, s, (const double*)d_cv.as<double>(), (const double*)d_cv2.as<double>(),
-                       cell_ptr, nc, O[THR_TDSTATS_STATS].as<double>());
-    THR_HIP_TRY(hipGetLastError());
+    const double* cv = d_cv.as<double>();
+    THR_TRY((reduce<4, 2, 1>(LoadTd1{x}, LC, d_slab.as<double>(), d_cv.as<double>(), s)));
+    THR_TRY((reduce<1, 1, 0>(LoadTd2{x, cv, pos_cell, cell_ptr}, LC, d_slab.as<double>(), d_cv2.as<double>(), s)));
+    THR_TRY(launch(k_td_fin, nc, s, cv, d_cv2.as<double>(), cell_ptr, nc, O[THR_TDSTATS_STATS].as<double>()));
     THR_HIP_TRY(hipEventRecord(ev[3].e, s));
 
     // ---- 3. the robust part
     if (robust) {
-        DevBuf d_sorted, d_dev;
-        THR_HIP_TRY(d_dev.alloc(size_t(m) * 8));
+        Work W{w};
+        THR_HIP_TRY(W.dev.alloc(size_t(m) * 8));
         THR_HIP_TRY(O[THR_TDSTATS_MEDIAN].alloc(size_t(nc) * 2 * 8));
         THR_HIP_TRY(O[THR_TDSTATS_MASK].alloc(size_t(m)));
         THR_HIP_TRY(O[THR_TDSTATS_ROBUST_STATS].alloc(size_t(nc) * 5 * 8));
         THR_HIP_TRY(O[THR_TDSTATS_ROBUST_COUNT].alloc(size_t(nc) * 8));
-        double* med = O[THR_TDSTATS_MEDIAN].as<double>();
+        Series SR;
+        SR.n = m;
+        SR.nc = nc;
+        SR.pos_cell = pos_cell;
+        SR.ptr = cell_ptr;
         const double* probe = O[THR_TDSTATS_STATS].as<double>() + 4;  // the cell's max: NaN when it holds one
-        if (const int rc = sort_by_cell_value(x, pos_cell, m, nc, w, d_sorted, s)) return rc;
-        hipLaunchKernelGGL(k_td_median, grid_for(nc), blk, 0, s, (const double*)d_sorted.as<double>(), cell_ptr, probe, 5, nc,
-                           med, 2);
-        THR_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_td_dev, grid_for(m), blk, 0, s, x, pos_cell, (const double*)med, m, d_dev.as<double>());
-        THR_HIP_TRY(hipGetLastError());
-        if (const int rc = sort_by_cell_value(d_dev.as<double>(), pos_cell, m, nc, w, d_sorted, s)) return rc;
-        hipLaunchKernelGGL(k_td_median, grid_for(nc), blk, 0, s, (const double*)d_sorted.as<double>(), cell_ptr, probe, 5, nc,
-                           med + 1, 2);
-        THR_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_td_mask, grid_for(m), blk, 0, s, (const double*)d_dev.as<double>(), pos_cell, cell_ptr,
-                           (const double*)med, m, O[THR_TDSTATS_MASK].as<unsigned char>());
-        THR_HIP_TRY(hipGetLastError());
         const unsigned char* mask = O[THR_TDSTATS_MASK].as<unsigned char>();
-        if (const int rc = reduce<5, 3, 1>(LoadRb1{x, mask}, LC, d_slab.as<double>(), d_cv.as<double>(), s)) return rc;
-        if (const int rc = reduce<1, 1, 0>(LoadRb2{x, (const double*)d_cv.as<double>(), mask, pos_cell}, LC, d_slab.as<double>(),
-                                           d_cv2.as<double>(), s))
-            return rc;
-        hipLaunchKernelGGL(k_rb_fin, grid_for(nc), blk, 0, s, (const double*)d_cv.as<double>(), (const double*)d_cv2.as<double>(),
-                           nc, O[THR_TDSTATS_ROBUST_STATS].as<double>(), O[THR_TDSTATS_ROBUST_COUNT].as<long long>());
-        THR_HIP_TRY(hipGetLastError());
-        THR_HIP_TRY(hipStreamSynchronize(s));  // d_sorted and d_dev go out of scope here
+        THR_TRY(outlier_mask(x, SR, probe, 5, 3.5, W, O[THR_TDSTATS_MEDIAN].as<double>(), 2, O[THR_TDSTATS_MASK].as<unsigned char>(), s));
+        THR_TRY((reduce<5, 3, 1>(LoadKept1<true>{x, mask}, LC, d_slab.as<double>(), d_cv.as<double>(), s)));
+        THR_TRY((reduce<1, 1, 0>(LoadKept2<true>{x, cv, mask, pos_cell}, LC, d_slab.as<double>(), d_cv2.as<double>(), s)));
+        THR_TRY(launch(k_rb_fin, nc, s, cv, d_cv2.as<double>(), nc, O[THR_TDSTATS_ROBUST_STATS].as<double>(),
+                       O[THR_TDSTATS_ROBUST_COUNT].as<long long>()));
+        THR_HIP_TRY(hipStreamSynchronize(s));  // W's buffers go out of scope here
     }
     THR_HIP_TRY(hipEventRecord(ev[4].e, s));
-    if (const int rc = record_times(ev, g_tdstats_ms)) return rc;
+    THR_TRY(record_times(ev, g_tdstats_ms));
 
     size_t* B = R->bytes;
     B[THR_TDSTATS_CELL_KEY] = size_t(nc) * 12;
@@ -983,42 +807,28 @@ extern "C" int thr_tdstats_fetch(thr_tdstats* R, int which, void* dst, size_t ds
     return thr::on_exception("thr_tdstats_fetch");
 }
 
-extern "C" void thr_tdstats_free(thr_tdstats* R) {
-    if (!R) return;
-    (void)hipSetDevice(R->device);
-    delete R;
-}
+extern "C" void thr_tdstats_free(thr_tdstats* R) { free_result(R); }
 
 extern "C" int thr_debug_beaconsync_times(double* ms_out) try {
-    if (!ms_out) return thr::fail_msg(THR_ERR_ARG, "thr_debug_beaconsync_times: null argument");
-    for (int i = 0; i < 5; ++i) ms_out[i] = g_bsync_ms[i];
-    return THR_OK;
+    return copy_times("thr_debug_beaconsync_times", g_bsync_ms, ms_out);
 } catch (...) {
     return thr::on_exception("thr_debug_beaconsync_times");
 }
 
 extern "C" int thr_debug_tdoastats_times(double* ms_out) try {
-    if (!ms_out) return thr::fail_msg(THR_ERR_ARG, "thr_debug_tdoastats_times: null argument");
-    for (int i = 0; i < 5; ++i) ms_out[i] = g_tdstats_ms[i];
-    return THR_OK;
+    return copy_times("thr_debug_tdoastats_times", g_tdstats_ms, ms_out);
 } catch (...) {
     return thr::on_exception("thr_debug_tdoastats_times");
 }
 
 extern "C" int thr_debug_beaconsync_geometry(int* tile_len, int* workgroup) try {
-    if (!tile_len || !workgroup) return thr::fail_msg(THR_ERR_ARG, "thr_debug_beaconsync_geometry: null argument");
-    *tile_len = kTile;
-    *workgroup = kBlock;
-    return THR_OK;
+    return geometry("thr_debug_beaconsync_geometry", tile_len, workgroup);
 } catch (...) {
     return thr::on_exception("thr_debug_beaconsync_geometry");
 }
 
 extern "C" int thr_debug_tdoastats_geometry(int* tile_len, int* workgroup) try {
-    if (!tile_len || !workgroup) return thr::fail_msg(THR_ERR_ARG, "thr_debug_tdoastats_geometry: null argument");
-    *tile_len = kTile;
-    *workgroup = kBlock;
-    return THR_OK;
+    return geometry("thr_debug_tdoastats_geometry", tile_len, workgroup);
 } catch (...) {
     return thr::on_exception("thr_debug_tdoastats_geometry");
 }

@@ -406,7 +406,7 @@ namespace {
 // sums cells' fragments, then receivers' cells
 int combine2(const double* slab, const int* cell_frag, int nc, const int* rx_cell, int nr, int K, int n_sum, int n_min,
              double* cv, double* rv, hipStream_t s) {
-    if (const int rc = launch_combine(slab, cell_frag, cell_frag + 1, 1, nc, K, n_sum, n_min, cv, s)) return rc;
+    THR_TRY(launch_combine(slab, cell_frag, cell_frag + 1, 1, nc, K, n_sum, n_min, cv, s));
     return launch_combine(cv, rx_cell, rx_cell + 1, 1, nr, K, n_sum, n_min, rv, s);
 }
 
@@ -449,13 +449,12 @@ extern "C" int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const
         return thr::fail_msg(THR_ERR_ARG, "thr_toadstats: the histograms would exceed 2^26 bins (timestamps span %g s)",
                              t_max - time0);
 
-    if (const int rc = pick_device(device_id)) return rc;
+    THR_TRY(pick_device(device_id));
     thr_tstats* R = new thr_tstats;
     ResultGuard guard{R};
     R->device = device_id;
     R->n_out = THR_TSTATS_N_OUTPUTS;
     hipStream_t s = nullptr;
-    const dim3 blk(kBlock);
     Event ev[5];
     for (Event& e : ev) THR_HIP_TRY(e.create());
     for (Event& e : R->ev) THR_HIP_TRY(e.create());
@@ -498,14 +497,12 @@ extern "C" int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const
     THR_HIP_TRY(d_tincl.alloc(size_t(m) * sizeof(Trip)));
     unsigned long long* keys = d_kb.as<unsigned long long>();
     unsigned* perm = d_perm.as<unsigned>();
-    hipLaunchKernelGGL(k_keys, grid_for(m), blk, 0, s, cols, m, d_ka.as<unsigned long long>(), d_ia.as<unsigned>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_keys, m, s, cols, m, d_ka.as<unsigned long long>(), d_ia.as<unsigned>()));
     THR_HIP_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
         return hipcub::DeviceRadixSort::SortPairs(t, b, d_ka.as<unsigned long long>(), keys, d_ia.as<unsigned>(), perm, m,
                                                   0, 64, s);
     }));
-    hipLaunchKernelGGL(k_heads, grid_for(m), blk, 0, s, keys, m, d_trip.as<Trip>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_heads, m, s, keys, m, d_trip.as<Trip>()));
     THR_HIP_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
         return hipcub::DeviceScan::InclusiveScan(t, b, d_trip.as<Trip>(), d_tincl.as<Trip>(), TripSum(), m, s);
     }));
@@ -535,14 +532,12 @@ extern "C" int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const
     const int *rx_ptr = d_rx_ptr.as<int>(), *frag_start = d_frag_start.as<int>();
     const int *pos_frag = d_pos_frag.as<int>(), *pos_cell = d_pos_cell.as<int>();
     const double* S = d_S.as<double>();
-    hipLaunchKernelGGL(k_layout, grid_for(m), blk, 0, s, keys, d_tincl.as<Trip>(), m, nc, nf, nr,
-                       O[THR_TSTATS_CELL_PTR].as<long long>(), O[THR_TSTATS_CELL_RX].as<int>(),
-                       O[THR_TSTATS_CELL_TX].as<int>(), d_cell_frag.as<int>(), d_cell_rxi.as<int>(), d_rx_cell.as<int>(),
-                       O[THR_TSTATS_RX_ID].as<int>(), d_rx_ptr.as<int>(), d_frag_start.as<int>(), d_pos_frag.as<int>(),
-                       d_pos_cell.as<int>());
-    hipLaunchKernelGGL(k_gather, grid_for(m), blk, 0, s, cols, perm, m, time0, d_S.as<double>(),
-                       O[THR_TSTATS_ORDER].as<long long>(), O[THR_TSTATS_SNR_DB].as<double>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_layout, m, s, keys, d_tincl.as<Trip>(), m, nc, nf, nr, O[THR_TSTATS_CELL_PTR].as<long long>(),
+                   O[THR_TSTATS_CELL_RX].as<int>(), O[THR_TSTATS_CELL_TX].as<int>(), d_cell_frag.as<int>(), d_cell_rxi.as<int>(),
+                   d_rx_cell.as<int>(), O[THR_TSTATS_RX_ID].as<int>(), d_rx_ptr.as<int>(), d_frag_start.as<int>(),
+                   d_pos_frag.as<int>(), d_pos_cell.as<int>()));
+    THR_TRY(launch(k_gather, m, s, cols, perm, m, time0, d_S.as<double>(), O[THR_TSTATS_ORDER].as<long long>(),
+                   O[THR_TSTATS_SNR_DB].as<double>()));
     THR_HIP_TRY(hipEventRecord(ev[2].e, s));
 
     // ---- 2. pass 1 and what follows from it
@@ -565,17 +560,11 @@ extern "C" int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const
     THR_HIP_TRY(O[THR_TSTATS_RESIDUAL].alloc(size_t(m) * 8));
     double* stats = O[THR_TSTATS_STATS].as<double>();
     long long *minute_ptr = O[THR_TSTATS_MINUTE_PTR].as<long long>(), *bin_ptr = O[THR_TSTATS_BIN_PTR].as<long long>();
-    if (const int rc = launch_reduce<kK1, kS1, kM1>(LoadPass1{S, size_t(m)}, m, pos_frag, frag_start, d_slab.as<double>(), s))
-        return rc;
-    if (const int rc = combine2(d_slab.as<double>(), cell_frag, nc, rx_cell, nr, kK1, kS1, kM1, d_cv.as<double>(),
-                                d_rv.as<double>(), s))
-        return rc;
-    hipLaunchKernelGGL(k_mid_cells, grid_for(nc), blk, 0, s, (const double*)d_cv.as<double>(), cell_ptr, nc, stats,
-                       d_mlen.as<long long>(), d_blen.as<long long>(), O[THR_TSTATS_BIN_FIRST].as<int>(),
-                       O[THR_TSTATS_OFFSET_EDGES].as<double>(), O[THR_TSTATS_CELL_FLAGS].as<int>());
-    hipLaunchKernelGGL(k_mid_rx, grid_for(nr), blk, 0, s, (const double*)d_rv.as<double>(), rx_ptr, nr,
-                       d_rxp.as<double>(), O[THR_TSTATS_RX_COUNT].as<long long>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY((launch_reduce<kK1, kS1, kM1>(LoadPass1{S, size_t(m)}, m, pos_frag, frag_start, d_slab.as<double>(), s)));
+    THR_TRY(combine2(d_slab.as<double>(), cell_frag, nc, rx_cell, nr, kK1, kS1, kM1, d_cv.as<double>(), d_rv.as<double>(), s));
+    THR_TRY(launch(k_mid_cells, nc, s, d_cv.as<double>(), cell_ptr, nc, stats, d_mlen.as<long long>(), d_blen.as<long long>(),
+                   O[THR_TSTATS_BIN_FIRST].as<int>(), O[THR_TSTATS_OFFSET_EDGES].as<double>(), O[THR_TSTATS_CELL_FLAGS].as<int>()));
+    THR_TRY(launch(k_mid_rx, nr, s, d_rv.as<double>(), rx_ptr, nr, d_rxp.as<double>(), O[THR_TSTATS_RX_COUNT].as<long long>()));
     THR_HIP_TRY(hipMemsetAsync(minute_ptr, 0, 8, s));
     THR_HIP_TRY(hipMemsetAsync(bin_ptr, 0, 8, s));
     THR_HIP_TRY(with_temp(d_tmp, tmp_bytes, [&](void* t, size_t& b) {
@@ -598,41 +587,27 @@ extern "C" int thr_toadstats(int device_id, size_t n, const int32_t* rxid, const
     THR_HIP_TRY(hipMemsetAsync(O[THR_TSTATS_MINUTE_HIST].p, 0, size_t(n_minute) * 8, s));
     THR_HIP_TRY(hipMemsetAsync(O[THR_TSTATS_BIN_HIST].p, 0, size_t(n_bin) * 8, s));
     THR_HIP_TRY(hipMemsetAsync(O[THR_TSTATS_OFFSET_HIST].p, 0, size_t(nc) * 10 * 8, s));
-    hipLaunchKernelGGL(k_pass2, tile_grid(n_tiles), blk, 0, s, S, m, n_tiles, pos_frag, frag_start, pos_cell,
-                       (const double*)stats, cell_rxi, (const double*)d_rxp.as<double>(), (const long long*)d_blen.as<long long>(), (const int*)O[THR_TSTATS_BIN_FIRST].as<int>(),
-                       (const double*)O[THR_TSTATS_OFFSET_EDGES].as<double>(),
-                       (const int*)O[THR_TSTATS_CELL_FLAGS].as<int>(), (const long long*)minute_ptr,
-                       (const long long*)bin_ptr, O[THR_TSTATS_MINUTE_HIST].as<unsigned long long>(),
-                       O[THR_TSTATS_BIN_HIST].as<unsigned long long>(),
-                       O[THR_TSTATS_OFFSET_HIST].as<unsigned long long>(), d_slab.as<double>());
-    THR_HIP_TRY(hipGetLastError());
-    if (const int rc = combine2(d_slab.as<double>(), cell_frag, nc, rx_cell, nr, kK2, kK2, 0, d_cv.as<double>(),
-                                d_rv.as<double>(), s))
-        return rc;
-    hipLaunchKernelGGL(k_fin_cells, grid_for(size_t(nc) * kQ), blk, 0, s, (const double*)d_cv.as<double>(), cell_ptr, nc,
-                       stats);
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch_grid(k_pass2, tile_grid(n_tiles), s, S, m, n_tiles, pos_frag, frag_start, pos_cell, stats, cell_rxi,
+                        d_rxp.as<double>(), d_blen.as<long long>(), O[THR_TSTATS_BIN_FIRST].as<int>(),
+                        O[THR_TSTATS_OFFSET_EDGES].as<double>(), O[THR_TSTATS_CELL_FLAGS].as<int>(), minute_ptr, bin_ptr,
+                        O[THR_TSTATS_MINUTE_HIST].as<unsigned long long>(), O[THR_TSTATS_BIN_HIST].as<unsigned long long>(),
+                        O[THR_TSTATS_OFFSET_HIST].as<unsigned long long>(), d_slab.as<double>()));
+    THR_TRY(combine2(d_slab.as<double>(), cell_frag, nc, rx_cell, nr, kK2, kK2, 0, d_cv.as<double>(), d_rv.as<double>(), s));
+    THR_TRY(launch(k_fin_cells, size_t(nc) * kQ, s, d_cv.as<double>(), cell_ptr, nc, stats));
     THR_HIP_TRY(hipEventRecord(ev[3].e, s));
 
     // ---- 3. the line, the residuals
     DevBuf d_line;
     THR_HIP_TRY(d_line.alloc(size_t(nr) * 2 * 8));
-    hipLaunchKernelGGL(k_fit_rx, grid_for(nr), blk, 0, s, (const double*)d_rv.as<double>(),
-                       (const long long*)O[THR_TSTATS_RX_COUNT].as<long long>(), (const double*)d_rxp.as<double>(), nr,
-                       d_line.as<double>(), O[THR_TSTATS_RX_FIT].as<double>());
-    THR_HIP_TRY(hipGetLastError());
-    if (const int rc = launch_reduce<kK3, 1, 0>(LoadPass3{S, size_t(m), pos_cell, cell_rxi, d_rxp.as<double>(), d_line.as<double>(),
-                                                           perm, O[THR_TSTATS_RESIDUAL].as<double>()},
-                                                m, pos_frag, frag_start, d_slab.as<double>(), s))
-        return rc;
-    if (const int rc = combine2(d_slab.as<double>(), cell_frag, nc, rx_cell, nr, kK3, 1, 0, d_cv.as<double>(),
-                                d_rv.as<double>(), s))
-        return rc;
-    hipLaunchKernelGGL(k_fin_rx, grid_for(nr), blk, 0, s, (const double*)d_rv.as<double>(),
-                       (const long long*)O[THR_TSTATS_RX_COUNT].as<long long>(), nr, O[THR_TSTATS_RX_FIT].as<double>());
-    THR_HIP_TRY(hipGetLastError());
+    THR_TRY(launch(k_fit_rx, nr, s, d_rv.as<double>(), O[THR_TSTATS_RX_COUNT].as<long long>(), d_rxp.as<double>(), nr,
+                   d_line.as<double>(), O[THR_TSTATS_RX_FIT].as<double>()));
+    THR_TRY((launch_reduce<kK3, 1, 0>(LoadPass3{S, size_t(m), pos_cell, cell_rxi, d_rxp.as<double>(), d_line.as<double>(), perm,
+                                                O[THR_TSTATS_RESIDUAL].as<double>()},
+                                      m, pos_frag, frag_start, d_slab.as<double>(), s)));
+    THR_TRY(combine2(d_slab.as<double>(), cell_frag, nc, rx_cell, nr, kK3, 1, 0, d_cv.as<double>(), d_rv.as<double>(), s));
+    THR_TRY(launch(k_fin_rx, nr, s, d_rv.as<double>(), O[THR_TSTATS_RX_COUNT].as<long long>(), nr, O[THR_TSTATS_RX_FIT].as<double>()));
     THR_HIP_TRY(hipEventRecord(ev[4].e, s));
-    if (const int rc = record_times(ev, g_times_ms)) return rc;  // synchronises: the temporaries go out of scope
+    THR_TRY(record_times(ev, g_times_ms));  // synchronises: the temporaries go out of scope
 
     size_t* B = R->bytes;
     B[THR_TSTATS_CELL_RX] = B[THR_TSTATS_CELL_TX] = B[THR_TSTATS_BIN_FIRST] = B[THR_TSTATS_CELL_FLAGS] = size_t(nc) * 4;
@@ -669,25 +644,16 @@ extern "C" int thr_tstats_fetch(thr_tstats* R, int which, void* dst, size_t dst_
     return thr::on_exception("thr_tstats_fetch");
 }
 
-extern "C" void thr_tstats_free(thr_tstats* R) {
-    if (!R) return;
-    (void)hipSetDevice(R->device);  // the buffers are freed on the device they were taken from
-    delete R;
-}
+extern "C" void thr_tstats_free(thr_tstats* R) { free_result(R); }
 
 extern "C" int thr_debug_toadstats_times(double* ms_out) try {
-    if (!ms_out) return thr::fail_msg(THR_ERR_ARG, "thr_debug_toadstats_times: null argument");
-    for (int i = 0; i < 5; ++i) ms_out[i] = g_times_ms[i];
-    return THR_OK;
+    return copy_times("thr_debug_toadstats_times", g_times_ms, ms_out);
 } catch (...) {
     return thr::on_exception("thr_debug_toadstats_times");
 }
 
 extern "C" int thr_debug_toadstats_geometry(int* tile_len, int* workgroup) try {
-    if (!tile_len || !workgroup) return thr::fail_msg(THR_ERR_ARG, "thr_debug_toadstats_geometry: null argument");
-    *tile_len = kTile;
-    *workgroup = kBlock;
-    return THR_OK;
+    return geometry("thr_debug_toadstats_geometry", tile_len, workgroup);
 } catch (...) {
     return thr::on_exception("thr_debug_toadstats_geometry");
 }
