@@ -6,6 +6,7 @@ Measured (MI355X), rel-L2 of mean_mag against the float64 oracle, largest interv
 1.53e-6 (bytes 126..129) against bounds of 5.2e-6 and 1.0e-5; fold path 7.2e-8 at 1024 and 1.7e-7 at 65536; fused
 against fold 5.3e-7.  Every case prints its figure before it asserts (pytest -s)."""
 import io
+import mmap
 import os
 import subprocess
 import sys
@@ -146,9 +147,9 @@ def test_raw_stream_equals_packed_blocks(sv):
             got = s.feed_stream(stream)
             assert all(np.array_equal(a, b) for a, b in zip(got, want))
             # through the handle's input window (64 KiB segments: several per chunk)
-            room = np.empty(len(stream) + 4096, dtype=np.uint8)
-            off = -room.ctypes.data % 4096
-            pinned = room[off:off + len(stream)]
+            # (a mapping of its own: the window page-locks whole pages, and a heap array's last page can
+            # hold the start of a result array, a copy into which would then be refused)
+            pinned = np.frombuffer(mmap.mmap(-1, len(stream)), dtype=np.uint8)
             pinned[:] = stream
             e.input_window(pinned, segment_bytes=1 << 16)
             s.reset()

@@ -120,6 +120,44 @@ def test_interval_properties():
     assert np.array_equal(bins % n, np.fft.fftshift(np.arange(n)))
 
 
+SIGNATURE_CASES = [(64, 3), (64, 5), (1024, 3), (1024, 5), (16384, 1), (16384, 3), (16384, 4), (16384, 8), (16384, 20)]
+
+
+@pytest.mark.parametrize("n,k", SIGNATURE_CASES)
+def test_signature_blocks_name_their_rows_on_the_oracle(n, k):
+    """tests/test_gpu_survey_seams.py decides row assignment by the K largest bins of a row being the tone
+    bins of that row's blocks.  The oracle alone passes that, with room: the K-th tone bin is at least 4
+    times the largest other bin.  Smallest factor measured over these cases: 5.32 (n = 64, K = 5); 6.84 at
+    1024 (K = 5) and 7.62 at 16384 (K = 20)."""
+    nb = {20: 45, 1: 20}.get(k, 29)
+    blocks = survey_ref.signature_blocks(nb, n, seed=5)
+    assert blocks.shape == (nb, 2 * n) and blocks.dtype == np.uint8
+    tail = survey_ref.signature_tail(n)
+    for b in (0, 1, nb - 1):
+        assert np.all(blocks[b, 2 * n - tail:] == (7 * b + 1) % 256)
+    backend = survey_ref.RefBackend(n, 0, k)
+    parts = [backend.feed(blocks[lo:lo + 8]) for lo in range(0, nb, 8)]         # the stand-in's own open interval
+    spec, hist, sums = [np.concatenate([p[i] for p in parts]) for i in range(3)]
+    mean_mag, want_hist, want_sums = survey_ref.survey(blocks, k)
+    assert len(spec) == nb // k and np.array_equal(hist, want_hist) and np.array_equal(sums, want_sums)
+    worst = np.inf
+    for j in range(len(spec)):
+        assert survey_ref.top_bins(spec[j], k) == survey_ref.tone_bins(j, k, n), j
+        assert survey_ref.top_bins(mean_mag[j], k) == survey_ref.tone_bins(j, k, n), j
+        worst = min(worst, survey_ref.tone_margin(spec[j], j, k, n))
+    print("signature blocks n=%d K=%d: smallest tone margin %.2f" % (n, k, worst))
+    assert worst >= 4.0
+    # a row one block late holds another set of bins: the assertion tells the two apart
+    assert survey_ref.tone_bins(0, k, n) != sorted(survey_ref.tone_bin(b, n) for b in range(1, k + 1))
+
+
+def test_signature_blocks_refuse_a_window_with_a_repeated_bin():
+    assert len({survey_ref.tone_bin(b, 64) for b in range(32)}) == 32
+    assert survey_ref.tone_bin(32, 64) == survey_ref.tone_bin(0, 64)
+    with pytest.raises(AssertionError):
+        survey_ref.tone_bins(0, 33, 64)
+
+
 def test_parser_and_command_line(tmp_path):
     parser = survey.build_parser()
     assert parser.get_default("integrate") == 100 and parser.get_default("output") is None
