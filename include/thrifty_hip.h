@@ -89,7 +89,10 @@ extern "C" {
  *      (tdoa_est.py:108-222); thr_post_settings.reserved (always 0) is now .tdoa_model, 0 = the polynomial
  *    + thr_reldist / thr_reldist_fetch / thr_reldist_free / thr_debug_reldist_times / _geometry -- the numbers
  *      of the reference's scripts/reldist_nearest.py (position along a baseline relative to a beacon, speed,
- *      carrier Doppler, both smoothed) for every (mobile, beacon, rx0 < rx1) cell in one call */
+ *      carrier Doppler, both smoothed) for every (mobile, beacon, rx0 < rx1) cell in one call
+ *    + thr_posq / thr_posq_fetch / thr_posq_free / thr_debug_posq_times -- thr_pos's 2-D solve with row weights,
+ *      the residuals, the inverse normal matrix, and the exclusion of one receiver whose arrivals contradict
+ *      the others (the open items of the reference's pos_est.py) */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -1523,6 +1526,71 @@ void thr_reldist_free(thr_reldist_result* result);
 int thr_debug_reldist_times(double* ms_out /* [5] */);
 /* tile length of the reductions, workgroup size, lanes that share one smoothed point */
 int thr_debug_reldist_geometry(int* tile_len, int* workgroup, int* point_lanes);
+
+/* ---- Position quality: thr_pos's 2-D solve with optional row weights, every row's residual, inv(A), and the
+ * exclusion of one receiver whose arrivals contradict the rest.  Host columns in, synchronous, the results stay
+ * on the device behind a handle until thr_posq_fetch (the pattern of thr_reldist).  The columns are thr_pos's;
+ * dims must be 2 (THR_ERR_ARG otherwise).  row_weight: NULL, or one finite weight >= 0 per row.
+ *   A TASK is a group solved over a subset of its rows from opts->x0 inside thr_pos's box, by thr_pos's own
+ *   iteration (csrc/pos_lm.hpp).  Row i of a task counts w_i * (m_used / sum of the task's w): the sum in team
+ *   order, then ONE division, so a column of ones is the unweighted solve to the bit; a zero sum ends as
+ *   THR_POS_NONFINITE.  F = sum w r^2, A = sum w g g'; rms = sqrt(F / m_used) with the last accepted F;
+ *   q = inv(A) = {a11 / det, -a01 / det, a00 / det}, NaN (and dop = -1) where det is 0 or not finite; dop is
+ *   thr_pos's expression on A.
+ *   1. every group is solved in full.
+ *   2. a group is FLAGGED when gate_m > 0, its full status is neither UNDERDETERMINED nor NONFINITE, it names
+ *      at least min_rx distinct receivers and rms_full > gate_m.  gate_m == 0: no exclusion.
+ *   3. a flagged group gets one candidate task per receiver it names (ascending dense index): the group
+ *      without the rows that name that receiver.
+ *   4. a candidate is eligible when its status is THR_POS_OK and it names at least min_rx - 1 receivers; the
+ *      best one has the smallest rms (the lowest receiver on ties); its receiver is excluded iff
+ *      rms_best <= ratio * rms_full.
+ *   5. every row's residual tdoa c - (|rx0 - p| - |rx1 - p|) at the chosen position, and whether the row was used.
+ * ratio in (0, 1], min_rx in 5 .. 64, gate_m >= 0 and finite, max_iter >= 0: THR_ERR_ARG otherwise. */
+typedef struct thr_posq_opts {
+    int32_t max_iter, min_rx;
+    double x0[2];
+    double gate_m, ratio;
+} thr_posq_opts;
+typedef struct thr_posq_counts {
+    size_t groups, rows, flagged, tasks;
+} thr_posq_counts;
+typedef struct thr_posq_result thr_posq_result; /* the handle: thr_posq is the call */
+#define THR_POSQ_INCONSISTENT 1 /* flagged */
+#define THR_POSQ_EXCLUDED 2     /* a receiver was excluded: pos, dop, status, iters, q, rms[1] are the candidate's */
+#define THR_POSQ_NO_CANDIDATE 4 /* flagged, but no candidate was eligible or the ratio was not met */
+/* what thr_posq_fetch copies, in terms of thr_posq_counts */
+#define THR_POSQ_POS 0          /* float64[groups][2]: the chosen position */
+#define THR_POSQ_DOP 1          /* float64[groups] */
+#define THR_POSQ_STATUS 2       /* int32[groups], THR_POS_* */
+#define THR_POSQ_ITERS 3        /* int32[groups] */
+#define THR_POSQ_Q 4            /* float64[groups][3]: q00, q01, q11 */
+#define THR_POSQ_RMS 5          /* float64[groups][2]: rms_full, rms of the chosen task */
+#define THR_POSQ_COUNTS 6       /* int32[groups][3]: receivers and rows of the chosen task, excluded dense index or -1 */
+#define THR_POSQ_FLAGS 7        /* int32[groups], THR_POSQ_INCONSISTENT | _EXCLUDED | _NO_CANDIDATE */
+#define THR_POSQ_FULL_POS 8     /* float64[groups][2]: the full solve */
+#define THR_POSQ_FULL_STATUS 9  /* int32[groups] */
+#define THR_POSQ_SNR 10         /* float64[groups]: the mean over all rows, as thr_pos */
+#define THR_POSQ_RESIDUAL 11    /* float64[rows], metres, at the chosen position */
+#define THR_POSQ_USED 12        /* uint8[rows]: 1 = the row belongs to the chosen task */
+#define THR_POSQ_TASK_PTR 13    /* int64[groups + 1] into the candidates */
+#define THR_POSQ_TASK_RX 14     /* int32[tasks]: the receiver left out (dense index) */
+#define THR_POSQ_TASK_POS 15    /* float64[tasks][2] */
+#define THR_POSQ_TASK_RMS 16    /* float64[tasks] */
+#define THR_POSQ_TASK_STATUS 17 /* int32[tasks] */
+#define THR_POSQ_TASK_NRX 18    /* int32[tasks]: distinct receivers of the candidate's rows */
+#define THR_POSQ_TASK_ITERS 19  /* int32[tasks] */
+#define THR_POSQ_N_OUTPUTS 20
+int thr_posq(int device_id, size_t n_groups, const int64_t* group_ptr, const int32_t* row_rx0, const int32_t* row_rx1,
+             const double* row_tdoa, const double* row_snr, const double* row_weight /* NULL: unweighted */, int n_rx,
+             int dims, const double* rx_coords, const thr_posq_opts* opts, thr_posq_result** result_out,
+             thr_posq_counts* counts_out);
+/* `which` is a THR_POSQ_* index; dst_bytes must be the size given there */
+int thr_posq_fetch(thr_posq_result* result, int which, void* dst, size_t dst_bytes);
+void thr_posq_free(thr_posq_result* result);
+/* Milliseconds of the calling thread's last thr_posq: {copies in, full solves, flags and expansion, candidates,
+ * choice and residuals, copies out (summed over the fetches)} */
+int thr_debug_posq_times(double* ms_out /* [6] */);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,7 @@ EXPORTS = [
     "thr_dossier_create", "thr_dossier_destroy", "thr_dossier_reset", "thr_dossier_feed", "thr_dossier_feed_card",
     "thr_dossier_feed_stream", "thr_dossier_result", "thr_dossier_geometry",
     "thr_reldist", "thr_reldist_fetch", "thr_reldist_free", "thr_debug_reldist_times", "thr_debug_reldist_geometry",
+    "thr_posq", "thr_posq_fetch", "thr_posq_free", "thr_debug_posq_times",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -67,6 +68,7 @@ CARD_HEADER_MAX = 48    # THR_CARD_HEADER_MAX
 BSYNC_COUNTS = ("rows", "cells", "discontinuities", "cuts")
 TDSTATS_COUNTS = ("rows", "cells", "robust")
 RELDIST_COUNTS = ("rows", "cells", "speeds", "speed_points", "dop_points")
+POSQ_COUNTS = ("groups", "rows", "flagged", "tasks")
 
 
 class ThrBsyncCounts(C.Structure):        # thr_bsync_counts
@@ -79,6 +81,15 @@ class ThrTdstatsCounts(C.Structure):      # thr_tdstats_counts
 
 class ThrReldistCounts(C.Structure):      # thr_reldist_counts
     _fields_ = [(name, C.c_size_t) for name in RELDIST_COUNTS]
+
+
+class ThrPosqCounts(C.Structure):         # thr_posq_counts
+    _fields_ = [(name, C.c_size_t) for name in POSQ_COUNTS]
+
+
+class ThrPosqOpts(C.Structure):           # thr_posq_opts
+    _fields_ = [("max_iter", C.c_int32), ("min_rx", C.c_int32), ("x0", C.c_double * 2), ("gate_m", C.c_double),
+                ("ratio", C.c_double)]
 
 
 class ThrReldistGeom(C.Structure):        # thr_reldist_geom
@@ -391,7 +402,10 @@ def load_library():
                                 [C.POINTER(ThrReldistOpts), C.POINTER(vp), C.POINTER(ThrReldistCounts)])
     lib.thr_debug_reldist_times.argtypes = [C.POINTER(C.c_double)]
     lib.thr_debug_reldist_geometry.argtypes = [ip, ip, ip]
-    for stem in ("bsync", "tdstats", "reldist"):
+    lib.thr_posq.argtypes = ([C.c_int, C.c_size_t] + [vp] * 6 + [C.c_int, C.c_int, vp, C.POINTER(ThrPosqOpts), C.POINTER(vp),
+                             C.POINTER(ThrPosqCounts)])
+    lib.thr_debug_posq_times.argtypes = [C.POINTER(C.c_double)]
+    for stem in ("bsync", "tdstats", "reldist", "posq"):
         getattr(lib, "thr_%s_fetch" % stem).argtypes = [vp, C.c_int, vp, C.c_size_t]
         getattr(lib, "thr_%s_free" % stem).argtypes = [vp]
         getattr(lib, "thr_%s_free" % stem).restype = None
@@ -2031,3 +2045,70 @@ def reldist_geometry():
     t, w, lanes = C.c_int(), C.c_int(), C.c_int()
     _check(lib, lib.thr_debug_reldist_geometry(C.byref(t), C.byref(w), C.byref(lanes)))
     return t.value, w.value, lanes.value
+
+
+POSQ_INCONSISTENT, POSQ_EXCLUDED, POSQ_NO_CANDIDATE = 1, 2, 4      # THR_POSQ_* flags
+POSQ_MIN_RX = 5         # the floor of min_rx: one of five receivers left out leaves four, one redundant arrival
+# THR_POSQ_*: name -> (index, dtype, shape as a function of the counts)
+POSQ_OUTPUTS = {
+    "pos": (0, np.float64, lambda c: (c["groups"], 2)),
+    "dop": (1, np.float64, lambda c: (c["groups"],)),
+    "status": (2, np.int32, lambda c: (c["groups"],)),
+    "iters": (3, np.int32, lambda c: (c["groups"],)),
+    "q": (4, np.float64, lambda c: (c["groups"], 3)),
+    "rms": (5, np.float64, lambda c: (c["groups"], 2)),
+    "counts": (6, np.int32, lambda c: (c["groups"], 3)),
+    "flags": (7, np.int32, lambda c: (c["groups"],)),
+    "full_pos": (8, np.float64, lambda c: (c["groups"], 2)),
+    "full_status": (9, np.int32, lambda c: (c["groups"],)),
+    "snr": (10, np.float64, lambda c: (c["groups"],)),
+    "residual": (11, np.float64, lambda c: (c["rows"],)),
+    "used": (12, np.uint8, lambda c: (c["rows"],)),
+    "task_ptr": (13, np.int64, lambda c: (c["groups"] + 1,)),
+    "task_rx": (14, np.int32, lambda c: (c["tasks"],)),
+    "task_pos": (15, np.float64, lambda c: (c["tasks"], 2)),
+    "task_rms": (16, np.float64, lambda c: (c["tasks"],)),
+    "task_status": (17, np.int32, lambda c: (c["tasks"],)),
+    "task_nrx": (18, np.int32, lambda c: (c["tasks"],)),
+    "task_iters": (19, np.int32, lambda c: (c["tasks"],)),
+}
+
+
+def posq(group_ptr, row_rx0, row_rx1, row_tdoa, row_snr, rx_coords, row_weight=None, gate_m=0.0, ratio=0.5, min_rx=POSQ_MIN_RX,
+         x0=(0.1, 0.1), max_iter=100, outputs=None, device_id=0):
+    """thr_posq on TDOA rows in CSR form (thr_pos's columns: dense receiver indices into rx_coords[n_rx, 2]) with an
+    optional weight per row -> (counts dict, {name: array}) with every output of POSQ_OUTPUTS (or those named in
+    `outputs`) fetched.  gate_m == 0 switches the exclusion off.  ValueError for what thr_posq refuses."""
+    lib = load_library()
+    ptr = np.ascontiguousarray(group_ptr, dtype=np.int64)
+    rx0, rx1 = np.ascontiguousarray(row_rx0, dtype=np.int32), np.ascontiguousarray(row_rx1, dtype=np.int32)
+    tdoa, snr = np.ascontiguousarray(row_tdoa, dtype=np.float64), np.ascontiguousarray(row_snr, dtype=np.float64)
+    weight = None if row_weight is None else np.ascontiguousarray(row_weight, dtype=np.float64)
+    xy = np.ascontiguousarray(rx_coords, dtype=np.float64)
+    if ptr.ndim != 1 or len(ptr) < 1 or xy.ndim != 2 or not (len(rx0) == len(rx1) == len(tdoa) == len(snr) == int(ptr[-1])):
+        raise ValueError("posq: group_ptr, the row columns or rx_coords have the wrong shape")
+    if weight is not None and weight.shape != tdoa.shape:
+        raise ValueError("posq: one weight per row")
+    start = np.ascontiguousarray(x0, dtype=np.float64)
+    if start.shape != (2,):
+        raise ValueError("posq: x0 holds two values")
+    opts = ThrPosqOpts(int(max_iter), int(min_rx), (C.c_double * 2)(*start.tolist()), float(gate_m), float(ratio))
+    keep = np.zeros(1, dtype=np.float64)      # an empty column still needs a pointer that is not NULL
+    handle, counts = C.c_void_p(), ThrPosqCounts()
+    rc = lib.thr_posq(int(device_id), len(ptr) - 1, ptr.ctypes.data, rx0.ctypes.data, rx1.ctypes.data, tdoa.ctypes.data,
+                      snr.ctypes.data, None if weight is None else (weight.ctypes.data if len(weight) else keep.ctypes.data),
+                      xy.shape[0], xy.shape[1], xy.ctypes.data, C.byref(opts), C.byref(handle), C.byref(counts))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    c = {name: int(getattr(counts, name)) for name in POSQ_COUNTS}
+    return c, _fetch_all(lib, "posq", handle, c, POSQ_OUTPUTS, outputs)
+
+
+def posq_times():
+    """Milliseconds (HIP events) of this thread's last posq(): copies in, full solves, flags and expansion, candidates,
+    choice and residuals, copies out."""
+    lib = load_library()
+    ms = (C.c_double * 6)()
+    _check(lib, lib.thr_debug_posq_times(ms))
+    return tuple(ms)

@@ -5,21 +5,9 @@
 // all eight from identical inputs, so a team's control flow is uniform.
 //
 // 2-D: minimise sum (tdoa_i c - (|rx0_i - p| - |rx1_i - p|))^2 from x0 inside the reference's box
-// (min(rx) - 10 km .. max(rx) + 10 km).  Not SciPy's TRF: a Levenberg-Marquardt iteration of our own.
-//   * an evaluation at p gives six team sums: the cost F, the normal matrix A = G'G, the gradient g = G'r;
-//   * an axis on which p sits on the box while -g points out of it is held (the step solves the other axis);
-//   * the undamped (Gauss-Newton) step h_gn is looked at first.  Where it is shorter than
-//     kGaussNewtonGate (|p| + 1) the damping is at its floor, zero: the cost resolves the position only to
-//     about sqrt(eps) of its scale, so from here on the step is taken without asking the cost, and the
-//     iteration ends when such a step is shorter than kStepTol (|p| + 1).  The gate looks at the step,
-//     not at mu (Nielsen's mu is still far from any floor when the cost stops resolving), and it is
-//     decided afresh in every iteration: far from a minimum h_gn is long (or NaN) and the judged branch
-//     runs; an unjudged step moves p by kGaussNewtonGate (|p| + 1) at most;
-//   * otherwise the damped step (A + mu I) h = -g, projected into the box, is accepted when the cost
-//     decreases, and mu follows the gain ratio (Nielsen's rule).
-// Every comparison is written so that a NaN takes the branch that ends or does not accept; the loop runs
-// max_iter times at most.  All lanes of a wave execute every evaluation (a finished team's state is held
-// by selects), so the DPP sums never read a disabled lane.
+// (min(rx) - 10 km .. max(rx) + 10 km).  Not SciPy's TRF: a Levenberg-Marquardt iteration of our own, stated
+// once in csrc/pos_lm.hpp (thr_posq's solves are the same template): evaluation, hold / step / gate / damping
+// rules, the stopping rule, the statuses and the closed-form dop.  Here it runs with no weights and every row on.
 // 1-D (two receivers): the reference's three float64 operations in its order, no iteration.
 // dop = sqrt(trace(inv(G'G))) at the estimate, closed form; -1 where the determinant is 0 or not finite.
 #include <hip/hip_runtime.h>
@@ -30,6 +18,7 @@
 
 #include "../../include/thrifty_hip.h"
 #include "lmdif8.hpp"
+#include "pos_lm.hpp"
 #include "post_stages.hpp"
 
 // the team's lanes must agree bit for bit and the 1-D result must equal numpy's: no a * b + c may become
@@ -40,54 +29,17 @@ namespace {
 
 using thr::DevBuf;
 using thr::Event;
-using thr::group8_sum;
 
 constexpr int kBlock = 256;                // workgroup size
 constexpr int kTeam = 8;                    // lanes per group
 constexpr int kTeams = kBlock / kTeam;      // groups per workgroup (_native.POS_GROUPS_PER_WORKGROUP)
 constexpr int kRegRows = 4;                 // rows per lane kept in registers: groups up to 32 rows (_native.POS_REGISTER_ROWS)
 constexpr int kMaxReceivers = 64;           // the distinct-receiver count is a popcount of a 64-bit mask
-constexpr double kSpeedOfLight = 2.997e8;   // the reference's constant (tdoa_est.py:25)
 constexpr double kMaxDist = 10e3;           // pos_est.py:24
-constexpr double kStepTol = 1e-13;          // the iteration ends on a step below kStepTol (|p| + 1)
-constexpr double kGaussNewtonGate = 1e-4;   // undamped steps below kGaussNewtonGate (|p| + 1) are taken unjudged
-constexpr double kMuStart = 1e-3;           // initial damping, relative to the larger diagonal entry of A
-constexpr double kMuMax = 1e100;            // (A + mu I)'s determinant stays finite
-
-enum Status : int { kOk = 0, kUnderdetermined = 1, kUnconverged = 2, kAtBound = 3, kNonfinite = 4 };
-
-struct Row {
-    double ax, ay, bx, by, tc;  // rx0, rx1 and tdoa * c
-};
-struct Sums {
-    double F, a00, a01, a11, g0, g1;
-};
-
-// one row's terms at (px, py), added to the lane's partial sums when `on`
-__device__ __forceinline__ void add_row(const Row& r, bool on, double px, double py, Sums& s) {
-    const double ax = r.ax - px, ay = r.ay - py, bx = r.bx - px, by = r.by - py;
-    const double da = sqrt(ax * ax + ay * ay), db = sqrt(bx * bx + by * by);
-    const double res = r.tc - (da - db);
-    const double gx = ax / da - bx / db, gy = ay / da - by / db;
-    s.F += on ? res * res : 0.0;
-    s.a00 += on ? gx * gx : 0.0;
-    s.a01 += on ? gx * gy : 0.0;
-    s.a11 += on ? gy * gy : 0.0;
-    s.g0 += on ? gx * res : 0.0;
-    s.g1 += on ? gy * res : 0.0;
-}
-
-__device__ __forceinline__ Row load_row(const int* __restrict__ rx0, const int* __restrict__ rx1,
-                                        const double* __restrict__ tdoa, const double* __restrict__ xy, long long i) {
-    const int a = rx0[i], b = rx1[i];
-    return Row{xy[2 * a], xy[2 * a + 1], xy[2 * b], xy[2 * b + 1], tdoa[i] * kSpeedOfLight};
-}
-
-__device__ __forceinline__ bool finite6(const Sums& s) {
-    return isfinite(s.F) && isfinite(s.a00) && isfinite(s.a01) && isfinite(s.a11) && isfinite(s.g0) && isfinite(s.g1);
-}
-
-__device__ __forceinline__ double clamp(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
+using thr::poslm::kSpeedOfLight;
+using thr::poslm::kOk;
+using thr::poslm::kNonfinite;
+static_assert(kTeam == thr::poslm::kTeam, "the team of pos_lm.hpp");
 
 // group g = one team.  group_ptr, row_rx0 / row_rx1 (< n_rx) and the table were checked on the host.
 __global__ __launch_bounds__(kBlock) void k_pos2d(const long long* __restrict__ group_ptr, const int* __restrict__ rx0,
@@ -101,127 +53,16 @@ __global__ __launch_bounds__(kBlock) void k_pos2d(const long long* __restrict__ 
     const bool live = team < n_groups;
     const long long beg = live ? group_ptr[team] : 0;
     const int m = live ? int(group_ptr[team + 1] - beg) : 0;
-
-    // ---- rows, the receivers' mask and the snr sum
-    Row reg[kRegRows];
-    unsigned long long mask = 0;
-    double snr_sum = 0.0;
-#pragma unroll
-    for (int k = 0; k < kRegRows; ++k) {
-        const int r = j + kTeam * k;
-        reg[k] = Row{1.0, 0.0, 0.0, 1.0, 0.0};
-        if (r < m) {
-            reg[k] = load_row(rx0, rx1, tdoa, xy, beg + r);
-            mask |= (1ull << rx0[beg + r]) | (1ull << rx1[beg + r]);
-            snr_sum += snr[beg + r];
-        }
-    }
-    for (int r = j + kTeam * kRegRows; r < m; r += kTeam) {
-        mask |= (1ull << rx0[beg + r]) | (1ull << rx1[beg + r]);
-        snr_sum += snr[beg + r];
-    }
-    unsigned mlo = unsigned(mask), mhi = unsigned(mask >> 32);
-#pragma unroll
-    for (int d = 1; d < kTeam; d <<= 1) {
-        mlo |= __shfl_xor(mlo, d, 64);
-        mhi |= __shfl_xor(mhi, d, 64);
-    }
-    const int n_distinct = __popc(mlo) + __popc(mhi);
-    const double snr_mean = group8_sum(snr_sum) / double(m);
-
-    auto evaluate = [&](double px, double py) {
-        Sums s{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int k = 0; k < kRegRows; ++k) add_row(reg[k], j + kTeam * k < m, px, py, s);
-        for (int r = j + kTeam * kRegRows; r < m; r += kTeam)  // long groups re-read their rows
-            add_row(load_row(rx0, rx1, tdoa, xy, beg + r), true, px, py, s);
-        return Sums{group8_sum(s.F), group8_sum(s.a00), group8_sum(s.a01), group8_sum(s.a11), group8_sum(s.g0),
-                    group8_sum(s.g1)};
-    };
-
-    double p0 = x0, p1 = y0;
-    Sums cur = evaluate(p0, p1);
-    int status = kUnconverged, iters = 0;
-    bool active = live;
-    if (n_distinct < 3) {
-        status = kUnderdetermined;
-        active = false;
-    } else if (!finite6(cur)) {
-        status = kNonfinite;
-        active = false;
-    }
-    double mu = kMuStart * fmax(cur.a00, cur.a11), nu = 2.0;
-
-    for (int it = 0; it < max_iter; ++it) {
-        if (!__any(active)) break;
-        // ---- the step, from identical values in the team's eight lanes
-        const bool zero_grad = fmax(fabs(cur.g0), fabs(cur.g1)) == 0.0;
-        const bool hold0 = (p0 <= lo0 && cur.g0 > 0.0) || (p0 >= hi0 && cur.g0 < 0.0);
-        const bool hold1 = (p1 <= lo1 && cur.g1 > 0.0) || (p1 >= hi1 && cur.g1 < 0.0);
-        const double scale = sqrt(p0 * p0 + p1 * p1) + 1.0;
-        double h0, h1;
-        auto solve = [&](double damp) {
-            const double a = cur.a00 + damp, d = cur.a11 + damp;
-            if (hold0 || hold1) {
-                h0 = hold0 ? 0.0 : -cur.g0 / a;
-                h1 = hold1 ? 0.0 : -cur.g1 / d;
-            } else {
-                const double det = a * d - cur.a01 * cur.a01;
-                h0 = (cur.a01 * cur.g1 - d * cur.g0) / det;
-                h1 = (cur.a01 * cur.g0 - a * cur.g1) / det;
-            }
-            h0 = clamp(p0 + h0, lo0, hi0) - p0;
-            h1 = clamp(p1 + h1, lo1, hi1) - p1;
-            return sqrt(h0 * h0 + h1 * h1);
-        };
-        double len = solve(0.0);
-        const bool gauss_newton = len <= kGaussNewtonGate * scale;  // false for a NaN
-        if (!gauss_newton) len = solve(mu);
-        const double t0 = p0 + h0, t1 = p1 + h1;
-        const Sums trial = evaluate(t0, t1);  // every lane of the wave, finished teams too
-
-        if (active) {
-            iters = it + 1;
-            if (zero_grad || (hold0 && hold1)) {
-                status = kOk;
-                active = false;
-            } else if (!finite6(trial) || !isfinite(len)) {
-                status = kNonfinite;
-                active = false;
-            } else if (gauss_newton) {
-                p0 = t0, p1 = t1, cur = trial;
-                if (len <= kStepTol * scale) {
-                    status = kOk;
-                    active = false;
-                }
-            } else if (trial.F < cur.F) {
-                const double pred = -(2.0 * (h0 * cur.g0 + h1 * cur.g1) +
-                                      (h0 * (cur.a00 * h0 + cur.a01 * h1) + h1 * (cur.a01 * h0 + cur.a11 * h1)));
-                const double rho = (cur.F - trial.F) / pred, q = 2.0 * rho - 1.0;
-                mu *= fmin(fmax(1.0 / 3.0, 1.0 - q * q * q), 2.0);  // a NaN ratio: 1/3 (fmax drops the NaN)
-                nu = 2.0;
-                p0 = t0, p1 = t1, cur = trial;
-                if (len <= kStepTol * scale) {
-                    status = kOk;
-                    active = false;
-                }
-            } else {
-                mu = fmin(mu * nu, kMuMax);
-                nu = fmin(nu * 2.0, kMuMax);
-            }
-        }
-    }
-    if (status == kOk && (p0 <= lo0 || p0 >= hi0 || p1 <= lo1 || p1 >= hi1)) status = kAtBound;
-
-    const double det = cur.a00 * cur.a11 - cur.a01 * cur.a01;
-    const double dop = (det == 0.0 || !isfinite(det)) ? -1.0 : sqrt((cur.a00 + cur.a11) / det);
+    const thr::poslm::Fit fit = thr::poslm::solve_team<false, kRegRows>(
+        live, beg, m, j, rx0, rx1, tdoa, snr, nullptr, xy, x0, y0, thr::poslm::Box{lo0, lo1, hi0, hi1}, max_iter,
+        thr::poslm::AllRows{});
     if (live && j == 0) {
-        pos_out[2 * team] = p0;
-        pos_out[2 * team + 1] = p1;
-        dop_out[team] = dop;
-        snr_out[team] = snr_mean;
-        status_out[team] = status;
-        iters_out[team] = iters;
+        pos_out[2 * team] = fit.p0;
+        pos_out[2 * team + 1] = fit.p1;
+        dop_out[team] = thr::poslm::dop_of(fit.cur);
+        snr_out[team] = fit.snr_mean;
+        status_out[team] = fit.status;
+        iters_out[team] = fit.iters;
     }
 }
 
