@@ -92,7 +92,10 @@ extern "C" {
  *      carrier Doppler, both smoothed) for every (mobile, beacon, rx0 < rx1) cell in one call
  *    + thr_posq / thr_posq_fetch / thr_posq_free / thr_debug_posq_times -- thr_pos's 2-D solve with row weights,
  *      the residuals, the inverse normal matrix, and the exclusion of one receiver whose arrivals contradict
- *      the others (the open items of the reference's pos_est.py) */
+ *      the others (the open items of the reference's pos_est.py)
+ *    + thr_track / thr_track_fetch / thr_track_free / thr_debug_track_times / _geometry -- per transmitter a
+ *      constant-velocity Kalman filter over the positions in time order, a gate on the innovations and a
+ *      fixed-interval smoother (the last open item of the reference's pos_est.py) */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -1591,6 +1594,74 @@ void thr_posq_free(thr_posq_result* result);
 /* Milliseconds of the calling thread's last thr_posq: {copies in, full solves, flags and expansion, candidates,
  * choice and residuals, copies out (summed over the fetches)} */
 int thr_debug_posq_times(double* ms_out /* [6] */);
+
+/* ---- Tracks: per transmitter a constant-velocity Kalman filter over positions in time order, a gate that leaves
+ * out the positions the track contradicts, and a fixed-interval (Rauch-Tung-Striebel) smoother.  Host columns in,
+ * synchronous, the results stay on the device behind a handle until thr_track_fetch (the pattern of thr_reldist).
+ * 2-D only.  Both recursions run as segmented scans of an associative operator (csrc/track_scan.hpp).
+ *   input   one row per position: tx, a finite timestamp (seconds), x, y (metres), the measurement variances rx,
+ *           ry of the two axes (m^2; finite and > 0 on valid rows, as x and y are finite there), valid (NULL: all).
+ *   order   rows are sorted by (tx, timestamp), rows of equal keys in their input order.  A TRACK is one tx.  It
+ *           starts at its first valid row; the rows before it, and every row of a track without a valid row, are
+ *           NOT TRACKED: their states and nis are NaN, used is 0.
+ *   model   the axes are filtered independently and share one mask.  Per axis s = [p, v]; between consecutive rows
+ *           dt = t_k - t_(k-1) >= 0, F = [[1, dt], [0, 1]], Q = q [[dt^3/3, dt^2/2], [dt^2/2, dt]]; a row in the
+ *           mask is a measurement z = p + noise of variance r, a row outside it a pure prediction.  The start row
+ *           has m = [z, 0], P = diag(r, v0^2).
+ *   nis     nu_x^2 / S_x + nu_y^2 / S_y with nu = z - (F m)[0] and S = (F P F' + Q)[0][0] + r from the state of the
+ *           row before; 0 at the start row, NaN on rows that are invalid or not tracked.
+ *   gate    mask_0 = valid.  Round i filters with mask_(i-1), then mask_i = valid & (start | nis_i <= gate) over
+ *           ALL rows, so a rejected row can come back.  The rounds end when the mask no longer changes (converged);
+ *           otherwise, after max_rounds rounds, one more filter runs with the last mask.  rounds = the filter runs;
+ *           nis and used are the last one's.  gate == 0: no gating, one run.  A converged track no longer changes,
+ *           so a track's result does not depend on the other tracks of the call.
+ *   smooth  RTS over the last filter run: G_k = P_k F' inv(F P_k F' + Q) with the F, Q of row k + 1.
+ *   stats   per track {rows, valid rows, used rows, rejected rows (valid, tracked, not used), mean nis of the used
+ *           rows, duration (last row's timestamp - start row's), path length (sum of the distances between
+ *           consecutive smoothed positions, in row order), mean of the smoothed speed over the tracked rows}; NaN
+ *           for the last four of a track without a valid row.  THR_TRACK_LOST: fewer than half of the valid rows
+ *           were used (2 * used < valid).
+ * An outlier as a track's start row is the known way to lose a track: everything after it contradicts it.  The
+ * remedy is the caller's: mark that row invalid.
+ * q (m^2/s^3, the spectral density of the acceleration noise) and the scale of rx, ry are the deployment's and
+ * have no defaults.  v0 (10 m/s in the Python interface), max_rounds (4), the gate (the 99.9 % point of chi^2
+ * with 2 degrees of freedom, 13.815510557964274) and "half" are conventions of the interface, not measurements.
+ * Errors (THR_ERR_ARG): a null pointer, more than 2^28 rows, a timestamp that is not finite, on a valid row x, y,
+ * rx or ry not finite or a variance <= 0, q < 0, v0 <= 0, gate < 0 (or one of them not finite), max_rounds
+ * outside 1 .. 16. */
+typedef struct thr_track_opts {
+    double q, v0, gate;
+    int32_t max_rounds, reserved;
+} thr_track_opts;
+typedef struct thr_track_counts {
+    size_t rows, tracks, used, rejected, rounds, converged;
+} thr_track_counts;
+typedef struct thr_track_result thr_track_result; /* the handle: thr_track is the call */
+#define THR_TRACK_LOST 1
+/* what thr_track_fetch copies, in terms of thr_track_counts; the per-row arrays are in input row order */
+#define THR_TRACK_ORDER 0       /* int64[rows]: sorted position -> input row */
+#define THR_TRACK_TRACK_TX 1    /* int32[tracks], ascending */
+#define THR_TRACK_TRACK_PTR 2   /* int64[tracks + 1] into the sorted positions */
+#define THR_TRACK_USED 3        /* uint8[rows] */
+#define THR_TRACK_NIS 4         /* float64[rows] */
+#define THR_TRACK_FILT 5        /* float64[rows][4]: x, vx, y, vy */
+#define THR_TRACK_FILT_VAR 6    /* float64[rows][6]: pp, pv, vv of x, then of y */
+#define THR_TRACK_SMOOTH 7      /* float64[rows][4] */
+#define THR_TRACK_SMOOTH_VAR 8  /* float64[rows][6] */
+#define THR_TRACK_TRACK_STATS 9 /* float64[tracks][8], see above */
+#define THR_TRACK_TRACK_FLAGS 10 /* int32[tracks], THR_TRACK_LOST */
+#define THR_TRACK_N_OUTPUTS 11
+int thr_track(int device_id, size_t n, const int32_t* tx, const double* timestamp, const double* x, const double* y,
+              const double* rx, const double* ry, const uint8_t* valid /* NULL: all valid */, const thr_track_opts* opts,
+              thr_track_result** result_out, thr_track_counts* counts_out);
+/* `which` is a THR_TRACK_* index; dst_bytes must be the size given there */
+int thr_track_fetch(thr_track_result* result, int which, void* dst, size_t dst_bytes);
+void thr_track_free(thr_track_result* result);
+/* Milliseconds of the calling thread's last thr_track: {copies in, sort and layout, filter rounds, smoother,
+ * statistics, copies out (summed over the fetches)} */
+int thr_debug_track_times(double* ms_out /* [6] */);
+/* tile length of the scans, workgroup size, doubles of one filter element */
+int thr_debug_track_geometry(int* tile_len, int* workgroup, int* element_doubles);
 
 #ifdef __cplusplus
 }

@@ -55,6 +55,7 @@ EXPORTS = [
     "thr_dossier_feed_stream", "thr_dossier_result", "thr_dossier_geometry",
     "thr_reldist", "thr_reldist_fetch", "thr_reldist_free", "thr_debug_reldist_times", "thr_debug_reldist_geometry",
     "thr_posq", "thr_posq_fetch", "thr_posq_free", "thr_debug_posq_times",
+    "thr_track", "thr_track_fetch", "thr_track_free", "thr_debug_track_times", "thr_debug_track_geometry",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -69,6 +70,7 @@ BSYNC_COUNTS = ("rows", "cells", "discontinuities", "cuts")
 TDSTATS_COUNTS = ("rows", "cells", "robust")
 RELDIST_COUNTS = ("rows", "cells", "speeds", "speed_points", "dop_points")
 POSQ_COUNTS = ("groups", "rows", "flagged", "tasks")
+TRACK_COUNTS = ("rows", "tracks", "used", "rejected", "rounds", "converged")
 
 
 class ThrBsyncCounts(C.Structure):        # thr_bsync_counts
@@ -90,6 +92,14 @@ class ThrPosqCounts(C.Structure):         # thr_posq_counts
 class ThrPosqOpts(C.Structure):           # thr_posq_opts
     _fields_ = [("max_iter", C.c_int32), ("min_rx", C.c_int32), ("x0", C.c_double * 2), ("gate_m", C.c_double),
                 ("ratio", C.c_double)]
+
+
+class ThrTrackCounts(C.Structure):        # thr_track_counts
+    _fields_ = [(name, C.c_size_t) for name in TRACK_COUNTS]
+
+
+class ThrTrackOpts(C.Structure):          # thr_track_opts
+    _fields_ = [("q", C.c_double), ("v0", C.c_double), ("gate", C.c_double), ("max_rounds", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ThrReldistGeom(C.Structure):        # thr_reldist_geom
@@ -405,7 +415,10 @@ def load_library():
     lib.thr_posq.argtypes = ([C.c_int, C.c_size_t] + [vp] * 6 + [C.c_int, C.c_int, vp, C.POINTER(ThrPosqOpts), C.POINTER(vp),
                              C.POINTER(ThrPosqCounts)])
     lib.thr_debug_posq_times.argtypes = [C.POINTER(C.c_double)]
-    for stem in ("bsync", "tdstats", "reldist", "posq"):
+    lib.thr_track.argtypes = [C.c_int, C.c_size_t] + [vp] * 7 + [C.POINTER(ThrTrackOpts), C.POINTER(vp), C.POINTER(ThrTrackCounts)]
+    lib.thr_debug_track_times.argtypes = [C.POINTER(C.c_double)]
+    lib.thr_debug_track_geometry.argtypes = [ip, ip, ip]
+    for stem in ("bsync", "tdstats", "reldist", "posq", "track"):
         getattr(lib, "thr_%s_fetch" % stem).argtypes = [vp, C.c_int, vp, C.c_size_t]
         getattr(lib, "thr_%s_free" % stem).argtypes = [vp]
         getattr(lib, "thr_%s_free" % stem).restype = None
@@ -2112,3 +2125,64 @@ def posq_times():
     ms = (C.c_double * 6)()
     _check(lib, lib.thr_debug_posq_times(ms))
     return tuple(ms)
+
+
+TRACK_LOST = 1          # THR_TRACK_LOST
+TRACK_GATE_999 = 13.815510557964274     # -2 ln 0.001: the 99.9 % point of chi^2 with 2 degrees of freedom
+TRACK_STATS = ("rows", "valid", "used", "rejected", "mean_nis", "duration", "path", "mean_speed")
+# THR_TRACK_*: name -> (index, dtype, shape as a function of the counts); the per-row arrays are in input row order
+TRACK_OUTPUTS = {
+    "order": (0, np.int64, lambda c: (c["rows"],)),
+    "track_tx": (1, np.int32, lambda c: (c["tracks"],)),
+    "track_ptr": (2, np.int64, lambda c: (c["tracks"] + 1,)),
+    "used": (3, np.uint8, lambda c: (c["rows"],)),
+    "nis": (4, np.float64, lambda c: (c["rows"],)),
+    "filt": (5, np.float64, lambda c: (c["rows"], 4)),
+    "filt_var": (6, np.float64, lambda c: (c["rows"], 6)),
+    "smooth": (7, np.float64, lambda c: (c["rows"], 4)),
+    "smooth_var": (8, np.float64, lambda c: (c["rows"], 6)),
+    "track_stats": (9, np.float64, lambda c: (c["tracks"], 8)),
+    "track_flags": (10, np.int32, lambda c: (c["tracks"],)),
+}
+
+
+def track(tx, timestamp, x, y, rx, ry, valid=None, q=None, v0=10.0, gate=TRACK_GATE_999, max_rounds=4, outputs=None,
+          device_id=0):
+    """thr_track on one row per position (rx, ry: the measurement variances of the two axes in m^2; q in m^2/s^3)
+    -> (counts dict, {name: array}) with every output of TRACK_OUTPUTS (or those named in `outputs`) fetched.
+    ValueError for what thr_track refuses."""
+    lib = load_library()
+    if q is None:
+        raise ValueError("track: q has no default, it is the deployment's")
+    tx = np.ascontiguousarray(tx, dtype=np.int32)
+    cols = [np.ascontiguousarray(v, dtype=np.float64) for v in (timestamp, x, y, rx, ry)]
+    mask = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+    if tx.ndim != 1 or any(v.shape != tx.shape for v in cols) or (mask is not None and mask.shape != tx.shape):
+        raise ValueError("track: the columns are one-dimensional and of one length")
+    n = len(tx)
+    opts = ThrTrackOpts(float(q), float(v0), float(gate), int(max_rounds), 0)
+    handle, counts = C.c_void_p(), ThrTrackCounts()
+    rc = lib.thr_track(int(device_id), n, tx.ctypes.data if n else None, *[v.ctypes.data if n else None for v in cols],
+                       None if mask is None or not n else mask.ctypes.data, C.byref(opts), C.byref(handle), C.byref(counts))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    c = {name: int(getattr(counts, name)) for name in TRACK_COUNTS}
+    return c, _fetch_all(lib, "track", handle, c, TRACK_OUTPUTS, outputs)
+
+
+def track_times():
+    """Milliseconds (HIP events) of this thread's last track(): copies in, sort and layout, filter rounds, smoother,
+    statistics, copies out."""
+    lib = load_library()
+    ms = (C.c_double * 6)()
+    _check(lib, lib.thr_debug_track_times(ms))
+    return tuple(ms)
+
+
+def track_geometry():
+    """thr_debug_track_geometry -> (tile length T, workgroup size W, doubles of one filter element)."""
+    lib = load_library()
+    t, w, e = C.c_int(), C.c_int(), C.c_int()
+    _check(lib, lib.thr_debug_track_geometry(C.byref(t), C.byref(w), C.byref(e)))
+    return t.value, w.value, e.value
