@@ -95,7 +95,11 @@ extern "C" {
  *      the others (the open items of the reference's pos_est.py)
  *    + thr_track / thr_track_fetch / thr_track_free / thr_debug_track_times / _geometry -- per transmitter a
  *      constant-velocity Kalman filter over the positions in time order, a gate on the innovations and a
- *      fixed-interval smoother (the last open item of the reference's pos_est.py) */
+ *      fixed-interval smoother (the last open item of the reference's pos_est.py)
+ *    + thr_posg / thr_posg_fetch / thr_posg_free / thr_debug_posg_times -- thr_pos's 2-D solve started from the
+ *      lowest local minima of the cost surface on a grid over the receivers' surroundings as well: the best
+ *      minimum, the runner-up, and whether the fixed start was wrong or two positions fit (the reference's "TODO:
+ *      use analytic solution or previous position as initial value") */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -1662,6 +1666,89 @@ void thr_track_free(thr_track_result* result);
 int thr_debug_track_times(double* ms_out /* [6] */);
 /* tile length of the scans, workgroup size, doubles of one filter element */
 int thr_debug_track_geometry(int* tile_len, int* workgroup, int* element_doubles);
+
+/* ---- Global position solve: grid starts, the best minimum, the ambiguity flag.  Host columns in, synchronous, the
+ * results stay on the device behind a handle until thr_posg_fetch (the pattern of thr_posq).  The columns are
+ * thr_pos's (CSR groups, dense receiver indices, rx_coords[n_rx][2]); dims must be 2.  All arithmetic is float64,
+ * no product and sum is contracted.  G = opts->grid, K = opts->starts.
+ *   area     lo = min over the receivers - margin_m, hi = max + margin_m per axis; 0 < margin_m <= 10 km, so the
+ *            area lies inside thr_pos's box.  Cell centres cx[i] = lo0 + (i + 0.5) * ((hi0 - lo0) / G), i = 0 .. G-1,
+ *            cy[j] alike from lo1, hi1; cell c = j * G + i.
+ *   surface  F[c] = sum over the group's rows, in row order, one accumulator from 0.0, of r * r with
+ *            r = tc - (|rx0 - p_c| - |rx1 - p_c|), tc = tdoa * 2.997e8, |v| = sqrt(vx * vx + vy * vy): thr_pos's
+ *            residual.  Nothing is divided: a centre on a receiver is finite.
+ *   minimum  cell c is a LOCAL MINIMUM when for each of its up to 8 neighbours n: F[c] < F[n], or F[c] == F[n] and
+ *            n > c; for a neighbour outside the grid: F[c] < +inf.  A NaN makes every comparison false: a NaN cell
+ *            is no minimum and keeps its neighbours from being one.  Edge and corner cells can be minima.
+ *   starts   the K local minima with the smallest (F, c), in that order; unused slots hold cell -1 and F = NaN.
+ *   tasks    K + 1 per group.  Task 0 starts from opts->x0: thr_pos's own solve.  Task k = 1 .. K starts from the
+ *            centre of start cell k - 1.  Every task is thr_pos's iteration (csrc/pos_lm.hpp) over all rows with
+ *            opts->max_iter, inside thr_pos's box: it returns the bits thr_pos returns on the group with that x0.
+ *            A group whose task 0 ends THR_POS_UNDERDETERMINED or THR_POS_NONFINITE gets no grid and no tasks
+ *            1 .. K (n_local 0, start cells -1, its map NaN).  A task that does not exist has status
+ *            THR_POSG_NO_TASK, iters 0 and NaN elsewhere.
+ *   choice   rms_t = sqrt(F_t / rows) with the task's last accepted F.  A task is ELIGIBLE when its status is
+ *            THR_POS_OK.  Task u comes BEFORE task t when u is eligible and (rms_u, u) < (rms_t, t).  The BEST is the
+ *            eligible task that none comes before.  An eligible task t is a DUPLICATE when some u before it has
+ *            sqrt(dx * dx + dy * dy) <= merge_m between their positions.  n_minima = the eligible tasks that are no
+ *            duplicates.  The SECOND is the first of those other than the best; pos2, rms2 are NaN without one.
+ *   flags    THR_POSG_MOVED: task 0 is not eligible, or the best position is not within merge_m of task 0's.
+ *            THR_POSG_AMBIGUOUS: a second exists and rms_second <= fmax(ratio * rms_best, floor_m).
+ *            THR_POSG_NO_MINIMUM: no task is eligible; pos, dop, status, rms are then task 0's (task = 0).
+ *   map      for the groups map_first .. map_first + map_count - 1 (at most 256): F itself and the local minima.
+ * grid 16, 32 or 64; starts 1 .. 8; merge_m > 0, ratio >= 1, floor_m >= 0, all finite; max_iter >= 0; map_first >= 0
+ * and map_first + map_count <= n_groups; groups * (starts + 1) <= 2^28: THR_ERR_ARG otherwise, with thr_pos's
+ * argument checks, before anything is launched.  grid = 32, starts = 4, merge_m = 1, ratio = 2 and margin_m = the
+ * longer side of the receivers' bounding box are conventions of the Python interface, not measurements; floor_m is
+ * the deployment's noise level (0: the ratio alone). */
+typedef struct thr_posg_opts {
+    int32_t max_iter, grid, starts;
+    double x0[2];
+    double margin_m, merge_m, ratio, floor_m;
+    int64_t map_first;
+    int32_t map_count;
+} thr_posg_opts;
+typedef struct thr_posg_counts {
+    size_t groups, rows, tasks /* per group: starts + 1 */, starts, grid, map_groups;
+} thr_posg_counts;
+typedef struct thr_posg_result thr_posg_result; /* the handle: thr_posg is the call */
+#define THR_POSG_MOVED 1
+#define THR_POSG_AMBIGUOUS 2
+#define THR_POSG_NO_MINIMUM 4
+#define THR_POSG_NO_TASK (-1) /* the status of a task that does not exist */
+#define THR_POSG_ROW_CHUNK 32  /* rows that the surface kernel stages in LDS at a time */
+/* what thr_posg_fetch copies, in terms of thr_posg_counts */
+#define THR_POSG_POS 0          /* float64[groups][2]: the chosen task's position */
+#define THR_POSG_DOP 1          /* float64[groups] */
+#define THR_POSG_STATUS 2       /* int32[groups], THR_POS_* */
+#define THR_POSG_TASK 3         /* int32[groups]: the chosen task, 0 .. starts */
+#define THR_POSG_RMS 4          /* float64[groups] */
+#define THR_POSG_POS2 5         /* float64[groups][2]: the second, or NaN */
+#define THR_POSG_RMS2 6         /* float64[groups] */
+#define THR_POSG_N_MINIMA 7     /* int32[groups] */
+#define THR_POSG_FLAGS 8        /* int32[groups], THR_POSG_MOVED | _AMBIGUOUS | _NO_MINIMUM */
+#define THR_POSG_SNR 9          /* float64[groups]: the mean over all rows, as thr_pos */
+#define THR_POSG_N_LOCAL 10     /* int32[groups]: local-minimum cells of the surface */
+#define THR_POSG_START_CELL 11  /* int32[groups][starts] */
+#define THR_POSG_START_F 12     /* float64[groups][starts] */
+#define THR_POSG_TASK_POS 13    /* float64[groups][tasks][2] */
+#define THR_POSG_TASK_DOP 14    /* float64[groups][tasks] */
+#define THR_POSG_TASK_RMS 15    /* float64[groups][tasks] */
+#define THR_POSG_TASK_STATUS 16 /* int32[groups][tasks], THR_POS_* or THR_POSG_NO_TASK */
+#define THR_POSG_TASK_ITERS 17  /* int32[groups][tasks] */
+#define THR_POSG_MAP 18         /* float64[map_groups][grid][grid]: F, row j, column i */
+#define THR_POSG_MAP_MIN 19     /* uint8[map_groups][grid][grid]: 1 = local minimum */
+#define THR_POSG_N_OUTPUTS 20
+int thr_posg(int device_id, size_t n_groups, const int64_t* group_ptr, const int32_t* row_rx0, const int32_t* row_rx1,
+             const double* row_tdoa, const double* row_snr, int n_rx, int dims, const double* rx_coords,
+             const thr_posg_opts* opts, thr_posg_result** result_out, thr_posg_counts* counts_out);
+/* `which` is a THR_POSG_* index; dst_bytes must be the size given there */
+int thr_posg_fetch(thr_posg_result* result, int which, void* dst, size_t dst_bytes);
+void thr_posg_free(thr_posg_result* result);
+/* Milliseconds of the calling thread's last thr_posg: {copies in, task 0 (the fixed start), surface minima and
+ * starts (one kernel: the surface never leaves LDS), refinement (tasks 1 .. K), choice, copies out (summed over the
+ * fetches)} */
+int thr_debug_posg_times(double* ms_out /* [6] */);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,7 @@ EXPORTS = [
     "thr_reldist", "thr_reldist_fetch", "thr_reldist_free", "thr_debug_reldist_times", "thr_debug_reldist_geometry",
     "thr_posq", "thr_posq_fetch", "thr_posq_free", "thr_debug_posq_times",
     "thr_track", "thr_track_fetch", "thr_track_free", "thr_debug_track_times", "thr_debug_track_geometry",
+    "thr_posg", "thr_posg_fetch", "thr_posg_free", "thr_debug_posg_times",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -71,6 +72,7 @@ TDSTATS_COUNTS = ("rows", "cells", "robust")
 RELDIST_COUNTS = ("rows", "cells", "speeds", "speed_points", "dop_points")
 POSQ_COUNTS = ("groups", "rows", "flagged", "tasks")
 TRACK_COUNTS = ("rows", "tracks", "used", "rejected", "rounds", "converged")
+POSG_COUNTS = ("groups", "rows", "tasks", "starts", "grid", "map_groups")
 
 
 class ThrBsyncCounts(C.Structure):        # thr_bsync_counts
@@ -92,6 +94,16 @@ class ThrPosqCounts(C.Structure):         # thr_posq_counts
 class ThrPosqOpts(C.Structure):           # thr_posq_opts
     _fields_ = [("max_iter", C.c_int32), ("min_rx", C.c_int32), ("x0", C.c_double * 2), ("gate_m", C.c_double),
                 ("ratio", C.c_double)]
+
+
+class ThrPosgCounts(C.Structure):         # thr_posg_counts
+    _fields_ = [(name, C.c_size_t) for name in POSG_COUNTS]
+
+
+class ThrPosgOpts(C.Structure):           # thr_posg_opts
+    _fields_ = [("max_iter", C.c_int32), ("grid", C.c_int32), ("starts", C.c_int32), ("x0", C.c_double * 2),
+                ("margin_m", C.c_double), ("merge_m", C.c_double), ("ratio", C.c_double), ("floor_m", C.c_double),
+                ("map_first", C.c_int64), ("map_count", C.c_int32)]
 
 
 class ThrTrackCounts(C.Structure):        # thr_track_counts
@@ -418,7 +430,10 @@ def load_library():
     lib.thr_track.argtypes = [C.c_int, C.c_size_t] + [vp] * 7 + [C.POINTER(ThrTrackOpts), C.POINTER(vp), C.POINTER(ThrTrackCounts)]
     lib.thr_debug_track_times.argtypes = [C.POINTER(C.c_double)]
     lib.thr_debug_track_geometry.argtypes = [ip, ip, ip]
-    for stem in ("bsync", "tdstats", "reldist", "posq", "track"):
+    lib.thr_posg.argtypes = ([C.c_int, C.c_size_t] + [vp] * 5 + [C.c_int, C.c_int, vp, C.POINTER(ThrPosgOpts), C.POINTER(vp),
+                             C.POINTER(ThrPosgCounts)])
+    lib.thr_debug_posg_times.argtypes = [C.POINTER(C.c_double)]
+    for stem in ("bsync", "tdstats", "reldist", "posq", "track", "posg"):
         getattr(lib, "thr_%s_fetch" % stem).argtypes = [vp, C.c_int, vp, C.c_size_t]
         getattr(lib, "thr_%s_free" % stem).argtypes = [vp]
         getattr(lib, "thr_%s_free" % stem).restype = None
@@ -2186,3 +2201,72 @@ def track_geometry():
     t, w, e = C.c_int(), C.c_int(), C.c_int()
     _check(lib, lib.thr_debug_track_geometry(C.byref(t), C.byref(w), C.byref(e)))
     return t.value, w.value, e.value
+
+
+POSG_MOVED, POSG_AMBIGUOUS, POSG_NO_MINIMUM = 1, 2, 4      # THR_POSG_* flags
+POSG_NO_TASK = -1           # THR_POSG_NO_TASK: the status of a task that does not exist
+POSG_ROW_CHUNK = 32         # THR_POSG_ROW_CHUNK: rows the surface kernel stages in LDS at a time
+POSG_DIST_RECEIVERS = 32    # kDistRx: up to this many receivers the surface kernel takes a cell's distances once per receiver
+POSG_GRIDS = (16, 32, 64)
+POSG_MAX_STARTS = 8
+POSG_MAX_MAP = 256          # groups whose surface one call can return
+POSG_MAX_MARGIN = 10e3      # thr_pos's box reaches this far beyond the receivers
+# THR_POSG_*: name -> (index, dtype, shape as a function of the counts)
+POSG_OUTPUTS = {
+    "pos": (0, np.float64, lambda c: (c["groups"], 2)),
+    "dop": (1, np.float64, lambda c: (c["groups"],)),
+    "status": (2, np.int32, lambda c: (c["groups"],)),
+    "task": (3, np.int32, lambda c: (c["groups"],)),
+    "rms": (4, np.float64, lambda c: (c["groups"],)),
+    "pos2": (5, np.float64, lambda c: (c["groups"], 2)),
+    "rms2": (6, np.float64, lambda c: (c["groups"],)),
+    "n_minima": (7, np.int32, lambda c: (c["groups"],)),
+    "flags": (8, np.int32, lambda c: (c["groups"],)),
+    "snr": (9, np.float64, lambda c: (c["groups"],)),
+    "n_local": (10, np.int32, lambda c: (c["groups"],)),
+    "start_cell": (11, np.int32, lambda c: (c["groups"], c["starts"])),
+    "start_f": (12, np.float64, lambda c: (c["groups"], c["starts"])),
+    "task_pos": (13, np.float64, lambda c: (c["groups"], c["tasks"], 2)),
+    "task_dop": (14, np.float64, lambda c: (c["groups"], c["tasks"])),
+    "task_rms": (15, np.float64, lambda c: (c["groups"], c["tasks"])),
+    "task_status": (16, np.int32, lambda c: (c["groups"], c["tasks"])),
+    "task_iters": (17, np.int32, lambda c: (c["groups"], c["tasks"])),
+    "map": (18, np.float64, lambda c: (c["map_groups"], c["grid"], c["grid"])),
+    "map_min": (19, np.uint8, lambda c: (c["map_groups"], c["grid"], c["grid"])),
+}
+
+
+def posg(group_ptr, row_rx0, row_rx1, row_tdoa, row_snr, rx_coords, margin_m, grid=32, starts=4, merge_m=1.0, ratio=2.0,
+         floor_m=0.0, map_first=0, map_count=0, x0=(0.1, 0.1), max_iter=100, outputs=None, device_id=0):
+    """thr_posg on TDOA rows in CSR form (thr_pos's columns: dense receiver indices into rx_coords[n_rx, 2]) ->
+    (counts dict, {name: array}) with every output of POSG_OUTPUTS (or those named in `outputs`) fetched.
+    ValueError for what thr_posg refuses."""
+    lib = load_library()
+    ptr = np.ascontiguousarray(group_ptr, dtype=np.int64)
+    rx0, rx1 = np.ascontiguousarray(row_rx0, dtype=np.int32), np.ascontiguousarray(row_rx1, dtype=np.int32)
+    tdoa, snr = np.ascontiguousarray(row_tdoa, dtype=np.float64), np.ascontiguousarray(row_snr, dtype=np.float64)
+    xy = np.ascontiguousarray(rx_coords, dtype=np.float64)
+    if ptr.ndim != 1 or len(ptr) < 1 or xy.ndim != 2 or not (len(rx0) == len(rx1) == len(tdoa) == len(snr) == int(ptr[-1])):
+        raise ValueError("posg: group_ptr, the row columns or rx_coords have the wrong shape")
+    start = np.ascontiguousarray(x0, dtype=np.float64)
+    if start.shape != (2,):
+        raise ValueError("posg: x0 holds two values")
+    opts = ThrPosgOpts(int(max_iter), int(grid), int(starts), (C.c_double * 2)(*start.tolist()), float(margin_m), float(merge_m),
+                       float(ratio), float(floor_m), int(map_first), int(map_count))
+    handle, counts = C.c_void_p(), ThrPosgCounts()
+    rc = lib.thr_posg(int(device_id), len(ptr) - 1, ptr.ctypes.data, rx0.ctypes.data, rx1.ctypes.data, tdoa.ctypes.data,
+                      snr.ctypes.data, xy.shape[0], xy.shape[1], xy.ctypes.data, C.byref(opts), C.byref(handle), C.byref(counts))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    c = {name: int(getattr(counts, name)) for name in POSG_COUNTS}
+    return c, _fetch_all(lib, "posg", handle, c, POSG_OUTPUTS, outputs)
+
+
+def posg_times():
+    """Milliseconds (HIP events) of this thread's last posg(): copies in, task 0 (the fixed start), surface minima and
+    starts, refinement (tasks 1 .. K), choice, copies out."""
+    lib = load_library()
+    ms = (C.c_double * 6)()
+    _check(lib, lib.thr_debug_posg_times(ms))
+    return tuple(ms)
