@@ -99,7 +99,10 @@ extern "C" {
  *    + thr_posg / thr_posg_fetch / thr_posg_free / thr_debug_posg_times -- thr_pos's 2-D solve started from the
  *      lowest local minima of the cost surface on a grid over the receivers' surroundings as well: the best
  *      minimum, the runner-up, and whether the fixed start was wrong or two positions fit (the reference's "TODO:
- *      use analytic solution or previous position as initial value") */
+ *      use analytic solution or previous position as initial value")
+ *    + thr_debug_seg_tile_grid / thr_debug_seg_tile_stats -- the cap on the workgroups of a tile kernel of thr_toadstats,
+ *      thr_beaconsync, thr_tdoastats, thr_reldist and thr_track (tests reach the loop's later trips at small
+ *      shapes), and how many trips the launches since took (results unchanged) */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -1339,6 +1342,17 @@ void thr_tstats_free(thr_tstats* result);
 int thr_debug_toadstats_times(double* ms_out /* [5] */);
 /* The tile length T (positions of the sorted order one workgroup reduces per loop trip) and the workgroup size. */
 int thr_debug_toadstats_geometry(int* tile_len, int* workgroup);
+/* For tests.  The tile kernels of thr_toadstats, thr_beaconsync, thr_tdoastats, thr_reldist and thr_track run on
+ * min(tiles, cap) workgroups, each of which walks the tiles w, w + grid, w + 2 grid, ...  `workgroups` sets the cap
+ * for the whole process: 0 restores the default (2048), 1 .. 65536 is taken as it is, anything else is THR_ERR_ARG.
+ * The cap decides which workgroup reduces which tile and moves no result: every value gives the bytes of the default.
+ * A call also resets what thr_debug_seg_tile_stats counts.  Not meant to be changed while another thread is inside
+ * one of those five calls (that call may then use either cap for a launch; its results are the same). */
+int thr_debug_seg_tile_grid(int workgroups);
+/* Since the last thr_debug_seg_tile_grid (or the library's load): *launches = how many times a tile grid was sized
+ * (a grid may serve several launches of one call), *max_trips = the largest ceil(tiles / workgroups) among them,
+ * i.e. the most trips any workgroup's tile loop took (0 when nothing was launched). */
+int thr_debug_seg_tile_stats(int* launches, int* max_trips);
 
 /* ---- clock-sync quality (the numbers of the reference's `thrifty analyze_beacon`, beacon_analysis.py:62-136)
  * for every cell at once.  Input: the detection columns rxid, txid, soa, energy, noise and the detection id

@@ -41,7 +41,7 @@ def test_without_a_gate_every_valid_row_is_used_in_one_run():
 def test_one_round_on_a_scene_that_needs_three():
     s, full = track_check.gating(0)
     assert full["counts"]["rounds"] == 3
-    ref = track_check.reference(s, max_rounds=1)
+    ref = track_check.gating_0_one_round()
     track_check.assert_margin(ref)
     counts, out = track_check.device(s, max_rounds=1)
     assert counts["converged"] == 0 and counts["rounds"] == 2

@@ -1,6 +1,7 @@
 """`thr_track` at the smallest shapes at which its scans can go wrong (tests/track_scenes.py: seams()): row counts
 around the tile of 256, tracks that meet inside a tile and at its edges, hundreds of one-row tracks, invalid rows at
-a track's start, at a tile's last and first position and across a whole tile, equal timestamps, epoch timestamps with
+a track's start, at a tile's last and first position and across a whole tile, a row that the gate rejects at a tile's
+last and first position, equal timestamps, epoch timestamps with
 millisecond steps -- against tests/track_ref.py within the tolerance recorded per scene, integers exact -- and the
 equalities of bytes the header promises."""
 import numpy as np
@@ -37,6 +38,13 @@ def test_what_the_scenes_hold():
     for name, at in (("invalid_255", [255]), ("invalid_256", [256]), ("invalid_tile", list(range(200, 521)))):
         s, ref = track_check.seam(name)
         assert np.flatnonzero(s["valid"][ref["order"]] == 0).tolist() == at
+    for name, at in (("reject_255", 255), ("reject_256", 256)):      # a row the gate rejects: valid, not used, its nis reported
+        s, ref = track_check.seam(name)
+        assert len(s["tx"]) == 600 and s["valid"].all() and ref["counts"]["tracks"] == 1
+        assert np.flatnonzero(s["outlier"][ref["order"]]).tolist() == [at]
+        row = int(ref["order"][at])
+        assert ref["used"][row] == 0 and ref["counts"]["rounds"] >= 2 and ref["counts"]["converged"] == 1
+        assert np.isfinite(ref["nis"][row]) and ref["nis"][row] > track_check.track_ref.GATE_999
     s = seams["equal_times"]
     assert all(len(set(s["timestamp"][s["tx"] == tx])) == 1 for tx in set(s["tx"].tolist()))
     s = seams["epoch_ms"]

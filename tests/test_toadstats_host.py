@@ -44,6 +44,33 @@ def test_thr_toadstats_is_declared_listed_and_built():
     assert "analyze_toads" not in cli.COMMANDS
 
 
+def test_the_tile_grid_cap_is_declared_listed_and_bound():
+    header = open(os.path.join(ROOT, "include", "thrifty_hip.h")).read()
+    within = header[header.index("within 11, a pure addition"):header.index("#define THR_ABI_VERSION")]
+    assert "+ thr_debug_seg_tile_grid / thr_debug_seg_tile_stats" in within
+    assert re.search(r"\bint thr_debug_seg_tile_grid\(int workgroups\);", header)
+    assert re.search(r"\bint thr_debug_seg_tile_stats\(int\* launches, int\* max_trips\);", header)
+    assert {"thr_debug_seg_tile_grid", "thr_debug_seg_tile_stats"} <= set(_native.EXPORTS)
+    assert callable(_native.seg_tile_grid) and callable(_native.seg_tile_stats)
+    # one place sizes a tile grid, and so one place counts: the header declares it, toadstats.hip defines it with
+    # the two entry points, and no stage works the grid out for itself
+    shared = open(os.path.join(build.CSRC, "seg_reduce.hpp")).read()
+    assert "dim3 tile_grid(int n_tiles);" in shared and "constexpr int kMaxTileGrid = 2048;" in shared
+    for name in ("toadstats.hip", "syncstats.hip", "reldist.hip", "track.hip", "seg_cells.hpp", "track_scan.hpp"):
+        text = open(os.path.join(build.CSRC, name)).read()
+        assert ("kMaxTileGrid" in text) == (name == "toadstats.hip"), name
+        assert len(re.findall(r"\bdim3 thr::seg::tile_grid\(int n_tiles\) \{", text)) == (name == "toadstats.hip"), name
+    assert os.path.exists(_native.LIB_PATH), "the library is not built: python -m thrifty_amd.build"
+    lib = _native.load_library()
+    assert lib.thr_debug_seg_tile_grid and lib.thr_debug_seg_tile_stats
+    for bad in (-1, 65537):      # refused before any device is looked for
+        with pytest.raises(ValueError, match="thr_debug_seg_tile_grid"):
+            _native.seg_tile_grid(bad)
+    for ok in (1, 65536, 0):
+        _native.seg_tile_grid(ok)
+        assert _native.seg_tile_stats() == (0, 0)
+
+
 def test_the_built_library_exports_thr_toadstats():
     assert os.path.exists(_native.LIB_PATH), "the library is not built: python -m thrifty_amd.build"
     lib = _native.load_library()

@@ -33,6 +33,12 @@ def gating(k):
 
 
 @functools.lru_cache(maxsize=None)
+def gating_0_one_round():
+    """The reference of gating(0) stopped after one round: the call that does not converge."""
+    return reference(track_scenes.gating(0), max_rounds=1)
+
+
+@functools.lru_cache(maxsize=None)
 def seams():
     return track_scenes.seams()
 

@@ -5,17 +5,20 @@
 
 The knobs: number of tracks, rows per track (one number or one per track), the time-step law ("exp": exponential
 with mean `step`, "fixed": `step`, "zero": every timestamp of a track equal), the share of duplicate timestamps, the
-share of planted outliers (100 m .. 10 km off, never a track's first row), invalid rows (a share at random, and / or
-explicit ranges of a track's rows, whose x is NaN), and whether the rows of the tracks are interleaved at random."""
+share of planted outliers (100 m .. 10 km off, never a track's first row), outliers at given rows of a track
+(`outlier_rows`: (track, row) pairs, x moved by OUTLIER_X metres, never row 0; they draw no random number, so a scene
+is the same rows with and without them), invalid rows (a share at random, and / or explicit ranges of a track's rows,
+whose x is NaN), and whether the rows of the tracks are interleaved at random."""
 import numpy as np
 
 SIGMA = 3.0       # metres, the noise of one axis
 ACCEL = 0.5       # m s^-3/2
 V0 = 10.0
+OUTLIER_X = 500.0     # metres, what an `outlier_rows` row is moved by on x
 
 
 def scene(seed, tracks=1, rows=256, law="exp", step=1.0, t0=0.0, duplicates=0.0, outliers=0.0, invalid=0.0, invalid_ranges=(),
-          interleave=True, first_tx=3):
+          interleave=True, first_tx=3, outlier_rows=()):
     rng = np.random.default_rng(seed)
     rows = [rows] * tracks if np.isscalar(rows) else list(rows)
     cols = {name: [] for name in ("tx", "timestamp", "x", "y", "rx", "ry", "valid", "outlier")}
@@ -39,6 +42,11 @@ def scene(seed, tracks=1, rows=256, law="exp", step=1.0, t0=0.0, duplicates=0.0,
         off = rng.uniform(np.log(100.0), np.log(1e4), n)
         ang = rng.uniform(0.0, 2.0 * np.pi, n)
         meas[out] += (np.exp(off) * np.stack([np.cos(ang), np.sin(ang)]))[:, out].T
+        for track, row in outlier_rows:
+            if track == c:
+                assert 0 < row < n, "an outlier is never a track's first row"
+                meas[row, 0] += OUTLIER_X
+                out[row] = True
         ok = rng.random(n) >= invalid
         for track, a, e in invalid_ranges:
             if track == c:
@@ -95,6 +103,8 @@ def seams():
     out["no_valid_row"] = scene(307, tracks=3, rows=(40, 30, 280), invalid_ranges=((1, 0, 30),))
     out["invalid_255"] = scene(308, rows=600, invalid_ranges=((0, 255, 256),))
     out["invalid_256"] = scene(309, rows=600, invalid_ranges=((0, 256, 257),))
+    out["reject_255"] = scene(575, rows=600, interleave=False, outlier_rows=((0, 255),))      # a row the gate rejects (valid,
+    out["reject_256"] = scene(576, rows=600, interleave=False, outlier_rows=((0, 256),))      # mask 0, nis reported) on a tile's seam
     out["invalid_tile"] = scene(310, rows=800, invalid_ranges=((0, 200, 521),))
     out["equal_times"] = scene(311, tracks=2, rows=(300, 20), law="zero")
     out["epoch_ms"] = scene(312, tracks=2, rows=(400, 200), law="fixed", step=1e-3, t0=1.5e9)

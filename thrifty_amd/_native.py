@@ -49,6 +49,7 @@ EXPORTS = [
     "thr_chipscan", "thr_debug_chipscan_geometry", "thr_debug_chipscan_budget", "thr_debug_chipscan_times",
     "thr_debug_chipscan_fill", "thr_debug_chipscan_groups",
     "thr_toadstats", "thr_tstats_fetch", "thr_tstats_free", "thr_debug_toadstats_times", "thr_debug_toadstats_geometry",
+    "thr_debug_seg_tile_grid", "thr_debug_seg_tile_stats",
     "thr_beaconsync", "thr_bsync_fetch", "thr_bsync_free", "thr_debug_beaconsync_times", "thr_debug_beaconsync_geometry",
     "thr_tdoastats", "thr_tdstats_fetch", "thr_tdstats_free", "thr_debug_tdoastats_times", "thr_debug_tdoastats_geometry",
     "thr_dossier_create", "thr_dossier_destroy", "thr_dossier_reset", "thr_dossier_feed", "thr_dossier_feed_card",
@@ -416,6 +417,8 @@ def load_library():
     lib.thr_tstats_free.restype = None
     lib.thr_debug_toadstats_times.argtypes = [C.POINTER(C.c_double)]
     lib.thr_debug_toadstats_geometry.argtypes = [ip, ip]
+    lib.thr_debug_seg_tile_grid.argtypes = [C.c_int]
+    lib.thr_debug_seg_tile_stats.argtypes = [ip, ip]
     lib.thr_beaconsync.argtypes = ([C.c_int, C.c_size_t] + [vp] * 6 + [C.c_size_t, vp, vp, C.c_int, vp, vp, C.c_size_t,
                                    vp, C.c_size_t, C.POINTER(vp), C.POINTER(ThrBsyncCounts)])
     lib.thr_tdoastats.argtypes = ([C.c_int, C.c_size_t] + [vp] * 7 + [vp, vp, C.c_int, C.POINTER(vp),
@@ -1843,6 +1846,26 @@ def toadstats_geometry():
     t, w = C.c_int(), C.c_int()
     _check(lib, lib.thr_debug_toadstats_geometry(C.byref(t), C.byref(w)))
     return t.value, w.value
+
+
+def seg_tile_grid(workgroups):
+    """thr_debug_seg_tile_grid: the most workgroups a tile kernel of toadstats, beaconsync, tdoastats, reldist and
+    track runs on (0: the default, 2048; 1 .. 65536), for the whole process; resets seg_tile_stats().  For tests: no
+    result depends on it.  ValueError for a value outside the range."""
+    lib = load_library()
+    rc = lib.thr_debug_seg_tile_grid(int(workgroups))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+
+
+def seg_tile_stats():
+    """thr_debug_seg_tile_stats -> (tile grids sized since the last seg_tile_grid(), the most trips a workgroup's
+    tile loop took among them)."""
+    lib = load_library()
+    launches, trips = C.c_int(), C.c_int()
+    _check(lib, lib.thr_debug_seg_tile_stats(C.byref(launches), C.byref(trips)))
+    return launches.value, trips.value
 
 
 # the detection columns of thr_beaconsync, in its argument order

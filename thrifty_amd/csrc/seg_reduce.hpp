@@ -16,7 +16,8 @@
 // Every launch of these stages goes through launch() / launch_grid(), which take the parameter types from the
 // kernel; the tail every stage ends in (free, the five times, the geometry) stands once beside fetch().
 //
-// Everything here is a template, inline, or static: every translation unit of a stage includes it.
+// Everything here is a template, inline, or static: every translation unit of a stage includes it.  The one
+// exception is tile_grid(), which is declared here and defined once, in toadstats.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,7 +42,14 @@ static_assert(kTile == kBlock, "one position per thread");
 
 inline dim3 grid_for(size_t n) { return dim3(unsigned((n + kBlock - 1) / kBlock)); }
 inline int tiles_of(int m) { return (m + kTile - 1) / kTile; }
-inline dim3 tile_grid(int n_tiles) { return dim3(unsigned(n_tiles < kMaxTileGrid ? n_tiles : kMaxTileGrid)); }
+constexpr int kTileGridLimit = 65536;         // the largest cap thr_debug_seg_tile_grid takes
+
+// The grid of a tile kernel over n_tiles tiles: min(n_tiles, cap) workgroups, the cap being kMaxTileGrid unless
+// thr_debug_seg_tile_grid has set another.  That setter is for tests: the cap decides which workgroup walks which
+// tile and how many trips its loop takes, and moves no result.  Every tile launch of every stage asks here and is
+// counted here (thr_debug_seg_tile_stats).  One definition for the library, beside the two entry points in
+// toadstats.hip, where the cap and the counts live.
+dim3 tile_grid(int n_tiles);
 
 // a step that returns THR_OK or an error which is already worded
 #define THR_TRY(expr)                           \

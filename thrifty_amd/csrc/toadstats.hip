@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -656,4 +657,45 @@ extern "C" int thr_debug_toadstats_geometry(int* tile_len, int* workgroup) try {
     return geometry("thr_debug_toadstats_geometry", tile_len, workgroup);
 } catch (...) {
     return thr::on_exception("thr_debug_toadstats_geometry");
+}
+
+// ---- the tile grid of every stage built on seg_reduce.hpp: the cap on a tile kernel's workgroups, set by tests through
+// thr_debug_seg_tile_grid, and what the grids sized since then looked like.  Process-wide; no result depends on it.
+namespace {
+std::atomic<int> g_tile_grid_cap{kMaxTileGrid};
+std::atomic<int> g_tile_launches{0}, g_tile_max_trips{0};
+}  // namespace
+
+dim3 thr::seg::tile_grid(int n_tiles) {
+    const int cap = g_tile_grid_cap.load(std::memory_order_relaxed);
+    const int grid = n_tiles < cap ? n_tiles : cap;
+    if (grid > 0) {
+        const int trips = (n_tiles + grid - 1) / grid;
+        g_tile_launches.fetch_add(1, std::memory_order_relaxed);
+        int seen = g_tile_max_trips.load(std::memory_order_relaxed);
+        while (trips > seen && !g_tile_max_trips.compare_exchange_weak(seen, trips, std::memory_order_relaxed)) {
+        }
+    }
+    return dim3(unsigned(grid));
+}
+
+extern "C" int thr_debug_seg_tile_grid(int workgroups) try {
+    if (workgroups < 0 || workgroups > kTileGridLimit)
+        return thr::fail_msg(THR_ERR_ARG, "thr_debug_seg_tile_grid: %d workgroups (0: the default, or 1 .. %d)", workgroups,
+                             kTileGridLimit);
+    g_tile_grid_cap.store(workgroups ? workgroups : kMaxTileGrid);
+    g_tile_launches.store(0);
+    g_tile_max_trips.store(0);
+    return THR_OK;
+} catch (...) {
+    return thr::on_exception("thr_debug_seg_tile_grid");
+}
+
+extern "C" int thr_debug_seg_tile_stats(int* launches, int* max_trips) try {
+    if (!launches || !max_trips) return thr::fail_msg(THR_ERR_ARG, "thr_debug_seg_tile_stats: null argument");
+    *launches = g_tile_launches.load();
+    *max_trips = g_tile_max_trips.load();
+    return THR_OK;
+} catch (...) {
+    return thr::on_exception("thr_debug_seg_tile_stats");
 }
