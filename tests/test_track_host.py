@@ -1,6 +1,8 @@
 """Host side of `thr_track` (no GPU): the wiring into the header, the symbol list and the build; the three CPU
 statements of tests/track_ref.py against the recorded tolerances (tests/golden/make_golden_track.py); the gate's
 rounds; what is refused before the library is loaded; the .track text format; the command line on a mocked device."""
+import hashlib
+import importlib.util
 import io
 import json
 import os
@@ -9,6 +11,7 @@ import re
 import numpy as np
 import pytest
 
+import track_check
 import track_ref
 import track_scenes
 from thrifty_amd import _native, build, pos_est, pos_quality, track
@@ -16,6 +19,15 @@ from thrifty_amd import _native, build, pos_est, pos_quality, track
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOLERANCES = json.load(open(os.path.join(ROOT, "tests", "golden", "track_tolerances.json")))
 OUTPUTS = ("filt", "filt_var", "smooth", "smooth_var", "nis")
+OLD_SCENES = {"gating_0", "gating_1", "gating_2", "gating_1_no_gate", "gating_0_one_round"} | set(track_scenes.seams())
+CLAUSES = sorted(track_scenes.clauses())
+
+
+def _generator():
+    spec = importlib.util.spec_from_file_location("make_golden_track", os.path.join(ROOT, "tests", "golden", "make_golden_track.py"))
+    module = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(module)
+    return module
 
 
 def _ref(s, **kw):
@@ -70,11 +82,85 @@ def test_csrc_hash_does_not_see_the_two_new_files(monkeypatch):
 def test_the_recorded_tolerances_cover_every_scene():
     scenes = TOLERANCES["scenes"]
     assert TOLERANCES["factor"] == 16 and TOLERANCES["longdouble_bits"] >= 64
-    assert set(scenes) == {"gating_0", "gating_1", "gating_2", "gating_1_no_gate", "gating_0_one_round"} | set(track_scenes.seams())
-    for name, record in scenes.items():
+    assert set(scenes) == OLD_SCENES | set(CLAUSES) and not OLD_SCENES & set(CLAUSES)
+    for name in OLD_SCENES:
         for key in OUTPUTS:
             # metres (m^2, 1) on positions of 2e4 m: an error in an element or a combination is ten orders above this
-            assert 0.0 <= record[key] < 1e-6, (name, key)
+            assert 0.0 <= scenes[name][key] < 1e-6, (name, key)
+    assert TOLERANCES["factor"] == track_check.FACTOR
+    not_compared = {}
+    for name in CLAUSES:      # their own condition, column by column: a bound below 1e-3 of what the column is measured against
+        assert isinstance(scenes[name]["gated"], bool)
+        assert ("with_gate" in scenes[name]) == (scenes[name]["gated"] and name in track_scenes.REGIMES)
+        for tag, record in (("", scenes[name]), (" with the gate", scenes[name].get("with_gate"))):
+            if record is None:
+                continue
+            assert [len(record["columns"][key]) for key in OUTPUTS] == [4, 6, 4, 6, 1]
+            assert all(0.0 <= max(record["columns"][key]) == record[key] for key in OUTPUTS)
+            assert 16 * max(record["columns"][key][col] for key in ("filt", "smooth") for col in (0, 2)) <= record["position_bound"]
+            assert record["position_bound"] < 1e-3 * record["smallest_sigma"]
+            for column, numbers in record["not_compared"].items():
+                assert numbers["bound"] >= 1e-3 * numbers["scale"] > 0.0 and column[:column.index("[")] in OUTPUTS[1:]
+            if record["not_compared"]:
+                not_compared[name + tag] = sorted(record["not_compared"])
+    # every regime is compared with the gate as well, and the columns whose bound says nothing are these and no others
+    # ("Range of the definition"): one that joins them does not do so unseen
+    assert all(scenes[name]["gated"] for name in CLAUSES) and len(track_scenes.REGIMES) == 11
+    velocity, position = ["smooth_var[2]", "smooth_var[5]"], ["filt_var[0]", "filt_var[3]", "smooth_var[0]", "smooth_var[3]"]
+    assert not_compared == {"v0_1e5": velocity, "v0_1e5 with the gate": velocity, "gap_400_v0_1e5": velocity,
+                            "gap_400_v0_1e5 with the gate": velocity, "steps_1e4": position, "steps_1e4 with the gate": position}
+    assert set(TOLERANCES["out_of_range"]) == set(track_scenes.OUT_OF_RANGE) and not set(track_scenes.OUT_OF_RANGE) & set(CLAUSES)
+    generator = _generator()
+    for name, record in TOLERANCES["out_of_range"].items():      # measured, documented, in no test
+        assert record["position_bound"] >= 1e-3 * record["smallest_sigma"], name
+        assert generator.measure_out_of_range(name, track_scenes.OUT_OF_RANGE[name]) == record, name
+
+
+def test_the_old_scenes_keep_their_bytes_and_their_records():
+    """The knobs that the clauses added draw no random number unless used; no recorded tolerance of an old scene moved.
+    The digests were taken before the knobs and the new scenes were added."""
+    h = hashlib.sha256()
+    for name, s in [("gating_%d" % k, track_scenes.gating(k)) for k in range(3)] + sorted(track_scenes.seams().items()):
+        h.update(name.encode())
+        for key in track_scenes.COLUMNS + ("outlier",):
+            h.update(np.ascontiguousarray(s[key]).tobytes())
+        h.update(repr((s["q"], s["v0"])).encode())
+    assert h.hexdigest() == "5bed668bfd8b4986d29a59691beaa559d54b8cb93d54c58b02901ef58042f3bf"
+    old = {name: TOLERANCES["scenes"][name] for name in OLD_SCENES}
+    assert hashlib.sha256(json.dumps(old, sort_keys=True).encode()).hexdigest() == \
+        "3816d1656859c196075e75d7680fa14ac5ad9c9e71eaab88c19861b33bcc2ec9"
+    generator = _generator()      # and the generator still writes them: a few of them measured again
+    assert generator.measure(track_scenes.gating(1), gate=0.0) == old["gating_1_no_gate"]
+    for name in ("single_257", "meet_at_last", "reject_256", "invalid_tile", "epoch_ms"):
+        assert generator.measure(track_scenes.seams()[name]) == old[name], name
+
+
+@pytest.mark.parametrize("name", CLAUSES)
+def test_a_clause_scene_holds_what_it_is_named_after_and_its_record_is_the_generators(name):
+    track_check.assert_clause_holds(name)
+    s, options = track_scenes.clauses()[name]      # measure_clause stops where the positions miss the usefulness condition
+    assert _generator().measure_clause(name, s, options) == TOLERANCES["scenes"][name]
+
+
+def test_the_tiles_form_is_the_scan_inside_one_fragment_and_the_recursion_across_fragments():
+    s = track_scenes.seams()["single_255"]
+    scan, tiles = _ref(s, form="scan"), _ref(s, form="tiles")
+    assert scan["counts"] == tiles["counts"]
+    for key in OUTPUTS + ("track_stats", "used"):
+        assert scan[key].tobytes() == tiles[key].tobytes(), key
+    assert track_ref.fragments(0, 255) == [(0, 255)] and track_ref.fragments(0, 769) == [(0, 256), (256, 512), (512, 768), (768, 769)]
+    assert track_ref.fragments(100, 600) == [(0, 156), (156, 412), (412, 600)] and track_ref.fragments(256, 3) == [(0, 3)]
+    assert track_ref.fragments(255, 2) == [(0, 1), (1, 2)] and track_ref.fragments(7, 0) == []
+    for name in ("invalid_tile", "single_769"):
+        s = track_scenes.seams()[name]
+        truth, tiles, scan = _ref(s, kind=np.longdouble), _ref(s, form="tiles"), _ref(s, form="scan")
+        assert tiles["counts"] == truth["counts"] and np.array_equal(tiles["used"], truth["used"])
+        assert any(tiles[out].tobytes() != scan[out].tobytes() for out in OUTPUTS)      # another tree
+        # the tolerance a device gets on this scene (the record of the OTHER two forms times 16), against longdouble
+        for out in OUTPUTS:
+            a, b = tiles[out].astype(np.longdouble), truth[out]
+            assert np.array_equal(np.isnan(a), np.isnan(b))
+            assert float(np.nanmax(np.abs(a - b))) <= track_check.bound(TOLERANCES["scenes"][name][out], tiles[out]), (name, out)
 
 
 @pytest.mark.parametrize("name", ["gating_1", "single_513", "invalid_tile", "equal_times", "epoch_ms", "no_valid_row"])

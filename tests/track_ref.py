@@ -1,7 +1,9 @@
 """The NumPy statement of thr_track (include/thrifty_hip.h): the plain sequential recursion, in float64 and in
-np.longdouble, and the same filter and smoother as scans whose elements are combined in a balanced tree.
+np.longdouble, and the same filter and smoother as scans whose elements are combined in a balanced tree over the whole
+track ("scan") or as track.hip combines them ("tiles": fragments cut where the sorted position crosses a multiple of
+the tile length, a doubling-step scan inside each, a sequential walk of five-double carries between them).
 
-    run(scene-like columns, q, v0, gate, max_rounds, kind=np.float64, form="sequential" | "scan") -> dict
+    run(scene-like columns, q, v0, gate, max_rounds, kind=np.float64, form="sequential" | "scan" | "tiles") -> dict
 
 Every array is in input row order except track_tx / track_ptr / track_stats / track_flags (per track) and order."""
 import numpy as np
@@ -163,8 +165,7 @@ def tree_scan(e, combine, backward=False):
     return e[::-1] if backward else e
 
 
-def filter_axis_scan(t, z, r, mask, q, v0, kind):
-    pre = tree_scan(filter_elements(t, z, r, mask, q, v0, kind), filter_combine)
+def _innovations(t, z, r, pre, q, kind):
     m, P = pre[:, 4:6].copy(), pre[:, 6:9].copy()
     nu, S = np.zeros(len(t), kind), np.ones(len(t), kind)
     if len(t) > 1:     # the gate kernel's step: the prediction from the state of the row before
@@ -176,45 +177,113 @@ def filter_axis_scan(t, z, r, mask, q, v0, kind):
     return m, P, nu, S
 
 
+def filter_axis_scan(t, z, r, mask, q, v0, kind):
+    return _innovations(t, z, r, tree_scan(filter_elements(t, z, r, mask, q, v0, kind), filter_combine), q, kind)
+
+
 def smooth_axis_scan(t, m, P, q, kind):
     suf = tree_scan(smooth_elements(t, m, P, q, kind), smooth_combine, backward=True)
     return suf[:, 4:6].copy(), suf[:, 6:9].copy()
 
 
+# ------------------------------------------------------------------ the same as track.hip's tiles and carries
+TILE = 256
+
+
+def fragments(first, n, tile=TILE):
+    """The n rows of a track whose first row has sorted position `first` in the whole call -> [(a, e), ...]: the
+    ranges of its rows between the multiples of the tile length."""
+    cuts = [0] + [p - first for p in range((first // tile + 1) * tile, first + n, tile)] + [n]
+    return [(a, e) for a, e in zip(cuts[:-1], cuts[1:]) if e > a]
+
+
+def _state(o):
+    """(0, state, 0): what k_filter_carry and k_smooth_carry keep of a combination, slots 4 .. 8 in both operators."""
+    c = np.zeros_like(o)
+    c[4:9] = o[4:9]
+    return c
+
+
+def filter_axis_tiles(t, z, r, mask, q, v0, kind, first=0, tile=TILE):
+    """k_filter<false>, k_filter_carry, k_filter<true>: every fragment's total without a carry, the walk over the
+    fragments in order (carry (x) total), the carry combined into the fragment's first element, and the scan again.
+    One departure: the fragments here are cut from the START row (`first` is its sorted position) and the first of them
+    reads no carry, while track.hip cuts from the track's first row and, where the start row lies beyond the first
+    tile boundary (invalid rows at a track's head, the `invalid_tile` kind of scene), combines a zero carry into the
+    fragments of identity rows before it and into the one that holds the start row.  The start row's A = 0 annihilates
+    whatever stands before it, so the state is the same; the path is not, and no scene of clauses() takes it."""
+    e = filter_elements(t, z, r, mask, q, v0, kind)
+    frags = fragments(first, len(t), tile)
+    carry, carries = np.zeros(14, kind), []
+    for a, b in frags:
+        carries.append(carry)
+        total = tree_scan(e[a:b], filter_combine)[-1]
+        carry = _state(filter_combine(carry[None], total[None])[0])
+    pre = np.zeros_like(e)
+    for f, (a, b) in enumerate(frags):
+        el = e[a:b].copy()
+        if f:       # a track's first fragment reads no carry
+            el[0] = filter_combine(carries[f][None], el[:1])[0]
+        pre[a:b] = tree_scan(el, filter_combine)
+    return _innovations(t, z, r, pre, q, kind)
+
+
+def smooth_axis_tiles(t, m, P, q, kind, first=0, tile=TILE):
+    """k_smooth<false>, k_smooth_carry, k_smooth<true>: the same backwards (total (x) carry, last element (x) carry)."""
+    e = smooth_elements(t, m, P, q, kind)
+    frags = fragments(first, len(t), tile)
+    carry, carries = np.zeros(9, kind), [None] * len(frags)
+    for f in range(len(frags) - 1, -1, -1):
+        a, b = frags[f]
+        carries[f] = carry
+        total = tree_scan(e[a:b], smooth_combine, backward=True)[0]
+        carry = _state(smooth_combine(total[None], carry[None])[0])
+    suf = np.zeros_like(e)
+    for f, (a, b) in enumerate(frags):
+        el = e[a:b].copy()
+        if f + 1 < len(frags):       # a track's last fragment reads no carry
+            el[-1] = smooth_combine(el[-1:], carries[f][None])[0]
+        suf[a:b] = tree_scan(el, smooth_combine, backward=True)
+    return suf[:, 4:6].copy(), suf[:, 6:9].copy()
+
+
 # ------------------------------------------------------------------ the whole call
 def run(tx, timestamp, x, y, rx, ry, valid=None, q=None, v0=10.0, gate=GATE_999, max_rounds=4, kind=np.float64,
-        form="sequential", smoother=True):
-    """thr_track.  `nis_rounds`: the nis of every filter run (for the gate's margin)."""
+        form="sequential", smoother=True, tile=TILE):
+    """thr_track.  `nis_rounds`: the nis of every filter run (for the gate's margin); `masks`: the mask every filter
+    run was made with.  `tile` matters to form="tiles" alone."""
     n = len(tx)
     order, track_tx, track_ptr = sort_rows(tx, timestamp)
     valid = np.ones(n, dtype=bool) if valid is None else np.asarray(valid).astype(bool)
     cols = [np.asarray(v, dtype=np.float64).astype(kind) for v in (timestamp, x, y, rx, ry)]
     q, v0 = kind(q), kind(v0)
-    filt_fn = filter_axis if form == "sequential" else filter_axis_scan
-    smooth_fn = smooth_axis if form == "sequential" else smooth_axis_scan
+    filt_fn = {"sequential": filter_axis, "scan": filter_axis_scan, "tiles": filter_axis_tiles}[form]
+    smooth_fn = {"sequential": smooth_axis, "scan": smooth_axis_scan, "tiles": smooth_axis_tiles}[form]
     nt = len(track_tx)
     out = {"order": order, "track_tx": track_tx, "track_ptr": track_ptr, "used": np.zeros(n, np.uint8),
            "nis": np.full(n, np.nan, kind), "filt": np.full((n, 4), np.nan, kind), "filt_var": np.full((n, 6), np.nan, kind),
            "smooth": np.full((n, 4), np.nan, kind), "smooth_var": np.full((n, 6), np.nan, kind),
            "track_stats": np.zeros((nt, 8), kind), "track_flags": np.zeros(nt, np.int32)}
-    tracks = []
+    tracks, where = [], []      # a track's rows from the start row on; form="tiles": the sorted position of the first
     for c in range(nt):
         rows = order[track_ptr[c]:track_ptr[c + 1]]
         ok = np.flatnonzero(valid[rows])
         rows = rows[ok[0]:] if len(ok) else rows[:0]       # from the start row on
         tracks.append(rows)
+        where.append(dict(first=int(track_ptr[c] + (ok[0] if len(ok) else 0)), tile=tile) if form == "tiles" else {})
     mask = valid.copy()
-    rounds, converged, nis_rounds = 0, 0, []
+    rounds, converged, nis_rounds, masks = 0, 0, [], []
 
     def one_run():
         nis = np.full(n, np.nan, kind)
-        for rows in tracks:
+        masks.append(mask.copy())
+        for rows, at in zip(tracks, where):
             if not len(rows):
                 continue
             t = cols[0][rows]
             value = np.zeros(len(rows), kind)
             for axis in range(2):
-                m, P, nu, S = filt_fn(t, cols[1 + axis][rows], cols[3 + axis][rows], mask[rows], q, v0, kind)
+                m, P, nu, S = filt_fn(t, cols[1 + axis][rows], cols[3 + axis][rows], mask[rows], q, v0, kind, **at)
                 out["filt"][rows, 2 * axis:2 * axis + 2], out["filt_var"][rows, 3 * axis:3 * axis + 3] = m, P
                 value = value + nu * nu / S
             value[0] = 0
@@ -253,7 +322,8 @@ def run(tx, timestamp, x, y, rx, ry, valid=None, q=None, v0=10.0, gate=GATE_999,
         t = cols[0][rows]
         if smoother:
             for axis in range(2):
-                ms, Ps = smooth_fn(t, out["filt"][rows, 2 * axis:2 * axis + 2], out["filt_var"][rows, 3 * axis:3 * axis + 3], q, kind)
+                ms, Ps = smooth_fn(t, out["filt"][rows, 2 * axis:2 * axis + 2], out["filt_var"][rows, 3 * axis:3 * axis + 3], q, kind,
+                                       **where[c])
                 out["smooth"][rows, 2 * axis:2 * axis + 2], out["smooth_var"][rows, 3 * axis:3 * axis + 3] = ms, Ps
         used = out["used"][rows].astype(bool)
         sm = out["smooth"][rows]
@@ -266,5 +336,6 @@ def run(tx, timestamp, x, y, rx, ry, valid=None, q=None, v0=10.0, gate=GATE_999,
     out["counts"] = {"rows": n, "tracks": nt, "used": int(out["used"].sum()),
                      "rejected": int(np.count_nonzero(valid & tracked) - out["used"].sum()), "rounds": rounds, "converged": converged}
     out["nis_rounds"] = nis_rounds
+    out["masks"] = masks
     out["tracked"] = tracked
     return out
