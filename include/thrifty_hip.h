@@ -102,7 +102,11 @@ extern "C" {
  *      use analytic solution or previous position as initial value")
  *    + thr_debug_seg_tile_grid / thr_debug_seg_tile_stats -- the cap on the workgroups of a tile kernel of thr_toadstats,
  *      thr_beaconsync, thr_tdoastats, thr_reldist and thr_track (tests reach the loop's later trips at small
- *      shapes), and how many trips the launches since took (results unchanged) */
+ *      shapes), and how many trips the launches since took (results unchanged)
+ *    + thr_tdoamatrix / thr_tdmat_fetch / thr_tdmat_free / thr_debug_tdoamatrix_times / _geometry -- the numbers of
+ *      the reference's scripts/tdoa_matrix.py: the TDOAs of every transmitter estimated again with ONE beacon's
+ *      matches as the clock model, for every (rx0 < rx1, beacon, transmitter) cell in one call, with the cell's
+ *      outlier mask and statistics (thr_tdoa_model's per-task arithmetic: csrc/tdoa_task.hpp states it once) */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -1763,6 +1767,83 @@ void thr_posg_free(thr_posg_result* result);
  * starts (one kernel: the surface never leaves LDS), refinement (tasks 1 .. K), choice, copies out (summed over the
  * fetches)} */
 int thr_debug_posg_times(double* ms_out /* [6] */);
+
+/* ---- Per-beacon TDOA matrices (the reference's scripts/tdoa_matrix.py:100-141, 144-191) for every cell at once.
+ * Host pointers, synchronous, no engine handle; the results stay on the device behind a handle until
+ * thr_tdmat_fetch (the pattern of thr_reldist).  The columns are positions into the detection arrays; the matches
+ * are CSR (match m is match_idx[match_ptr[m] .. match_ptr[m + 1])), each of ONE transmitter, read off its first
+ * detection.
+ *   rows    every match whose txid is a listed beacon or a target gives one ROW per pair of its detections at
+ *           listed receivers, det0 at the lower receiver (the script's extract_match_matrix: one detection per
+ *           receiver per match).  The rows of (tx, rx0, rx1) in match order are that transmitter's LIST at that pair.
+ *   tasks   every row of a target t gives one TASK per listed beacon b != t.  The cell key is (rx0, rx1, b, t); the
+ *           cells are in ascending key order, the tasks of a cell in row (match) order.  A cell exists when it has a
+ *           task.  targets empty: every txid present in a selected match is a target, the beacons included.
+ *   flags   THR_TDMAT_CELL_TOO_FEW: the list (b, rx0, rx1) or the list (t, rx0, rx1) has fewer than 3 rows (the
+ *           script's constants, whatever the model).  The cell's tasks are not estimated: status THR_TDMAT_SKIPPED,
+ *           n_window = n_kept = 0, tdoa NaN.
+ *   task    on the list (b, rx0, rx1) exactly thr_tdoa_model's arithmetic (csrc/tdoa_task.hpp): Python's bisect_left /
+ *           bisect_right on the list's det0 timestamps at t0 -/+ window, t0 the task's det0 timestamp; the median /
+ *           MAD mask on soa0 - soa1 when the window holds more than one pair; the model (THR_TDOA_*, deg 1..3 for the
+ *           two polynomials) with beacon_sdoa = (dist[rx0][b] - dist[rx1][b]) / 2.997e8 * sample_rate (dist NULL:
+ *           zeros, the script's geometry); |tdoa| >= 30e3 / 2.997e8 is THR_TDMAT_OUT_OF_RANGE, no model
+ *           THR_TDMAT_NO_MODEL; both leave tdoa and model_quality NaN.  snr = the mean of the task's two
+ *           (energy / noise)**2, model_quality as thr_tdoa_model.
+ *   mask    over the tasks of a cell that gave a TDOA, in task order: stat_tools.is_outlier (threshold 3.5) on the
+ *           TDOAs in seconds, numpy's float64 operations; a cell of one TDOA keeps it.  A task without a TDOA has
+ *           outlier 0.  median and MAD are those of the cell's TDOAs (NaN without one).
+ *   stats   over the TDOAs the mask kept, x = tdoa * 2.997e8: mean, population std, rms, min, max (metres); tiled
+ *           segmented reductions, slab partials combined in tile order, no atomics: a repeated call returns the same
+ *           bits.  A cell without a kept TDOA holds NaN.
+ * dist is float64[n_receivers][n_beacons] in the order of the two lists as given (it needs the receiver list).
+ * THR_ERR_ARG, before anything is launched: a null argument; a beacon or a receiver listed twice; more than
+ * THR_TDMAT_MAX_BEACONS beacons; a model outside THR_TDOA_POLY .. THR_TDOA_LINEAR or a polynomial's deg outside
+ * 1..3; a window that is negative or not finite, a sample_rate that is not positive; a malformed CSR or a match with
+ * two detections of one receiver (the host pass of thr_reldist); more than 2^28 tasks.  Nothing selected -- no
+ * match, no beacon, no pair at listed receivers -- is THR_OK with zero cells (cell_ptr = {0}). */
+#define THR_TDMAT_MAX_BEACONS 64
+typedef struct thr_tdmat_counts {
+    size_t tasks, cells, rows /* of all lists */, tdoas /* tasks with status THR_TDMAT_OK */;
+} thr_tdmat_counts;
+typedef struct thr_tdmat thr_tdmat; /* the handle: thr_tdoamatrix is the call */
+#define THR_TDMAT_CELL_TOO_FEW 1
+#define THR_TDMAT_OK 0
+#define THR_TDMAT_NO_MODEL 1
+#define THR_TDMAT_OUT_OF_RANGE 2
+#define THR_TDMAT_SKIPPED 3
+/* what thr_tdmat_fetch copies, in terms of thr_tdmat_counts */
+#define THR_TDMAT_CELL_KEY 0       /* int32[cells][4]: rx0, rx1, beacon, tx */
+#define THR_TDMAT_CELL_PTR 1       /* int64[cells + 1] into the tasks */
+#define THR_TDMAT_CELL_FLAGS 2     /* int32[cells], THR_TDMAT_CELL_* */
+#define THR_TDMAT_CELL_COUNTS 3    /* int64[cells][5]: beacon rows, target rows, TDOAs, failures, kept */
+#define THR_TDMAT_CELL_STATS 4     /* float64[cells][5]: mean, std, rms, min, max of the kept TDOAs (metres) */
+#define THR_TDMAT_MEDIANS 5        /* float64[cells][2]: median and MAD of the cell's TDOAs (seconds) */
+#define THR_TDMAT_TASK_DET 6       /* int64[tasks][2]: detection at rx0, at rx1 */
+#define THR_TDMAT_TASK_MATCH 7     /* int64[tasks]: the match the task's row came from */
+#define THR_TDMAT_TIMESTAMP 8      /* float64[tasks]: the timestamp of det0 */
+#define THR_TDMAT_TDOA 9           /* float64[tasks], seconds; NaN for a failure or a skipped task */
+#define THR_TDMAT_STATUS 10        /* int32[tasks]: THR_TDMAT_OK / _NO_MODEL / _OUT_OF_RANGE / _SKIPPED */
+#define THR_TDMAT_SNR 11           /* float64[tasks] */
+#define THR_TDMAT_MODEL_QUALITY 12 /* float64[tasks]; NaN without a TDOA */
+#define THR_TDMAT_N_WINDOW 13      /* int32[tasks]: beacon rows in the task's window */
+#define THR_TDMAT_N_KEPT 14        /* int32[tasks]: those the window's outlier mask kept */
+#define THR_TDMAT_OUTLIER 15       /* uint8[tasks]: 1 = the cell mask drops this TDOA */
+#define THR_TDMAT_N_OUTPUTS 16
+int thr_tdoamatrix(int device_id, size_t n_det, const int32_t* rxid, const int32_t* txid, const double* timestamp,
+                   const double* soa, const double* energy, const double* noise, size_t n_matches,
+                   const int64_t* match_ptr, const int64_t* match_idx, const int32_t* receivers /* NULL: all */,
+                   size_t n_receivers, const int32_t* beacons, size_t n_beacons,
+                   const int32_t* targets /* none: every txid present */, size_t n_targets,
+                   const double* dist /* NULL: zeros */, double window, double sample_rate, int model, int deg,
+                   thr_tdmat** result_out, thr_tdmat_counts* counts_out);
+/* `which` is a THR_TDMAT_* index; dst_bytes must be the size given there */
+int thr_tdmat_fetch(thr_tdmat* result, int which, void* dst, size_t dst_bytes);
+void thr_tdmat_free(thr_tdmat* result);
+/* Milliseconds of the calling thread's last thr_tdoamatrix: {copies in, rows and tasks, estimate, mask and
+ * statistics, copies out (summed over the fetches)} */
+int thr_debug_tdoamatrix_times(double* ms_out /* [5] */);
+/* tile length and workgroup size of the segmented stages, tasks (wavefronts) per workgroup of the estimate kernel */
+int thr_debug_tdoamatrix_geometry(int* tile_len, int* workgroup, int* tasks_per_workgroup);
 
 #ifdef __cplusplus
 }

@@ -58,6 +58,7 @@ EXPORTS = [
     "thr_posq", "thr_posq_fetch", "thr_posq_free", "thr_debug_posq_times",
     "thr_track", "thr_track_fetch", "thr_track_free", "thr_debug_track_times", "thr_debug_track_geometry",
     "thr_posg", "thr_posg_fetch", "thr_posg_free", "thr_debug_posg_times",
+    "thr_tdoamatrix", "thr_tdmat_fetch", "thr_tdmat_free", "thr_debug_tdoamatrix_times", "thr_debug_tdoamatrix_geometry",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -74,6 +75,7 @@ RELDIST_COUNTS = ("rows", "cells", "speeds", "speed_points", "dop_points")
 POSQ_COUNTS = ("groups", "rows", "flagged", "tasks")
 TRACK_COUNTS = ("rows", "tracks", "used", "rejected", "rounds", "converged")
 POSG_COUNTS = ("groups", "rows", "tasks", "starts", "grid", "map_groups")
+TDMAT_COUNTS = ("tasks", "cells", "rows", "tdoas")
 
 
 class ThrBsyncCounts(C.Structure):        # thr_bsync_counts
@@ -105,6 +107,10 @@ class ThrPosgOpts(C.Structure):           # thr_posg_opts
     _fields_ = [("max_iter", C.c_int32), ("grid", C.c_int32), ("starts", C.c_int32), ("x0", C.c_double * 2),
                 ("margin_m", C.c_double), ("merge_m", C.c_double), ("ratio", C.c_double), ("floor_m", C.c_double),
                 ("map_first", C.c_int64), ("map_count", C.c_int32)]
+
+
+class ThrTdmatCounts(C.Structure):        # thr_tdmat_counts
+    _fields_ = [(name, C.c_size_t) for name in TDMAT_COUNTS]
 
 
 class ThrTrackCounts(C.Structure):        # thr_track_counts
@@ -436,7 +442,11 @@ def load_library():
     lib.thr_posg.argtypes = ([C.c_int, C.c_size_t] + [vp] * 5 + [C.c_int, C.c_int, vp, C.POINTER(ThrPosgOpts), C.POINTER(vp),
                              C.POINTER(ThrPosgCounts)])
     lib.thr_debug_posg_times.argtypes = [C.POINTER(C.c_double)]
-    for stem in ("bsync", "tdstats", "reldist", "posq", "track", "posg"):
+    lib.thr_tdoamatrix.argtypes = ([C.c_int, C.c_size_t] + [vp] * 6 + [C.c_size_t, vp, vp] + [vp, C.c_size_t] * 3 +
+                                   [vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(ThrTdmatCounts)])
+    lib.thr_debug_tdoamatrix_times.argtypes = [C.POINTER(C.c_double)]
+    lib.thr_debug_tdoamatrix_geometry.argtypes = [ip, ip, ip]
+    for stem in ("bsync", "tdstats", "reldist", "posq", "track", "posg", "tdmat"):
         getattr(lib, "thr_%s_fetch" % stem).argtypes = [vp, C.c_int, vp, C.c_size_t]
         getattr(lib, "thr_%s_free" % stem).argtypes = [vp]
         getattr(lib, "thr_%s_free" % stem).restype = None
@@ -2096,6 +2106,88 @@ def reldist_geometry():
     t, w, lanes = C.c_int(), C.c_int(), C.c_int()
     _check(lib, lib.thr_debug_reldist_geometry(C.byref(t), C.byref(w), C.byref(lanes)))
     return t.value, w.value, lanes.value
+
+
+# the detection columns of thr_tdoamatrix, in its argument order
+TDMAT_COLUMNS = (("rxid", np.int32), ("txid", np.int32), ("timestamp", np.float64), ("soa", np.float64),
+                 ("energy", np.float64), ("noise", np.float64))
+TDMAT_MAX_BEACONS = 64          # THR_TDMAT_MAX_BEACONS
+TDMAT_CELL_TOO_FEW = 1          # THR_TDMAT_CELL_TOO_FEW
+TDMAT_OK, TDMAT_NO_MODEL, TDMAT_OUT_OF_RANGE, TDMAT_SKIPPED = 0, 1, 2, 3      # THR_TDMAT_* task statuses
+# THR_TDMAT_*: name -> (index, dtype, shape as a function of the counts)
+TDMAT_OUTPUTS = {
+    "cell_key": (0, np.int32, lambda c: (c["cells"], 4)),
+    "cell_ptr": (1, np.int64, lambda c: (c["cells"] + 1,)),
+    "cell_flags": (2, np.int32, lambda c: (c["cells"],)),
+    "cell_counts": (3, np.int64, lambda c: (c["cells"], 5)),
+    "cell_stats": (4, np.float64, lambda c: (c["cells"], 5)),
+    "medians": (5, np.float64, lambda c: (c["cells"], 2)),
+    "task_det": (6, np.int64, lambda c: (c["tasks"], 2)),
+    "task_match": (7, np.int64, lambda c: (c["tasks"],)),
+    "timestamp": (8, np.float64, lambda c: (c["tasks"],)),
+    "tdoa": (9, np.float64, lambda c: (c["tasks"],)),
+    "status": (10, np.int32, lambda c: (c["tasks"],)),
+    "snr": (11, np.float64, lambda c: (c["tasks"],)),
+    "model_quality": (12, np.float64, lambda c: (c["tasks"],)),
+    "n_window": (13, np.int32, lambda c: (c["tasks"],)),
+    "n_kept": (14, np.int32, lambda c: (c["tasks"],)),
+    "outlier": (15, np.uint8, lambda c: (c["tasks"],)),
+}
+
+
+def tdoamatrix(columns, match_ptr, match_idx, beacons, receivers=None, targets=None, dist=None, window=4.0, sample_rate=2.4e6,
+               model=0, deg=2, outputs=None, device_id=0):
+    """thr_tdoamatrix on the six detection columns (a mapping with the names of TDMAT_COLUMNS) and the matches as CSR
+    -> (counts dict, {name: array}) with every output of TDMAT_OUTPUTS (or those named in `outputs`) fetched.
+    `dist`: float64[len(receivers)][len(beacons)] in the order of the two lists (None: zeros); `model`: a
+    TDOA_MODELS code.  ValueError for what thr_tdoamatrix refuses."""
+    lib = load_library()
+    cols = _columns(columns, TDMAT_COLUMNS, "tdoamatrix")
+    n = len(cols[0])
+    ptr = np.ascontiguousarray(match_ptr, dtype=np.int64)
+    idx = np.ascontiguousarray(match_idx, dtype=np.int64)
+    if ptr.ndim != 1 or idx.ndim != 1 or len(ptr) < 1 or (ptr[-1] != len(idx) if len(ptr) else True):
+        raise ValueError("tdoamatrix: match_ptr and match_idx are not a CSR pair")
+    if beacons is None:
+        raise ValueError("tdoamatrix: a list of beacons is needed")
+    lists = [None if v is None else np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (receivers, beacons, targets)]
+    if dist is not None:
+        if lists[0] is None:
+            raise ValueError("tdoamatrix: dist needs the list of receivers its rows are of")
+        dist = np.ascontiguousarray(dist, dtype=np.float64)
+        if dist.shape != (len(lists[0]), len(lists[1])):
+            raise ValueError("tdoamatrix: dist must be float64[%d receivers][%d beacons]" % (len(lists[0]), len(lists[1])))
+    keep = np.zeros(1, dtype=np.int64)      # an empty array still needs a pointer that is not NULL
+    args = []
+    for v in lists:
+        args += [None if v is None else (v.ctypes.data if len(v) else keep.ctypes.data), 0 if v is None else len(v)]
+    handle, counts = C.c_void_p(), ThrTdmatCounts()
+    rc = lib.thr_tdoamatrix(int(device_id), n, *[col.ctypes.data if n else None for col in cols], len(ptr) - 1, ptr.ctypes.data,
+                            idx.ctypes.data if len(idx) else keep.ctypes.data, *args,
+                            None if dist is None else (dist.ctypes.data if dist.size else keep.ctypes.data), float(window),
+                            float(sample_rate), int(model), int(deg), C.byref(handle), C.byref(counts))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    c = {name: int(getattr(counts, name)) for name in TDMAT_COUNTS}
+    return c, _fetch_all(lib, "tdmat", handle, c, TDMAT_OUTPUTS, outputs)
+
+
+def tdoamatrix_times():
+    """Milliseconds (HIP events) of this thread's last tdoamatrix(): copies in, rows and tasks, estimate, mask and
+    statistics, copies out."""
+    lib = load_library()
+    ms = (C.c_double * 5)()
+    _check(lib, lib.thr_debug_tdoamatrix_times(ms))
+    return tuple(ms)
+
+
+def tdoamatrix_geometry():
+    """thr_debug_tdoamatrix_geometry -> (tile length T, workgroup size W, tasks per workgroup of the estimate kernel)."""
+    lib = load_library()
+    t, w, tasks = C.c_int(), C.c_int(), C.c_int()
+    _check(lib, lib.thr_debug_tdoamatrix_geometry(C.byref(t), C.byref(w), C.byref(tasks)))
+    return t.value, w.value, tasks.value
 
 
 POSQ_INCONSISTENT, POSQ_EXCLUDED, POSQ_NO_CANDIDATE = 1, 2, 4      # THR_POSQ_* flags

@@ -1,5 +1,5 @@
 // Rows into cells, cells into fragments, and what a stage does with a cell's values: everything that the
-// statistics stages on seg_reduce.hpp share beyond the reduction itself (syncstats.hip, reldist.hip).
+// statistics stages on seg_reduce.hpp share beyond the reduction itself (syncstats.hip, reldist.hip, tdoamatrix.hip).
 //   find_sorted / upload_list   an ascending id list on the device, searched by bisection;
 //   scan                        an inclusive sum of flags and its total, read back;
 //   build_layout / reduce       the fragments of contiguous segments (a Layout), and one reduction over them;
@@ -186,9 +186,10 @@ inline int sort_cells(DevBuf& key_hi, DevBuf& key_lo, int m, Scratch& w, Cells& 
 
 // ------------------------------------------------------------------ matches into rows of detection pairs
 // The host pass over the matches: match_ptr starts at 0 and does not decrease, every match_idx is a detection,
-// no receiver appears twice in a match; *n_pairs = the pairs of detections that share a match.
+// no receiver appears twice in a match; *n_pairs = the pairs of detections that share a match.  No pair at all is
+// an error unless the stage says that it may be (may_be_empty: it answers with an empty result).
 inline int check_matches(const char* who, size_t n_det, const int32_t* rxid, size_t n_matches, const int64_t* match_ptr,
-                         const int64_t* match_idx, uint64_t* n_pairs) {
+                         const int64_t* match_idx, uint64_t* n_pairs, bool may_be_empty = false) {
     if (match_ptr[0] != 0) return thr::fail_msg(THR_ERR_ARG, "%s: match_ptr[0] must be 0", who);
     uint64_t pairs = 0;
     for (size_t m = 0; m < n_matches; ++m) {
@@ -206,7 +207,7 @@ inline int check_matches(const char* who, size_t n_det, const int32_t* rxid, siz
         pairs += uint64_t(e - a) * uint64_t(e - a > 0 ? e - a - 1 : 0) / 2;
     }
     if (pairs > (uint64_t(1) << 28)) return thr::fail_msg(THR_ERR_ARG, "%s: too many detection pairs", who);
-    if (n_matches == 0 || pairs == 0) return thr::fail_msg(THR_ERR_ARG, "%s: the selection is empty", who);
+    if ((n_matches == 0 || pairs == 0) && !may_be_empty) return thr::fail_msg(THR_ERR_ARG, "%s: the selection is empty", who);
     *n_pairs = pairs;
     return THR_OK;
 }

@@ -9,7 +9,8 @@ that the reference's stat_tools.is_outlier keeps (modified z-score over the medi
 cell of one row is left alone, as in scripts/tdoa_matrix.py).  One device call (thr_tdoastats,
 csrc/syncstats.hip) covers every cell; `variance_table`, `mean_table` and `count_table` are the per-transmitter
 tabulation of scripts/tdoa_matrix.py for one receiver pair, from an existing .tdoa (its re-estimation per
-beacon is not part of this port).  No plot: `TdoaStats.cell` gives the rows behind the reference's figure.
+beacon, the beacon x transmitter matrices themselves, is `thrifty_amd.tdoa_matrix`).  No plot: `TdoaStats.cell`
+gives the rows behind the reference's figure.
 """
 from __future__ import annotations
 
