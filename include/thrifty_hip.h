@@ -106,7 +106,11 @@ extern "C" {
  *    + thr_tdoamatrix / thr_tdmat_fetch / thr_tdmat_free / thr_debug_tdoamatrix_times / _geometry -- the numbers of
  *      the reference's scripts/tdoa_matrix.py: the TDOAs of every transmitter estimated again with ONE beacon's
  *      matches as the clock model, for every (rx0 < rx1, beacon, transmitter) cell in one call, with the cell's
- *      outlier mask and statistics (thr_tdoa_model's per-task arithmetic: csrc/tdoa_task.hpp states it once) */
+ *      outlier mask and statistics (thr_tdoa_model's per-task arithmetic: csrc/tdoa_task.hpp states it once)
+ *    + thr_coverage / thr_coverage_fetch / thr_coverage_free / thr_debug_coverage_times -- a coverage map of a
+ *      deployment without a recording: per cell of a raster the dop, the predicted covariance of thr_pos's
+ *      estimator under per-receiver arrival noise, and the error statistics of T simulated transmissions, each
+ *      solved by thr_pos's own iteration (the reference's "TODO: estimate confidence with SNR and DOP") */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -1844,6 +1848,114 @@ void thr_tdmat_free(thr_tdmat* result);
 int thr_debug_tdoamatrix_times(double* ms_out /* [5] */);
 /* tile length and workgroup size of the segmented stages, tasks (wavefronts) per workgroup of the estimate kernel */
 int thr_debug_tdoamatrix_geometry(int* tile_len, int* workgroup, int* tasks_per_workgroup);
+
+/* ---- Coverage map: where can this deployment position a tag, how well, and where does the fixed start lose it.
+ * No recording: receiver coordinates rx_coords[n_rx][2] and a timing noise sigma_rx[n_rx] (metres, >= 0) in, per cell
+ * of a raster the analytic prediction and the statistics of T simulated transmissions out.  Host pointers,
+ * synchronous, the results stay on the device behind a handle until thr_coverage_fetch (the pattern of thr_posg).
+ * 2-D only, n_rx <= 64 (thr_pos's limit).  All arithmetic is float64, no product and sum is contracted.
+ *   cells    cx[i] = lo0 + (i + 0.5) * ((hi0 - lo0) / nx), i = 0 .. nx - 1; cy[j] alike from lo1, hi1, ny; cell
+ *            c = j * nx + i, p_c = (cx[i], cy[j]).
+ *   hearing  receiver r HEARS cell c when range_m <= 0 or sqrt(dx * dx + dy * dy) <= range_m, (dx, dy) = rx_r - p_c.
+ *            h = the hearing receivers (n_heard; heard_mask bit r).  h < 3: the cell is THR_COV_UNCOVERED, it gets no
+ *            trials, its counts are 0 and every float64 output is NaN.  The ROWS of a cell are all pairs (a, b), a < b,
+ *            of its hearing receivers, a-major in ascending receiver index: m = h (h - 1) / 2 rows.
+ *   analytic at p_c, with e_r = ((rx_r - p) / |rx_r - p|) taken per component as thr_pos takes it (ax / da):
+ *            g_row = e_a - e_b; N = sum over the rows in order of g g' (three accumulators from 0.0); dop = thr_pos's
+ *            closed form sqrt((N00 + N11) / det N), -1 where det N = N00 * N11 - N01 * N01 is 0 or not finite (the
+ *            cell is then THR_COV_DEGENERATE and its predictions are NaN).  thr_pos's estimator is the UNWEIGHTED
+ *            least squares over ALL pairs, and the rows' noises n_a - n_b are correlated through the receivers they
+ *            share, so its covariance to first order is not sigma^2 inv(N) but
+ *                u_r = sum over the rows naming r, in order, of s g_row (s = +1: r is rx0, -1: r is rx1)
+ *                M = sum over the hearing r, ascending, of sigma_r^2 u_r u_r'      Cov = inv(N) M inv(N)
+ *            with I = (N11, -N01, N00) / det (three divisions), T = I M, Cov = T I, every 2 x 2 product written
+ *            a * b + c * d.  pred = (dop, sxx, sxy, syy, rms = sqrt(sxx + syy)).
+ *   noise    of (cell c, trial t, receiver r): Philox4x32-10, key (seed_lo, seed_hi), counter (c, t, r, 0),
+ *            multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85; output words w0, w1 give
+ *            u1 = (w0 + 1) * 2^-32 in (0, 1], u2 = w1 * 2^-32; z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2),
+ *            n_r = sigma_rx[r] * z.  One normal per counter.  Known answers: counter and key 0 ->
+ *            6627e8d5 e169c58d bc57ac4c 9b00dbd8; all ones -> 408f276d 41c83b0e a20bc7c6 6d5451fd.
+ *   trial    row (a, b) of trial t carries tdoa = ((|rx_a - p| - |rx_b - p|) + (n_a - n_b)) / 2.997e8 and snr 1.0.
+ *            Every trial is one group handed to thr_pos's stage (csrc/pos.hip's core, on device pointers) with
+ *            opts->x0, opts->max_iter and thr_pos's box: its (pos, status, iters) are the bits thr_pos returns on
+ *            that group.  TASK k = covered_index(c) * T + t: cell-major over the covered cells in ascending c.
+ *   slabs    the tasks are materialised and solved slab by slab: consecutive tasks, at most slab_groups of
+ *            them, the last slab shorter; a slab boundary may fall inside a cell and moves no result.
+ *            opts->slab_groups = 0 takes the default, THR_COV_SLAB_BYTES / (bytes of one task's columns with
+ *            n_rx (n_rx - 1) / 2 rows); a positive value is a test knob and is capped by that default.
+ *   error    of a trial: status THR_POS_NONFINITE or a position that is not finite gives e = +inf; otherwise
+ *            dx = x - cx, dy = y - cy, e = sqrt(dx * dx + dy * dy).  A trial is GOOD when its status is THR_POS_OK and
+ *            e <= gross_m.
+ *   counts   int32[6] per cell: trials ending THR_POS_OK, _AT_BOUND, _UNCONVERGED, _NONFINITE; n_good; n_gross =
+ *            T - n_good.  iters_sum is the int64 sum of the trials' iteration counts.
+ *   stats    float64[8] per cell: bias_x, bias_y = the means of dx, dy over the good trials; sxx, sxy, syy = the means
+ *            of dx * dx, dx * dy, dy * dy; rms = sqrt(sxx + syy); all NaN when n_good == 0.  ONE order: lane l = 0 ..
+ *            63 adds its good trials l, l + 64, ... in ascending order to an accumulator that starts at 0.0; then for
+ *            d = 32, 16, 8, 4, 2, 1: lane[l] = lane[l] + lane[l + d] for l < d; the sum is lane[0], the mean is
+ *            sum / n_good.  No atomics: the same bytes every time and for every slab size.
+ *            q50, q95 over ALL T trials with +inf included: sorted[(T + 1) / 2 - 1] and sorted[(95 T + 99) / 100 - 1]
+ *            (integer divisions: the nearest-rank ceil(p T) - 1).  q95 = +inf says more than 5 % of the trials have
+ *            no position.  One workgroup per cell, e in LDS padded with +inf to a power of two, a bitonic sort.
+ *   flags    THR_COV_UNCOVERED; THR_COV_DEGENERATE; THR_COV_LOSSY: n_gross * 2 > T.
+ *   keep     for the covered cells among keep_first .. keep_first + keep_count - 1 (keep_count <= 64), their tasks in
+ *            order: the CSR columns exactly as the solver saw them (keep_ptr from 0), keep_noise[task][n_rx] (every
+ *            receiver, hearing or not), and the trial's pos, status, iters and e.
+ * THR_ERR_ARG, each with a sentence, before anything is launched: a null argument; n_rx outside 1 .. 64; a
+ * coordinate or sigma that is not finite, sigma < 0; lo, hi not finite or lo >= hi; nx, ny < 1 or nx * ny > 2^20;
+ * trials outside 1 .. THR_COV_MAX_TRIALS; cells * trials > 2^28; gross_m not positive and finite; range_m not finite;
+ * max_iter < 0; slab_groups < 0; keep_count outside 0 .. 64 or the keep range past the cells; x0 not finite; the
+ * area not inside thr_pos's box (10 km beyond the receivers' bounding box, the rule of thr_posg's margin).
+ * sigma = 0 for every receiver is allowed: with T = 1 the map is the convergence map of the fixed start.  256 trials,
+ * the 95 % point and "half" for LOSSY are conventions, not measurements. */
+#define THR_COV_MAX_TRIALS 4096
+#define THR_COV_MAX_KEEP 64
+#define THR_COV_SLAB_BYTES (512u << 20) /* the byte budget of one slab's columns, noise and solver outputs */
+typedef struct thr_coverage_opts {
+    double lo[2], hi[2];
+    int32_t nx, ny, trials, max_iter;
+    double range_m /* <= 0: every receiver hears every cell */, gross_m;
+    double x0[2];
+    uint32_t seed_lo, seed_hi;
+    int64_t slab_groups; /* 0: the default */
+    int32_t keep_first, keep_count;
+} thr_coverage_opts;
+typedef struct thr_coverage_counts {
+    size_t cells, nx, ny, n_rx, trials, covered, tasks, rows /* of all tasks */, slabs, slab_groups /* the cap in use */,
+        slab_bytes /* the largest slab */, keep_tasks, keep_rows;
+} thr_coverage_counts;
+typedef struct thr_coverage_result thr_coverage_result; /* the handle: thr_coverage is the call */
+#define THR_COV_UNCOVERED 1
+#define THR_COV_DEGENERATE 2
+#define THR_COV_LOSSY 4
+/* what thr_coverage_fetch copies, in terms of thr_coverage_counts */
+#define THR_COV_CX 0           /* float64[nx] */
+#define THR_COV_CY 1           /* float64[ny] */
+#define THR_COV_N_HEARD 2      /* int32[cells] */
+#define THR_COV_HEARD_MASK 3   /* uint64[cells] */
+#define THR_COV_FLAGS 4        /* int32[cells], THR_COV_UNCOVERED | _DEGENERATE | _LOSSY */
+#define THR_COV_PRED 5         /* float64[cells][5]: dop, pred_sxx, pred_sxy, pred_syy, pred_rms */
+#define THR_COV_COUNTS 6       /* int32[cells][6]: n_ok, n_at_bound, n_unconverged, n_nonfinite, n_good, n_gross */
+#define THR_COV_ITERS_SUM 7    /* int64[cells] */
+#define THR_COV_STATS 8        /* float64[cells][8]: bias_x, bias_y, sxx, sxy, syy, rms, q50, q95 */
+#define THR_COV_KEEP_PTR 9     /* int64[keep_tasks + 1] */
+#define THR_COV_KEEP_RX0 10    /* int32[keep_rows] */
+#define THR_COV_KEEP_RX1 11    /* int32[keep_rows] */
+#define THR_COV_KEEP_TDOA 12   /* float64[keep_rows] */
+#define THR_COV_KEEP_NOISE 13  /* float64[keep_tasks][n_rx], metres */
+#define THR_COV_KEEP_POS 14    /* float64[keep_tasks][2] */
+#define THR_COV_KEEP_STATUS 15 /* int32[keep_tasks], THR_POS_* */
+#define THR_COV_KEEP_ITERS 16  /* int32[keep_tasks] */
+#define THR_COV_KEEP_ERR 17    /* float64[keep_tasks] */
+#define THR_COV_N_OUTPUTS 18
+int thr_coverage(int device_id, int n_rx, const double* rx_coords, const double* sigma_rx, const thr_coverage_opts* opts,
+                 thr_coverage_result** result_out, thr_coverage_counts* counts_out);
+/* `which` is a THR_COV_* index; dst_bytes must be the size given there */
+int thr_coverage_fetch(thr_coverage_result* result, int which, void* dst, size_t dst_bytes);
+void thr_coverage_free(thr_coverage_result* result);
+/* Milliseconds of the calling thread's last thr_coverage: {copies in, cells (analytic columns and the scans),
+ * synthesis (noise and rows, summed over the slabs), solve (summed over the slabs), reduction (the trials' errors,
+ * the sums and the sort), copies out (summed over the fetches)} */
+int thr_debug_coverage_times(double* ms_out /* [6] */);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,7 @@ EXPORTS = [
     "thr_track", "thr_track_fetch", "thr_track_free", "thr_debug_track_times", "thr_debug_track_geometry",
     "thr_posg", "thr_posg_fetch", "thr_posg_free", "thr_debug_posg_times",
     "thr_tdoamatrix", "thr_tdmat_fetch", "thr_tdmat_free", "thr_debug_tdoamatrix_times", "thr_debug_tdoamatrix_geometry",
+    "thr_coverage", "thr_coverage_fetch", "thr_coverage_free", "thr_debug_coverage_times",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -76,6 +77,8 @@ POSQ_COUNTS = ("groups", "rows", "flagged", "tasks")
 TRACK_COUNTS = ("rows", "tracks", "used", "rejected", "rounds", "converged")
 POSG_COUNTS = ("groups", "rows", "tasks", "starts", "grid", "map_groups")
 TDMAT_COUNTS = ("tasks", "cells", "rows", "tdoas")
+COVERAGE_COUNTS = ("cells", "nx", "ny", "n_rx", "trials", "covered", "tasks", "rows", "slabs", "slab_groups", "slab_bytes",
+                   "keep_tasks", "keep_rows")
 
 
 class ThrBsyncCounts(C.Structure):        # thr_bsync_counts
@@ -111,6 +114,17 @@ class ThrPosgOpts(C.Structure):           # thr_posg_opts
 
 class ThrTdmatCounts(C.Structure):        # thr_tdmat_counts
     _fields_ = [(name, C.c_size_t) for name in TDMAT_COUNTS]
+
+
+class ThrCoverageCounts(C.Structure):     # thr_coverage_counts
+    _fields_ = [(name, C.c_size_t) for name in COVERAGE_COUNTS]
+
+
+class ThrCoverageOpts(C.Structure):       # thr_coverage_opts
+    _fields_ = [("lo", C.c_double * 2), ("hi", C.c_double * 2), ("nx", C.c_int32), ("ny", C.c_int32), ("trials", C.c_int32),
+                ("max_iter", C.c_int32), ("range_m", C.c_double), ("gross_m", C.c_double), ("x0", C.c_double * 2),
+                ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("slab_groups", C.c_int64), ("keep_first", C.c_int32),
+                ("keep_count", C.c_int32)]
 
 
 class ThrTrackCounts(C.Structure):        # thr_track_counts
@@ -446,7 +460,9 @@ def load_library():
                                    [vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(ThrTdmatCounts)])
     lib.thr_debug_tdoamatrix_times.argtypes = [C.POINTER(C.c_double)]
     lib.thr_debug_tdoamatrix_geometry.argtypes = [ip, ip, ip]
-    for stem in ("bsync", "tdstats", "reldist", "posq", "track", "posg", "tdmat"):
+    lib.thr_coverage.argtypes = [C.c_int, C.c_int, vp, vp, C.POINTER(ThrCoverageOpts), C.POINTER(vp), C.POINTER(ThrCoverageCounts)]
+    lib.thr_debug_coverage_times.argtypes = [C.POINTER(C.c_double)]
+    for stem in ("bsync", "tdstats", "reldist", "posq", "track", "posg", "tdmat", "coverage"):
         getattr(lib, "thr_%s_fetch" % stem).argtypes = [vp, C.c_int, vp, C.c_size_t]
         getattr(lib, "thr_%s_free" % stem).argtypes = [vp]
         getattr(lib, "thr_%s_free" % stem).restype = None
@@ -2384,4 +2400,76 @@ def posg_times():
     lib = load_library()
     ms = (C.c_double * 6)()
     _check(lib, lib.thr_debug_posg_times(ms))
+    return tuple(ms)
+
+
+COVERAGE_UNCOVERED, COVERAGE_DEGENERATE, COVERAGE_LOSSY = 1, 2, 4      # THR_COV_* flags
+COVERAGE_MAX_TRIALS = 4096      # THR_COV_MAX_TRIALS
+COVERAGE_MAX_KEEP = 64          # THR_COV_MAX_KEEP: cells whose trials one call can return
+COVERAGE_MAX_CELLS = 1 << 20
+COVERAGE_MAX_TASKS = 1 << 28    # cells x trials
+COVERAGE_SLAB_BYTES = 512 << 20  # THR_COV_SLAB_BYTES: the byte budget of one slab
+COVERAGE_PRED = ("dop", "pred_sxx", "pred_sxy", "pred_syy", "pred_rms")                      # the columns of "pred"
+COVERAGE_CELL_COUNTS = ("n_ok", "n_at_bound", "n_unconverged", "n_nonfinite", "n_good", "n_gross")   # of "counts"
+COVERAGE_STATS = ("bias_x", "bias_y", "sxx", "sxy", "syy", "rms", "q50", "q95")              # of "stats"
+# THR_COV_*: name -> (index, dtype, shape as a function of the counts)
+COVERAGE_OUTPUTS = {
+    "cx": (0, np.float64, lambda c: (c["nx"],)),
+    "cy": (1, np.float64, lambda c: (c["ny"],)),
+    "n_heard": (2, np.int32, lambda c: (c["cells"],)),
+    "heard_mask": (3, np.uint64, lambda c: (c["cells"],)),
+    "flags": (4, np.int32, lambda c: (c["cells"],)),
+    "pred": (5, np.float64, lambda c: (c["cells"], 5)),
+    "counts": (6, np.int32, lambda c: (c["cells"], 6)),
+    "iters_sum": (7, np.int64, lambda c: (c["cells"],)),
+    "stats": (8, np.float64, lambda c: (c["cells"], 8)),
+    "keep_ptr": (9, np.int64, lambda c: (c["keep_tasks"] + 1,)),
+    "keep_rx0": (10, np.int32, lambda c: (c["keep_rows"],)),
+    "keep_rx1": (11, np.int32, lambda c: (c["keep_rows"],)),
+    "keep_tdoa": (12, np.float64, lambda c: (c["keep_rows"],)),
+    "keep_noise": (13, np.float64, lambda c: (c["keep_tasks"], c["n_rx"])),
+    "keep_pos": (14, np.float64, lambda c: (c["keep_tasks"], 2)),
+    "keep_status": (15, np.int32, lambda c: (c["keep_tasks"],)),
+    "keep_iters": (16, np.int32, lambda c: (c["keep_tasks"],)),
+    "keep_err": (17, np.float64, lambda c: (c["keep_tasks"],)),
+}
+
+
+def coverage(rx_coords, sigma_rx, lo, hi, nx, ny, gross_m, trials=256, range_m=0.0, seed=0, x0=(0.1, 0.1), max_iter=100,
+             slab_groups=0, keep_first=0, keep_count=0, outputs=None, device_id=0):
+    """thr_coverage for receivers rx_coords[n_rx, 2] with arrival noise sigma_rx[n_rx] (metres) on the nx x ny raster
+    over lo .. hi -> (counts dict, {name: array}) with every output of COVERAGE_OUTPUTS (or those named in `outputs`)
+    fetched.  `seed` is a 64-bit number: its low and high words are the generator's key.  ValueError for what
+    thr_coverage refuses."""
+    lib = load_library()
+    xy = np.ascontiguousarray(rx_coords, dtype=np.float64)
+    sigma = np.ascontiguousarray(sigma_rx, dtype=np.float64)
+    if xy.ndim != 2 or xy.shape[1] != 2 or sigma.shape != (xy.shape[0],):
+        raise ValueError("coverage: rx_coords is [n_rx, 2] and sigma_rx [n_rx]")
+    corners = [np.ascontiguousarray(v, dtype=np.float64) for v in (lo, hi, x0)]
+    if any(v.shape != (2,) for v in corners):
+        raise ValueError("coverage: lo, hi and x0 hold two values each")
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("coverage: seed must lie in 0 .. 2^64 - 1")
+    pair = lambda v: (C.c_double * 2)(*v.tolist())     # noqa: E731
+    opts = ThrCoverageOpts(pair(corners[0]), pair(corners[1]), int(nx), int(ny), int(trials), int(max_iter), float(range_m),
+                           float(gross_m), pair(corners[2]), seed & 0xFFFFFFFF, seed >> 32, int(slab_groups), int(keep_first),
+                           int(keep_count))
+    handle, counts = C.c_void_p(), ThrCoverageCounts()
+    rc = lib.thr_coverage(int(device_id), xy.shape[0], xy.ctypes.data, sigma.ctypes.data, C.byref(opts), C.byref(handle),
+                          C.byref(counts))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    c = {name: int(getattr(counts, name)) for name in COVERAGE_COUNTS}
+    return c, _fetch_all(lib, "coverage", handle, c, COVERAGE_OUTPUTS, outputs)
+
+
+def coverage_times():
+    """Milliseconds (HIP events) of this thread's last coverage(): copies in, cells, synthesis, solve, reduction and sort,
+    copies out."""
+    lib = load_library()
+    ms = (C.c_double * 6)()
+    _check(lib, lib.thr_debug_coverage_times(ms))
     return tuple(ms)
