@@ -110,7 +110,10 @@ extern "C" {
  *    + thr_coverage / thr_coverage_fetch / thr_coverage_free / thr_debug_coverage_times -- a coverage map of a
  *      deployment without a recording: per cell of a raster the dop, the predicted covariance of thr_pos's
  *      estimator under per-receiver arrival noise, and the error statistics of T simulated transmissions, each
- *      solved by thr_pos's own iteration (the reference's "TODO: estimate confidence with SNR and DOP") */
+ *      solved by thr_pos's own iteration (the reference's "TODO: estimate confidence with SNR and DOP")
+ *    + thr_pos3 / thr_debug_pos3_times -- thr_pos's solve for receivers with three coordinates (pos-rx.cfg's
+ *      `id: x y z`, the z of the reference's POSITION_INFO_DTYPE): (x, y) with the transmitter's height known, or
+ *      (x, y, z) with dop split into its horizontal and vertical parts */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -1956,6 +1959,42 @@ void thr_coverage_free(thr_coverage_result* result);
  * synthesis (noise and rows, summed over the slabs), solve (summed over the slabs), reduction (the trials' errors,
  * the sums and the sort), copies out (summed over the fetches)} */
 int thr_debug_coverage_times(double* ms_out /* [6] */);
+
+/* ---- Positions from receivers with three coordinates: thr_pos's 2-D solve for antennas at different heights.
+ * Synchronous, no handle (the pattern of thr_pos).  The columns are thr_pos's (CSR groups, DENSE receiver indices)
+ * and the table is rx_xyz[n_rx][3], finite, n_rx <= 64.  One 8-lane team per group runs thr_pos's own iteration
+ * (csrc/pos3_lm.hpp restates csrc/pos_lm.hpp's rules for both modes); a row's residual is
+ * tdoa c - (|rx0 - p| - |rx1 - p|), c = 2.997e8, |v| = sqrt((vx * vx + vy * vy) + vz * vz).  All arithmetic is
+ * float64, no product and sum is contracted.
+ *  mode THR_POS3_KNOWN_HEIGHT: the unknowns are (x, y); group_h[n_groups] (finite) gives each transmission's height,
+ *     so vz = rz - group_h[g] is a constant of the solve.  Starts from x0[0], x0[1] (x0[2] and z_range are not
+ *     read) inside thr_pos's box on x and y.  Fewer than 3 distinct receivers: THR_POS_UNDERDETERMINED.
+ *     dop_out = hdop_out = sqrt(trace(inv(G'G))) of the 2 x 2 (the horizontal dilution GIVEN the height),
+ *     vdop_out = 0, pos_out[g] = (x, y, group_h[g]).  Where every receiver's z equals group_h[g] the position, dop,
+ *     snr, status and iters are the bits thr_pos returns on the table without its z column.
+ *  mode THR_POS3_FREE_Z: the unknowns are (x, y, z), from x0[3] inside the box min(rx) - 10 km .. max(rx) + 10 km
+ *     per axis, whose z axis is replaced by z_range[2] = {z_lo, z_hi} (finite, z_lo < z_hi) when that is not NULL;
+ *     x0[2] must lie inside it.  group_h is not read.  Fewer than 4 distinct receivers: THR_POS_UNDERDETERMINED.
+ *     With inv = inv(G'G) (3 x 3, by cofactors): dop_out = sqrt(trace(inv)) (the reference's dop()), hdop_out =
+ *     sqrt(inv00 + inv11), vdop_out = sqrt(inv22); all three -1 where the determinant is 0 or not finite.
+ *     The cost is even in z about the receivers' plane when all of them share one height: a start ON that plane
+ *     has a z gradient of exactly zero and never leaves it (thrifty_amd/pos_3d.py refuses it).
+ * Per group, in group order: pos_out[g * 3 ..], rms_out[g] = sqrt(sum r^2 / rows) in metres at the position (NaN for
+ * a group without rows), snr_out, status_out (THR_POS_*) and iters_out as thr_pos writes them.  max_iter == 0
+ * evaluates at the start.  Nothing is compacted.  THR_ERR_ARG before anything is launched: an index out of range, a
+ * decreasing group_ptr, a group over 2^24 rows, more than 2^28 groups or 2^30 rows, n_rx outside 1 .. 64, a
+ * non-finite coordinate, height, x0 or z_range, z_lo >= z_hi, x0[2] outside the z range, an unknown mode, a null
+ * argument, max_iter < 0, a bad device_id.  n_groups == 0: THR_OK once the arguments and device_id have been checked. */
+#define THR_POS3_KNOWN_HEIGHT 0
+#define THR_POS3_FREE_Z 1
+int thr_pos3(int device_id, size_t n_groups, const int64_t* group_ptr, const int32_t* row_rx0, const int32_t* row_rx1,
+             const double* row_tdoa, const double* row_snr, int n_rx, const double* rx_xyz, int mode,
+             const double* group_h /* [n_groups], or NULL with z free */, const double* x0 /* [3] */,
+             const double* z_range /* [2], or NULL */, int max_iter, double* pos_out /* [n_groups][3] */,
+             double* dop_out, double* hdop_out, double* vdop_out, double* rms_out, double* snr_out, int32_t* status_out,
+             int32_t* iters_out);
+/* Milliseconds of the calling thread's last thr_pos3: {copies in, the kernel, copies out} (HIP events). */
+int thr_debug_pos3_times(double* ms_out /* [3] */);
 
 #ifdef __cplusplus
 }

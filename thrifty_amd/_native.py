@@ -60,6 +60,7 @@ EXPORTS = [
     "thr_posg", "thr_posg_fetch", "thr_posg_free", "thr_debug_posg_times",
     "thr_tdoamatrix", "thr_tdmat_fetch", "thr_tdmat_free", "thr_debug_tdoamatrix_times", "thr_debug_tdoamatrix_geometry",
     "thr_coverage", "thr_coverage_fetch", "thr_coverage_free", "thr_debug_coverage_times",
+    "thr_pos3", "thr_debug_pos3_times",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -462,6 +463,8 @@ def load_library():
     lib.thr_debug_tdoamatrix_geometry.argtypes = [ip, ip, ip]
     lib.thr_coverage.argtypes = [C.c_int, C.c_int, vp, vp, C.POINTER(ThrCoverageOpts), C.POINTER(vp), C.POINTER(ThrCoverageCounts)]
     lib.thr_debug_coverage_times.argtypes = [C.POINTER(C.c_double)]
+    lib.thr_pos3.argtypes = [C.c_int, C.c_size_t] + [vp] * 5 + [C.c_int, vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 8
+    lib.thr_debug_pos3_times.argtypes = [C.POINTER(C.c_double)]
     for stem in ("bsync", "tdstats", "reldist", "posq", "track", "posg", "tdmat", "coverage"):
         getattr(lib, "thr_%s_fetch" % stem).argtypes = [vp, C.c_int, vp, C.c_size_t]
         getattr(lib, "thr_%s_free" % stem).argtypes = [vp]
@@ -2472,4 +2475,54 @@ def coverage_times():
     lib = load_library()
     ms = (C.c_double * 6)()
     _check(lib, lib.thr_debug_coverage_times(ms))
+    return tuple(ms)
+
+
+POS3_GROUPS_PER_WORKGROUP = 32  # kTeams of csrc/pos3.hip: one 8-lane team per group
+POS3_REGISTER_ROWS = 4          # kRegRows: rows per lane held in registers; groups over 32 rows re-read theirs
+POS3_KNOWN_HEIGHT, POS3_FREE_Z = 0, 1       # THR_POS3_*
+POS3_OUTPUTS = ("pos", "dop", "hdop", "vdop", "rms", "snr", "status", "iters")
+
+
+def pos3(group_ptr, row_rx0, row_rx1, row_tdoa, row_snr, rx_xyz, mode, group_h=None, x0=(0.1, 0.1, 0.0), z_range=None,
+         max_iter=100, device_id=0):
+    """thr_pos3 on TDOA rows in CSR form (thr_pos's columns: dense receiver indices into rx_xyz[n_rx, 3]) -> dict of
+    pos float64[g, 3], dop / hdop / vdop / rms / snr float64[g], status / iters int32[g], every group in order.
+    mode POS3_KNOWN_HEIGHT reads group_h[g]; POS3_FREE_Z reads x0[2] and z_range.  ValueError for what thr_pos3 refuses."""
+    lib = load_library()
+    ptr = np.ascontiguousarray(group_ptr, dtype=np.int64)
+    rx0, rx1 = np.ascontiguousarray(row_rx0, dtype=np.int32), np.ascontiguousarray(row_rx1, dtype=np.int32)
+    tdoa, snr = np.ascontiguousarray(row_tdoa, dtype=np.float64), np.ascontiguousarray(row_snr, dtype=np.float64)
+    xyz = np.ascontiguousarray(rx_xyz, dtype=np.float64)
+    if (ptr.ndim != 1 or len(ptr) < 1 or xyz.ndim != 2 or xyz.shape[1] != 3 or
+            not (len(rx0) == len(rx1) == len(tdoa) == len(snr) == int(ptr[-1]))):
+        raise ValueError("pos3: group_ptr, the row columns or rx_xyz[n_rx, 3] have the wrong shape")
+    n = len(ptr) - 1
+    start = np.ascontiguousarray(x0, dtype=np.float64)
+    if start.shape != (3,):
+        raise ValueError("pos3: x0 holds three values")
+    heights = None if group_h is None else np.ascontiguousarray(group_h, dtype=np.float64)
+    if heights is not None and heights.shape != (n,):
+        raise ValueError("pos3: group_h holds one height per group")
+    box = None if z_range is None else np.ascontiguousarray(z_range, dtype=np.float64)
+    if box is not None and box.shape != (2,):
+        raise ValueError("pos3: z_range holds two values")
+    out = {"pos": np.zeros((n, 3), dtype=np.float64)}
+    out.update({key: np.zeros(n, dtype=np.float64) for key in ("dop", "hdop", "vdop", "rms", "snr")})
+    out.update({key: np.zeros(n, dtype=np.int32) for key in ("status", "iters")})
+    rc = lib.thr_pos3(int(device_id), n, ptr.ctypes.data, rx0.ctypes.data, rx1.ctypes.data, tdoa.ctypes.data,
+                      snr.ctypes.data, xyz.shape[0], xyz.ctypes.data, int(mode),
+                      None if heights is None else heights.ctypes.data, start.ctypes.data,
+                      None if box is None else box.ctypes.data, int(max_iter), *[out[key].ctypes.data for key in POS3_OUTPUTS])
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    return out
+
+
+def pos3_times():
+    """{copies in, the kernel, copies out} of this thread's last pos3(), milliseconds (HIP events)."""
+    lib = load_library()
+    ms = (C.c_double * 3)()
+    _check(lib, lib.thr_debug_pos3_times(ms))
     return tuple(ms)
