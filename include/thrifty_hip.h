@@ -113,7 +113,11 @@ extern "C" {
  *      solved by thr_pos's own iteration (the reference's "TODO: estimate confidence with SNR and DOP")
  *    + thr_pos3 / thr_debug_pos3_times -- thr_pos's solve for receivers with three coordinates (pos-rx.cfg's
  *      `id: x y z`, the z of the reference's POSITION_INFO_DTYPE): (x, y) with the transmitter's height known, or
- *      (x, y, z) with dop split into its horizontal and vertical parts */
+ *      (x, y, z) with dop split into its horizontal and vertical parts
+ *    + thr_posg3 / thr_posg3_fetch / thr_posg3_free / thr_debug_posg3_times -- thr_posg's idea for thr_pos3's two
+ *      modes: the cost on a grid x grid x grid_z volume (one plane with the height known), its lowest local minima as
+ *      further starts of thr_pos3's own iteration, the best minimum, the runner-up, and a flag where the two differ
+ *      in height only (the mirror about nearly coplanar antennas) */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -1995,6 +1999,102 @@ int thr_pos3(int device_id, size_t n_groups, const int64_t* group_ptr, const int
              int32_t* iters_out);
 /* Milliseconds of the calling thread's last thr_pos3: {copies in, the kernel, copies out} (HIP events). */
 int thr_debug_pos3_times(double* ms_out /* [3] */);
+
+/* ---- Global solve for receivers with three coordinates: thr_posg's grid starts, best minimum and ambiguity flag
+ * for thr_pos3's two modes.  Host columns in, synchronous, the results stay on the device behind a handle until
+ * thr_posg3_fetch (the pattern of thr_posg).  The columns are thr_pos3's (CSR groups, dense receiver indices,
+ * rx_xyz[n_rx][3], n_rx <= 64, mode, group_h).  All arithmetic is float64, no product and sum is contracted.
+ * G = opts->grid (16 or 32), Gz = opts->grid_z (1 with the height known, 2 .. 32 with z free), K = opts->starts (1 .. 8).
+ *   area     x and y exactly as thr_posg: lo = min over the receivers - margin_m, hi = max + margin_m per axis,
+ *            0 < margin_m <= 10 km.  Free z: z_grid[2] = {zg_lo, zg_hi}, both finite, zg_lo < zg_hi, inside the z box
+ *            thr_pos3 would use (z_range if given, else min rz - 10 km .. max rz + 10 km).
+ *            Centres cx[i] = lo0 + (i + 0.5) * ((hi0 - lo0) / G), cy[j] alike; free z: cz[k] = zg_lo + (k + 0.5) *
+ *            ((zg_hi - zg_lo) / Gz); known height: cz = group_h[g], one plane.  Cell c = (k * G + j) * G + i.
+ *   surface  F[c] = sum over the group's rows, in row order, one accumulator from 0.0, of r * r with
+ *            r = tc - (|rx0 - p_c| - |rx1 - p_c|), tc = tdoa * 2.997e8, v = rx - p_c,
+ *            |v| = sqrt((vx * vx + vy * vy) + vz * vz), the additions in this order (csrc/pos3_lm.hpp's).  With every
+ *            antenna at group_h[g], vz is 0 and F has thr_posg's bits.
+ *   minimum  thr_posg's rule over the up to 26 neighbours n of cell c (8 when Gz = 1): F[c] < F[n], or F[c] == F[n]
+ *            and n > c; for a neighbour outside the volume, the planes -1 and Gz included: F[c] < +inf.  A NaN makes
+ *            every comparison false.
+ *   starts   the K local minima with the smallest (F, c), in that order; unused slots hold cell -1 and F = NaN.
+ *   tasks    K + 1 per group.  Task 0 is thr_pos3's own solve from opts->x0[3].  Task k = 1 .. K starts from the centre
+ *            of start cell k - 1 (known height: its (cx, cy)).  Every task is thr::pos3lm::solve_team of
+ *            csrc/pos3_lm.hpp with thr_pos3's box and opts->max_iter: it returns the bits thr_pos3 returns for that
+ *            group with that start -- pos, dop, hdop, vdop, rms = sqrt(F / rows), status and iters.  A group whose
+ *            task 0 ends THR_POS_UNDERDETERMINED or THR_POS_NONFINITE gets no grid and no tasks 1 .. K (n_local 0,
+ *            start cells -1, its map NaN).  A task that does not exist has status THR_POSG3_NO_TASK, iters 0 and NaN
+ *            elsewhere.
+ *   choice   thr_posg's pairwise rule word for word: ELIGIBLE means THR_POS_OK; task u comes BEFORE task t when u is
+ *            eligible and (rms_u, u) < (rms_t, t); the BEST is the eligible task that none comes before; an eligible
+ *            task is a DUPLICATE when some u before it lies within merge_m of it, the distance being
+ *            sqrt((dx * dx + dy * dy) + dz * dz) with z free and sqrt(dx * dx + dy * dy) with the height known;
+ *            n_minima = the eligible tasks that are no duplicates; the SECOND is the first of those other than the
+ *            best; pos2, rms2 are NaN without one.
+ *   flags    THR_POSG3_MOVED, _AMBIGUOUS, _NO_MINIMUM as thr_posg defines them (with the distance above).
+ *            THR_POSG3_MIRROR, free z only: AMBIGUOUS, and the second lies within merge_m of the best HORIZONTALLY
+ *            (sqrt(dx * dx + dy * dy) <= merge_m): x and y can be trusted, the height cannot.  A solve that ends
+ *            THR_POS_AT_BOUND is not eligible: a group without an eligible task is NO_MINIMUM and carries task 0's
+ *            outputs, thr_pos3's answer.
+ *   map      for the groups map_first .. map_first + map_count - 1 (at most 256): F as [Gz][G][G] and the local minima.
+ * THR_ERR_ARG before anything is launched: everything thr_pos3 refuses; grid, grid_z or starts out of range;
+ * grid_z != 1 with the height known; a missing, non-finite or out-of-box z_grid with z free; merge_m, ratio, floor_m
+ * or margin_m as thr_posg refuses them; the map range; groups * (starts + 1) > 2^28.  grid = 32, grid_z = 8, starts = 4,
+ * merge_m = 1, ratio = 2, the margin and the default z_grid are conventions of the Python interface, not measurements. */
+typedef struct thr_posg3_opts {
+    int32_t max_iter, grid, grid_z, starts;
+    double x0[3];
+    double margin_m, merge_m, ratio, floor_m;
+    int64_t map_first;
+    int32_t map_count;
+} thr_posg3_opts;
+typedef struct thr_posg3_counts {
+    size_t groups, rows, tasks /* per group: starts + 1 */, starts, grid, grid_z, map_groups;
+} thr_posg3_counts;
+typedef struct thr_posg3_result thr_posg3_result; /* the handle: thr_posg3 is the call */
+#define THR_POSG3_MOVED 1
+#define THR_POSG3_AMBIGUOUS 2
+#define THR_POSG3_NO_MINIMUM 4
+#define THR_POSG3_MIRROR 8
+#define THR_POSG3_NO_TASK (-1) /* the status of a task that does not exist */
+/* what thr_posg3_fetch copies, in terms of thr_posg3_counts: THR_POSG_*'s indices with positions [3], then the rest */
+#define THR_POSG3_POS 0          /* float64[groups][3]: the chosen task's position */
+#define THR_POSG3_DOP 1          /* float64[groups] */
+#define THR_POSG3_STATUS 2       /* int32[groups], THR_POS_* */
+#define THR_POSG3_TASK 3         /* int32[groups]: the chosen task, 0 .. starts */
+#define THR_POSG3_RMS 4          /* float64[groups] */
+#define THR_POSG3_POS2 5         /* float64[groups][3]: the second, or NaN */
+#define THR_POSG3_RMS2 6         /* float64[groups] */
+#define THR_POSG3_N_MINIMA 7     /* int32[groups] */
+#define THR_POSG3_FLAGS 8        /* int32[groups], THR_POSG3_MOVED | _AMBIGUOUS | _NO_MINIMUM | _MIRROR */
+#define THR_POSG3_SNR 9          /* float64[groups]: the mean over all rows, as thr_pos3 */
+#define THR_POSG3_N_LOCAL 10     /* int32[groups]: local-minimum cells of the volume */
+#define THR_POSG3_START_CELL 11  /* int32[groups][starts] */
+#define THR_POSG3_START_F 12     /* float64[groups][starts] */
+#define THR_POSG3_TASK_POS 13    /* float64[groups][tasks][3] */
+#define THR_POSG3_TASK_DOP 14    /* float64[groups][tasks] */
+#define THR_POSG3_TASK_RMS 15    /* float64[groups][tasks] */
+#define THR_POSG3_TASK_STATUS 16 /* int32[groups][tasks], THR_POS_* or THR_POSG3_NO_TASK */
+#define THR_POSG3_TASK_ITERS 17  /* int32[groups][tasks] */
+#define THR_POSG3_MAP 18         /* float64[map_groups][grid_z][grid][grid]: F, plane k, row j, column i */
+#define THR_POSG3_MAP_MIN 19     /* uint8[map_groups][grid_z][grid][grid]: 1 = local minimum */
+#define THR_POSG3_HDOP 20        /* float64[groups]: the chosen task's, as thr_pos3 */
+#define THR_POSG3_VDOP 21        /* float64[groups] */
+#define THR_POSG3_TASK_HDOP 22   /* float64[groups][tasks] */
+#define THR_POSG3_TASK_VDOP 23   /* float64[groups][tasks] */
+#define THR_POSG3_N_OUTPUTS 24
+int thr_posg3(int device_id, size_t n_groups, const int64_t* group_ptr, const int32_t* row_rx0, const int32_t* row_rx1,
+              const double* row_tdoa, const double* row_snr, int n_rx, const double* rx_xyz, int mode /* THR_POS3_* */,
+              const double* group_h /* [n_groups], or NULL with z free */, const double* z_range /* [2], or NULL */,
+              const double* z_grid /* [2] with z free; not read with the height known */, const thr_posg3_opts* opts,
+              thr_posg3_result** result_out, thr_posg3_counts* counts_out);
+/* `which` is a THR_POSG3_* index; dst_bytes must be the size given there */
+int thr_posg3_fetch(thr_posg3_result* result, int which, void* dst, size_t dst_bytes);
+void thr_posg3_free(thr_posg3_result* result);
+/* Milliseconds of the calling thread's last thr_posg3: {copies in, task 0 (the fixed start), surface, minima and
+ * starts (one kernel: three planes of the volume at a time in LDS), refinement (tasks 1 .. K), choice, copies out
+ * (summed over the fetches)} */
+int thr_debug_posg3_times(double* ms_out /* [6] */);
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,7 @@ EXPORTS = [
     "thr_tdoamatrix", "thr_tdmat_fetch", "thr_tdmat_free", "thr_debug_tdoamatrix_times", "thr_debug_tdoamatrix_geometry",
     "thr_coverage", "thr_coverage_fetch", "thr_coverage_free", "thr_debug_coverage_times",
     "thr_pos3", "thr_debug_pos3_times",
+    "thr_posg3", "thr_posg3_fetch", "thr_posg3_free", "thr_debug_posg3_times",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -77,6 +78,7 @@ RELDIST_COUNTS = ("rows", "cells", "speeds", "speed_points", "dop_points")
 POSQ_COUNTS = ("groups", "rows", "flagged", "tasks")
 TRACK_COUNTS = ("rows", "tracks", "used", "rejected", "rounds", "converged")
 POSG_COUNTS = ("groups", "rows", "tasks", "starts", "grid", "map_groups")
+POSG3_COUNTS = ("groups", "rows", "tasks", "starts", "grid", "grid_z", "map_groups")
 TDMAT_COUNTS = ("tasks", "cells", "rows", "tdoas")
 COVERAGE_COUNTS = ("cells", "nx", "ny", "n_rx", "trials", "covered", "tasks", "rows", "slabs", "slab_groups", "slab_bytes",
                    "keep_tasks", "keep_rows")
@@ -111,6 +113,16 @@ class ThrPosgOpts(C.Structure):           # thr_posg_opts
     _fields_ = [("max_iter", C.c_int32), ("grid", C.c_int32), ("starts", C.c_int32), ("x0", C.c_double * 2),
                 ("margin_m", C.c_double), ("merge_m", C.c_double), ("ratio", C.c_double), ("floor_m", C.c_double),
                 ("map_first", C.c_int64), ("map_count", C.c_int32)]
+
+
+class ThrPosg3Counts(C.Structure):        # thr_posg3_counts
+    _fields_ = [(name, C.c_size_t) for name in POSG3_COUNTS]
+
+
+class ThrPosg3Opts(C.Structure):          # thr_posg3_opts
+    _fields_ = [("max_iter", C.c_int32), ("grid", C.c_int32), ("grid_z", C.c_int32), ("starts", C.c_int32),
+                ("x0", C.c_double * 3), ("margin_m", C.c_double), ("merge_m", C.c_double), ("ratio", C.c_double),
+                ("floor_m", C.c_double), ("map_first", C.c_int64), ("map_count", C.c_int32)]
 
 
 class ThrTdmatCounts(C.Structure):        # thr_tdmat_counts
@@ -465,6 +477,12 @@ def load_library():
     lib.thr_debug_coverage_times.argtypes = [C.POINTER(C.c_double)]
     lib.thr_pos3.argtypes = [C.c_int, C.c_size_t] + [vp] * 5 + [C.c_int, vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 8
     lib.thr_debug_pos3_times.argtypes = [C.POINTER(C.c_double)]
+    lib.thr_posg3.argtypes = ([C.c_int, C.c_size_t] + [vp] * 5 + [C.c_int, vp, C.c_int, vp, vp, vp, C.POINTER(ThrPosg3Opts),
+                              C.POINTER(vp), C.POINTER(ThrPosg3Counts)])
+    lib.thr_debug_posg3_times.argtypes = [C.POINTER(C.c_double)]
+    lib.thr_posg3_fetch.argtypes = [vp, C.c_int, vp, C.c_size_t]
+    lib.thr_posg3_free.argtypes = [vp]
+    lib.thr_posg3_free.restype = None
     for stem in ("bsync", "tdstats", "reldist", "posq", "track", "posg", "tdmat", "coverage"):
         getattr(lib, "thr_%s_fetch" % stem).argtypes = [vp, C.c_int, vp, C.c_size_t]
         getattr(lib, "thr_%s_free" % stem).argtypes = [vp]
@@ -2525,4 +2543,90 @@ def pos3_times():
     lib = load_library()
     ms = (C.c_double * 3)()
     _check(lib, lib.thr_debug_pos3_times(ms))
+    return tuple(ms)
+
+
+POSG3_MOVED, POSG3_AMBIGUOUS, POSG3_NO_MINIMUM, POSG3_MIRROR = 1, 2, 4, 8      # THR_POSG3_* flags
+POSG3_NO_TASK = -1          # THR_POSG3_NO_TASK: the status of a task that does not exist
+POSG3_ROW_CHUNK = 32        # kRowChunk of csrc/posg3.hip: a longer group stages its chunks again for every plane
+POSG3_DIST_RECEIVERS = 32   # kDistRx: up to this many receivers the volume kernel takes a cell's distances once per receiver
+POSG3_GRIDS = (16, 32)
+POSG3_MAX_GRID_Z = 32       # planes with z free: 2 .. 32; one plane with the height known
+POSG3_MAX_STARTS = 8
+POSG3_MAX_MAP = 256         # groups whose volume one call can return
+POSG3_MAX_MARGIN = 10e3     # thr_pos3's box reaches this far beyond the receivers
+_volume = lambda c: (c["map_groups"], c["grid_z"], c["grid"], c["grid"])      # noqa: E731
+# THR_POSG3_*: name -> (index, dtype, shape as a function of the counts)
+POSG3_OUTPUTS = {
+    "pos": (0, np.float64, lambda c: (c["groups"], 3)),
+    "dop": (1, np.float64, lambda c: (c["groups"],)),
+    "status": (2, np.int32, lambda c: (c["groups"],)),
+    "task": (3, np.int32, lambda c: (c["groups"],)),
+    "rms": (4, np.float64, lambda c: (c["groups"],)),
+    "pos2": (5, np.float64, lambda c: (c["groups"], 3)),
+    "rms2": (6, np.float64, lambda c: (c["groups"],)),
+    "n_minima": (7, np.int32, lambda c: (c["groups"],)),
+    "flags": (8, np.int32, lambda c: (c["groups"],)),
+    "snr": (9, np.float64, lambda c: (c["groups"],)),
+    "n_local": (10, np.int32, lambda c: (c["groups"],)),
+    "start_cell": (11, np.int32, lambda c: (c["groups"], c["starts"])),
+    "start_f": (12, np.float64, lambda c: (c["groups"], c["starts"])),
+    "task_pos": (13, np.float64, lambda c: (c["groups"], c["tasks"], 3)),
+    "task_dop": (14, np.float64, lambda c: (c["groups"], c["tasks"])),
+    "task_rms": (15, np.float64, lambda c: (c["groups"], c["tasks"])),
+    "task_status": (16, np.int32, lambda c: (c["groups"], c["tasks"])),
+    "task_iters": (17, np.int32, lambda c: (c["groups"], c["tasks"])),
+    "map": (18, np.float64, _volume),
+    "map_min": (19, np.uint8, _volume),
+    "hdop": (20, np.float64, lambda c: (c["groups"],)),
+    "vdop": (21, np.float64, lambda c: (c["groups"],)),
+    "task_hdop": (22, np.float64, lambda c: (c["groups"], c["tasks"])),
+    "task_vdop": (23, np.float64, lambda c: (c["groups"], c["tasks"])),
+}
+
+
+def posg3(group_ptr, row_rx0, row_rx1, row_tdoa, row_snr, rx_xyz, mode, margin_m, group_h=None, x0=(0.1, 0.1, 0.0), z_range=None,
+          z_grid=None, grid=32, grid_z=8, starts=4, merge_m=1.0, ratio=2.0, floor_m=0.0, map_first=0, map_count=0, max_iter=100,
+          outputs=None, device_id=0):
+    """thr_posg3 on TDOA rows in CSR form (thr_pos3's columns: dense receiver indices into rx_xyz[n_rx, 3]) ->
+    (counts dict, {name: array}) with every output of POSG3_OUTPUTS (or those named in `outputs`) fetched.  mode
+    POS3_KNOWN_HEIGHT reads group_h[g] (grid_z must be 1); POS3_FREE_Z reads x0[2], z_range and z_grid.  ValueError for
+    what thr_posg3 refuses."""
+    lib = load_library()
+    ptr = np.ascontiguousarray(group_ptr, dtype=np.int64)
+    rx0, rx1 = np.ascontiguousarray(row_rx0, dtype=np.int32), np.ascontiguousarray(row_rx1, dtype=np.int32)
+    tdoa, snr = np.ascontiguousarray(row_tdoa, dtype=np.float64), np.ascontiguousarray(row_snr, dtype=np.float64)
+    xyz = np.ascontiguousarray(rx_xyz, dtype=np.float64)
+    if (ptr.ndim != 1 or len(ptr) < 1 or xyz.ndim != 2 or xyz.shape[1] != 3 or
+            not (len(rx0) == len(rx1) == len(tdoa) == len(snr) == int(ptr[-1]))):
+        raise ValueError("posg3: group_ptr, the row columns or rx_xyz[n_rx, 3] have the wrong shape")
+    n = len(ptr) - 1
+    start = np.ascontiguousarray(x0, dtype=np.float64)
+    if start.shape != (3,):
+        raise ValueError("posg3: x0 holds three values")
+    heights = None if group_h is None else np.ascontiguousarray(group_h, dtype=np.float64)
+    if heights is not None and heights.shape != (n,):
+        raise ValueError("posg3: group_h holds one height per group")
+    pairs = [None if v is None else np.ascontiguousarray(v, dtype=np.float64) for v in (z_range, z_grid)]
+    if any(v is not None and v.shape != (2,) for v in pairs):
+        raise ValueError("posg3: z_range and z_grid hold two values each")
+    opts = ThrPosg3Opts(int(max_iter), int(grid), int(grid_z), int(starts), (C.c_double * 3)(*start.tolist()), float(margin_m),
+                        float(merge_m), float(ratio), float(floor_m), int(map_first), int(map_count))
+    handle, counts = C.c_void_p(), ThrPosg3Counts()
+    rc = lib.thr_posg3(int(device_id), n, ptr.ctypes.data, rx0.ctypes.data, rx1.ctypes.data, tdoa.ctypes.data, snr.ctypes.data,
+                       xyz.shape[0], xyz.ctypes.data, int(mode), _ptr(heights), _ptr(pairs[0]), _ptr(pairs[1]), C.byref(opts),
+                       C.byref(handle), C.byref(counts))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    c = {name: int(getattr(counts, name)) for name in POSG3_COUNTS}
+    return c, _fetch_all(lib, "posg3", handle, c, POSG3_OUTPUTS, outputs)
+
+
+def posg3_times():
+    """Milliseconds (HIP events) of this thread's last posg3(): copies in, task 0 (the fixed start), surface, minima and
+    starts, refinement (tasks 1 .. K), choice, copies out."""
+    lib = load_library()
+    ms = (C.c_double * 6)()
+    _check(lib, lib.thr_debug_posg3_times(ms))
     return tuple(ms)
