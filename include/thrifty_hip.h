@@ -117,7 +117,9 @@ extern "C" {
  *    + thr_posg3 / thr_posg3_fetch / thr_posg3_free / thr_debug_posg3_times -- thr_posg's idea for thr_pos3's two
  *      modes: the cost on a grid x grid x grid_z volume (one plane with the height known), its lowest local minima as
  *      further starts of thr_pos3's own iteration, the best minimum, the runner-up, and a flag where the two differ
- *      in height only (the mirror about nearly coplanar antennas) */
+ *      in height only (the mirror about nearly coplanar antennas)
+ *    + thr_posq3 / thr_posq3_fetch / thr_posq3_free / thr_debug_posq3_times -- thr_posq's weights, residuals,
+ *      inverse normal matrix and receiver exclusion for thr_pos3's two modes */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -2095,6 +2097,77 @@ void thr_posg3_free(thr_posg3_result* result);
  * starts (one kernel: three planes of the volume at a time in LDS), refinement (tasks 1 .. K), choice, copies out
  * (summed over the fetches)} */
 int thr_debug_posg3_times(double* ms_out /* [6] */);
+
+/* ---- Position quality for receivers with three coordinates: thr_posq's row weights, residuals, inv(A) and the
+ * exclusion of one receiver, for thr_pos3's two modes.  Host columns in, synchronous, the results stay on the device
+ * behind a handle until thr_posq3_fetch (the pattern of thr_posq).  The columns, rx_xyz[n_rx][3], mode and group_h
+ * are thr_pos3's; the box, the start (opts->x0, opts->z_range when opts->has_z_range != 0) and every refusal are
+ * thr_pos3's too.  row_weight: NULL, or one finite weight >= 0 per row.
+ *   A TASK is a group solved over a subset of its rows by thr_pos3's own iteration (csrc/pos3_lm.hpp).  Row i of a
+ *   task counts w_i * (m_used / sum of the task's w): the sum in team order, then ONE division, so a column of ones is
+ *   the unweighted solve to the bit; a zero sum ends as THR_POS_NONFINITE.  F = sum w r^2, A = sum w g g';
+ *   rms = sqrt(F / m_used) with the last accepted F (thr_pos3's rms_out for an unweighted full solve).
+ *   q = inv(A) as {q00, q01, q11, q02, q12, q22}.  Free z: by the cofactors thr_pos3 takes its dops from, all six NaN
+ *   (and the dops -1) where the determinant is 0 or not finite.  Known height: the first three are thr_posq's 2 x 2
+ *   inverse {a11 / det, -a01 / det, a00 / det} and the last three 0.0.  dop, hdop, vdop are thr_pos3's.
+ *   Stages 1 .. 5 are thr_posq's, word for word: the full solve; FLAGGED when gate_m > 0, the full status is neither
+ *   UNDERDETERMINED nor NONFINITE, the group names at least min_rx distinct receivers and rms_full > gate_m; one
+ *   candidate per named receiver (ascending dense index): the group without the rows that name it, from the start
+ *   again; a candidate is eligible when THR_POS_OK and it names at least min_rx - 1 receivers, the smallest rms wins
+ *   (the lowest receiver on ties) and is excluded iff rms_best <= ratio * rms_full; every row's residual
+ *   tdoa c - (|rx0 - p| - |rx1 - p|), |v| = sqrt((vx * vx + vy * vy) + vz * vz), at the chosen position.
+ *   With every antenna at group_h[g], every output thr_posq has carries thr_posq's bits on the flat table.
+ * min_rx: N receivers give N - 1 independent TDOAs, and a candidate (N - 1 receivers) must keep one redundant
+ * arrival, N - 2 > unknowns: 5 .. 64 with the height known, 6 .. 64 with z free.  ratio in (0, 1], gate_m >= 0 and
+ * finite, max_iter >= 0: THR_ERR_ARG otherwise. */
+typedef struct thr_posq3_opts {
+    int32_t max_iter, min_rx, has_z_range;
+    double x0[3];
+    double z_range[2]; /* read when has_z_range != 0 and z is free */
+    double gate_m, ratio;
+} thr_posq3_opts;
+typedef struct thr_posq3_counts {
+    size_t groups, rows, flagged, tasks;
+} thr_posq3_counts;
+typedef struct thr_posq3_result thr_posq3_result; /* the handle: thr_posq3 is the call */
+#define THR_POSQ3_INCONSISTENT 1 /* flagged */
+#define THR_POSQ3_EXCLUDED 2     /* a receiver was excluded: pos, dops, status, iters, q, rms[1] are the candidate's */
+#define THR_POSQ3_NO_CANDIDATE 4 /* flagged, but no candidate was eligible or the ratio was not met */
+/* what thr_posq3_fetch copies, in terms of thr_posq3_counts: THR_POSQ_*'s indices with positions [3] and q [6], then
+ * the rest */
+#define THR_POSQ3_POS 0          /* float64[groups][3]: the chosen position (known height: z = group_h[g]) */
+#define THR_POSQ3_DOP 1          /* float64[groups] */
+#define THR_POSQ3_STATUS 2       /* int32[groups], THR_POS_* */
+#define THR_POSQ3_ITERS 3        /* int32[groups] */
+#define THR_POSQ3_Q 4            /* float64[groups][6]: q00, q01, q11, q02, q12, q22 */
+#define THR_POSQ3_RMS 5          /* float64[groups][2]: rms_full, rms of the chosen task */
+#define THR_POSQ3_COUNTS 6       /* int32[groups][3]: receivers and rows of the chosen task, excluded dense index or -1 */
+#define THR_POSQ3_FLAGS 7        /* int32[groups], THR_POSQ3_INCONSISTENT | _EXCLUDED | _NO_CANDIDATE */
+#define THR_POSQ3_FULL_POS 8     /* float64[groups][3]: the full solve */
+#define THR_POSQ3_FULL_STATUS 9  /* int32[groups] */
+#define THR_POSQ3_SNR 10         /* float64[groups]: the mean over all rows, as thr_pos3 */
+#define THR_POSQ3_RESIDUAL 11    /* float64[rows], metres, at the chosen position */
+#define THR_POSQ3_USED 12        /* uint8[rows]: 1 = the row belongs to the chosen task */
+#define THR_POSQ3_TASK_PTR 13    /* int64[groups + 1] into the candidates */
+#define THR_POSQ3_TASK_RX 14     /* int32[tasks]: the receiver left out (dense index) */
+#define THR_POSQ3_TASK_POS 15    /* float64[tasks][3] */
+#define THR_POSQ3_TASK_RMS 16    /* float64[tasks] */
+#define THR_POSQ3_TASK_STATUS 17 /* int32[tasks] */
+#define THR_POSQ3_TASK_NRX 18    /* int32[tasks]: distinct receivers of the candidate's rows */
+#define THR_POSQ3_TASK_ITERS 19  /* int32[tasks] */
+#define THR_POSQ3_HDOP 20        /* float64[groups]: the chosen task's, as thr_pos3 */
+#define THR_POSQ3_VDOP 21        /* float64[groups] */
+#define THR_POSQ3_N_OUTPUTS 22
+int thr_posq3(int device_id, size_t n_groups, const int64_t* group_ptr, const int32_t* row_rx0, const int32_t* row_rx1,
+              const double* row_tdoa, const double* row_snr, const double* row_weight /* NULL: unweighted */, int n_rx,
+              const double* rx_xyz, int mode /* THR_POS3_* */, const double* group_h /* [n_groups], or NULL with z free */,
+              const thr_posq3_opts* opts, thr_posq3_result** result_out, thr_posq3_counts* counts_out);
+/* `which` is a THR_POSQ3_* index; dst_bytes must be the size given there */
+int thr_posq3_fetch(thr_posq3_result* result, int which, void* dst, size_t dst_bytes);
+void thr_posq3_free(thr_posq3_result* result);
+/* Milliseconds of the calling thread's last thr_posq3: {copies in, full solves, flags and expansion, candidates,
+ * choice and residuals, copies out (summed over the fetches)} */
+int thr_debug_posq3_times(double* ms_out /* [6] */);
 
 #ifdef __cplusplus
 }

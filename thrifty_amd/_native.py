@@ -62,6 +62,7 @@ EXPORTS = [
     "thr_coverage", "thr_coverage_fetch", "thr_coverage_free", "thr_debug_coverage_times",
     "thr_pos3", "thr_debug_pos3_times",
     "thr_posg3", "thr_posg3_fetch", "thr_posg3_free", "thr_debug_posg3_times",
+    "thr_posq3", "thr_posq3_fetch", "thr_posq3_free", "thr_debug_posq3_times",
 ]
 ERR_ARG, ERR_DEVICE, ERR_STATE, ERR_INDEX = -1, -2, -3, -4       # THR_ERR_*
 VARIANT_DEFAULT, VARIANT_PRESHIFT, VARIANT_FASTDET, VARIANT_GATE = 0, 1, 2, 3      # THR_VARIANT_*
@@ -123,6 +124,15 @@ class ThrPosg3Opts(C.Structure):          # thr_posg3_opts
     _fields_ = [("max_iter", C.c_int32), ("grid", C.c_int32), ("grid_z", C.c_int32), ("starts", C.c_int32),
                 ("x0", C.c_double * 3), ("margin_m", C.c_double), ("merge_m", C.c_double), ("ratio", C.c_double),
                 ("floor_m", C.c_double), ("map_first", C.c_int64), ("map_count", C.c_int32)]
+
+
+class ThrPosq3Counts(C.Structure):        # thr_posq3_counts
+    _fields_ = [(name, C.c_size_t) for name in POSQ_COUNTS]
+
+
+class ThrPosq3Opts(C.Structure):          # thr_posq3_opts
+    _fields_ = [("max_iter", C.c_int32), ("min_rx", C.c_int32), ("has_z_range", C.c_int32), ("x0", C.c_double * 3),
+                ("z_range", C.c_double * 2), ("gate_m", C.c_double), ("ratio", C.c_double)]
 
 
 class ThrTdmatCounts(C.Structure):        # thr_tdmat_counts
@@ -483,6 +493,13 @@ def load_library():
     lib.thr_posg3_fetch.argtypes = [vp, C.c_int, vp, C.c_size_t]
     lib.thr_posg3_free.argtypes = [vp]
     lib.thr_posg3_free.restype = None
+    if hasattr(lib, "thr_posq3"):       # a THRIFTY_HIP_LIB build from before thr_posq3 still loads for an A/B run; posq3() on it raises
+        lib.thr_posq3.argtypes = ([C.c_int, C.c_size_t] + [vp] * 6 + [C.c_int, vp, C.c_int, vp, C.POINTER(ThrPosq3Opts), C.POINTER(vp),
+                                  C.POINTER(ThrPosq3Counts)])
+        lib.thr_debug_posq3_times.argtypes = [C.POINTER(C.c_double)]
+        lib.thr_posq3_fetch.argtypes = [vp, C.c_int, vp, C.c_size_t]
+        lib.thr_posq3_free.argtypes = [vp]
+        lib.thr_posq3_free.restype = None
     for stem in ("bsync", "tdstats", "reldist", "posq", "track", "posg", "tdmat", "coverage"):
         getattr(lib, "thr_%s_fetch" % stem).argtypes = [vp, C.c_int, vp, C.c_size_t]
         getattr(lib, "thr_%s_free" % stem).argtypes = [vp]
@@ -2629,4 +2646,87 @@ def posg3_times():
     lib = load_library()
     ms = (C.c_double * 6)()
     _check(lib, lib.thr_debug_posg3_times(ms))
+    return tuple(ms)
+
+
+POSQ3_INCONSISTENT, POSQ3_EXCLUDED, POSQ3_NO_CANDIDATE = 1, 2, 4      # THR_POSQ3_* flags
+# the floors of min_rx (known height, free z): N receivers give N - 1 independent TDOAs, and a candidate (N - 1
+# receivers) must keep one redundant arrival: N - 2 > unknowns
+POSQ3_MIN_RX = (5, 6)
+# THR_POSQ3_*: name -> (index, dtype, shape as a function of the counts); POSQ_OUTPUTS' names, indices and types
+POSQ3_OUTPUTS = {
+    "pos": (0, np.float64, lambda c: (c["groups"], 3)),
+    "dop": (1, np.float64, lambda c: (c["groups"],)),
+    "status": (2, np.int32, lambda c: (c["groups"],)),
+    "iters": (3, np.int32, lambda c: (c["groups"],)),
+    "q": (4, np.float64, lambda c: (c["groups"], 6)),
+    "rms": (5, np.float64, lambda c: (c["groups"], 2)),
+    "counts": (6, np.int32, lambda c: (c["groups"], 3)),
+    "flags": (7, np.int32, lambda c: (c["groups"],)),
+    "full_pos": (8, np.float64, lambda c: (c["groups"], 3)),
+    "full_status": (9, np.int32, lambda c: (c["groups"],)),
+    "snr": (10, np.float64, lambda c: (c["groups"],)),
+    "residual": (11, np.float64, lambda c: (c["rows"],)),
+    "used": (12, np.uint8, lambda c: (c["rows"],)),
+    "task_ptr": (13, np.int64, lambda c: (c["groups"] + 1,)),
+    "task_rx": (14, np.int32, lambda c: (c["tasks"],)),
+    "task_pos": (15, np.float64, lambda c: (c["tasks"], 3)),
+    "task_rms": (16, np.float64, lambda c: (c["tasks"],)),
+    "task_status": (17, np.int32, lambda c: (c["tasks"],)),
+    "task_nrx": (18, np.int32, lambda c: (c["tasks"],)),
+    "task_iters": (19, np.int32, lambda c: (c["tasks"],)),
+    "hdop": (20, np.float64, lambda c: (c["groups"],)),
+    "vdop": (21, np.float64, lambda c: (c["groups"],)),
+}
+
+
+def posq3(group_ptr, row_rx0, row_rx1, row_tdoa, row_snr, rx_xyz, mode, group_h=None, row_weight=None, gate_m=0.0, ratio=0.5,
+          min_rx=None, x0=(0.1, 0.1, 0.0), z_range=None, max_iter=100, outputs=None, device_id=0):
+    """thr_posq3 on TDOA rows in CSR form (thr_pos3's columns: dense receiver indices into rx_xyz[n_rx, 3]) with an
+    optional weight per row -> (counts dict, {name: array}) with every output of POSQ3_OUTPUTS (or those named in
+    `outputs`) fetched.  mode POS3_KNOWN_HEIGHT reads group_h[g]; POS3_FREE_Z reads x0[2] and z_range.  gate_m == 0
+    switches the exclusion off; min_rx None is the mode's floor (POSQ3_MIN_RX).  ValueError for what thr_posq3 refuses."""
+    lib = load_library()
+    ptr = np.ascontiguousarray(group_ptr, dtype=np.int64)
+    rx0, rx1 = np.ascontiguousarray(row_rx0, dtype=np.int32), np.ascontiguousarray(row_rx1, dtype=np.int32)
+    tdoa, snr = np.ascontiguousarray(row_tdoa, dtype=np.float64), np.ascontiguousarray(row_snr, dtype=np.float64)
+    weight = None if row_weight is None else np.ascontiguousarray(row_weight, dtype=np.float64)
+    xyz = np.ascontiguousarray(rx_xyz, dtype=np.float64)
+    if (ptr.ndim != 1 or len(ptr) < 1 or xyz.ndim != 2 or xyz.shape[1] != 3 or
+            not (len(rx0) == len(rx1) == len(tdoa) == len(snr) == int(ptr[-1]))):
+        raise ValueError("posq3: group_ptr, the row columns or rx_xyz[n_rx, 3] have the wrong shape")
+    if weight is not None and weight.shape != tdoa.shape:
+        raise ValueError("posq3: one weight per row")
+    n = len(ptr) - 1
+    start = np.ascontiguousarray(x0, dtype=np.float64)
+    if start.shape != (3,):
+        raise ValueError("posq3: x0 holds three values")
+    heights = None if group_h is None else np.ascontiguousarray(group_h, dtype=np.float64)
+    if heights is not None and heights.shape != (n,):
+        raise ValueError("posq3: group_h holds one height per group")
+    box = None if z_range is None else np.ascontiguousarray(z_range, dtype=np.float64)
+    if box is not None and box.shape != (2,):
+        raise ValueError("posq3: z_range holds two values")
+    if min_rx is None:
+        min_rx = POSQ3_MIN_RX[1 if int(mode) == POS3_FREE_Z else 0]
+    opts = ThrPosq3Opts(int(max_iter), int(min_rx), int(box is not None), (C.c_double * 3)(*start.tolist()),
+                        (C.c_double * 2)(*(box.tolist() if box is not None else (0.0, 0.0))), float(gate_m), float(ratio))
+    keep = np.zeros(1, dtype=np.float64)      # an empty column still needs a pointer that is not NULL
+    handle, counts = C.c_void_p(), ThrPosq3Counts()
+    rc = lib.thr_posq3(int(device_id), n, ptr.ctypes.data, rx0.ctypes.data, rx1.ctypes.data, tdoa.ctypes.data, snr.ctypes.data,
+                       None if weight is None else (weight.ctypes.data if len(weight) else keep.ctypes.data),
+                       xyz.shape[0], xyz.ctypes.data, int(mode), _ptr(heights), C.byref(opts), C.byref(handle), C.byref(counts))
+    if rc == ERR_ARG:
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
+    c = {name: int(getattr(counts, name)) for name in POSQ_COUNTS}
+    return c, _fetch_all(lib, "posq3", handle, c, POSQ3_OUTPUTS, outputs)
+
+
+def posq3_times():
+    """Milliseconds (HIP events) of this thread's last posq3(): copies in, full solves, flags and expansion, candidates,
+    choice and residuals, copies out."""
+    lib = load_library()
+    ms = (C.c_double * 6)()
+    _check(lib, lib.thr_debug_posq3_times(ms))
     return tuple(ms)

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libthriftyhip.so")
-SOURCES = ["handle.hip", "window.hip", "pipeline.hip", "entry.hip", "text.hip", "detect16k.hip", "detect16k_geom0.hip", "detect16k_geom1.hip", "detect16k_geom2.hip", "detect16k_carrier.hip", "detect16k_preshift.hip", "detect16k_sec.hip", "detect_seg.hip", "detect_long.hip", "detect_small.hip", "generic.hip", "card_ingest.hip", "identify.hip", "run_file.hip", "card_gate.hip", "run_gate.hip", "template_extract.hip", "run_extract.hip", "match.hip", "tdoa.hip", "pos.hip", "postdetect.hip", "survey.hip", "chipscan.hip", "toadstats.hip", "syncstats.hip", "dossier.hip", "reldist.hip", "posq.hip", "track.hip", "posg.hip", "tdoamatrix.hip", "coverage.hip", "pos3.hip", "posg3.hip"]
+SOURCES = ["handle.hip", "window.hip", "pipeline.hip", "entry.hip", "text.hip", "detect16k.hip", "detect16k_geom0.hip", "detect16k_geom1.hip", "detect16k_geom2.hip", "detect16k_carrier.hip", "detect16k_preshift.hip", "detect16k_sec.hip", "detect_seg.hip", "detect_long.hip", "detect_small.hip", "generic.hip", "card_ingest.hip", "identify.hip", "run_file.hip", "card_gate.hip", "run_gate.hip", "template_extract.hip", "run_extract.hip", "match.hip", "tdoa.hip", "pos.hip", "postdetect.hip", "survey.hip", "chipscan.hip", "toadstats.hip", "syncstats.hip", "dossier.hip", "reldist.hip", "posq.hip", "track.hip", "posg.hip", "tdoamatrix.hip", "coverage.hip", "pos3.hip", "posg3.hip", "posq3.hip"]
 HEADERS = ["host_internal.hpp", "correlate16k.hpp", "correlate16k_geom.hpp", "detect_common.hpp", "fft_regs.hpp", "kernel_util.hpp", "lmdif8.hpp", "passes_w8.hpp", "card_gate.hpp", "template_extract.hpp", "post_stages.hpp", "run_loop.hpp", "hip_own.hpp", "input_window.hpp", "survey.hpp", "chipscan.hpp", "dossier.hpp", "seg_reduce.hpp", "seg_cells.hpp", "pos_lm.hpp", "track_scan.hpp", "tdoa_task.hpp", "pos3_lm.hpp", os.path.join("..", "..", "include", "thrifty_hip.h")]
 HOST_ONLY = ("handle.hip", "window.hip", "pipeline.hip", "entry.hip", "text.hip", "run_file.hip", "run_gate.hip", "run_extract.hip",
              "host_internal.hpp", "run_loop.hpp", "hip_own.hpp", "input_window.hpp")     # no kernels: csrc_hash() leaves these out
@@ -58,6 +58,8 @@ UNPROFILED_COVERAGE = ("coverage.hip",)
 UNPROFILED_POS3 = ("pos3.hip", "pos3_lm.hpp")
 # and for the global solve on receivers with three coordinates (thr_posg3)
 UNPROFILED_POSG3 = ("posg3.hip",)
+# and for the position quality on receivers with three coordinates (thr_posq3)
+UNPROFILED_POSQ3 = ("posq3.hip",)
 # per-file code-generation flags (measured on MI355X, see csrc/detect16k_carrier.hip)
 PER_FILE_FLAGS = {"detect16k_carrier.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                   # the work cursor's atomicAdd stays ONE lane's atomic whose result is waited for where it is
@@ -86,7 +88,9 @@ PER_FILE_FLAGS = {"detect16k_carrier.hip": ["-mllvm", "-amdgpu-sched-strategy=ma
                   # the team's eight lanes must agree bit for bit, and the known-height mode on a flat table gives thr_pos's bits
                   "pos3.hip": ["-ffp-contract=off"],
                   # a task must return thr_pos3's bits, and a cell's sum the statement's (thr_posg's on a flat table)
-                  "posg3.hip": ["-ffp-contract=off"]}
+                  "posg3.hip": ["-ffp-contract=off"],
+                  # a task must return thr_pos3's bits, a column of ones the unweighted bits, a flat table thr_posq's
+                  "posq3.hip": ["-ffp-contract=off"]}
 
 
 # host glue in C (CPython API, no device code): the batch constructor of the per-block result objects
@@ -125,11 +129,11 @@ def compile_cmd(src, path, obj, extra=()):
 
 def csrc_hash():
     """sha256 (first 16 hex digits) over the kernel sources and headers (everything but the host
-    side, HOST_ONLY, and the kernels no profiled workload launches, UNPROFILED / UNPROFILED_EXTRACT / UNPROFILED_MATCH / UNPROFILED_TDOA / UNPROFILED_POS / UNPROFILED_POST / UNPROFILED_SURVEY / UNPROFILED_CHIPSCAN / UNPROFILED_TOADSTATS / UNPROFILED_SYNCSTATS / UNPROFILED_SEGREDUCE / UNPROFILED_DOSSIER / UNPROFILED_RELDIST / UNPROFILED_POSQ / UNPROFILED_TRACK / UNPROFILED_POSG / UNPROFILED_TDMAT / UNPROFILED_COVERAGE / UNPROFILED_POS3 / UNPROFILED_POSG3): profiles/hbm_traffic.json records the hash its counter passes were taken on,
+    side, HOST_ONLY, and the kernels no profiled workload launches, UNPROFILED / UNPROFILED_EXTRACT / UNPROFILED_MATCH / UNPROFILED_TDOA / UNPROFILED_POS / UNPROFILED_POST / UNPROFILED_SURVEY / UNPROFILED_CHIPSCAN / UNPROFILED_TOADSTATS / UNPROFILED_SYNCSTATS / UNPROFILED_SEGREDUCE / UNPROFILED_DOSSIER / UNPROFILED_RELDIST / UNPROFILED_POSQ / UNPROFILED_TRACK / UNPROFILED_POSG / UNPROFILED_TDMAT / UNPROFILED_COVERAGE / UNPROFILED_POS3 / UNPROFILED_POSG3 / UNPROFILED_POSQ3): profiles/hbm_traffic.json records the hash its counter passes were taken on,
     bench.py flags a mismatch (`traffic_stale`)."""
     import hashlib
     h = hashlib.sha256()
-    skipped = HOST_ONLY + UNPROFILED + UNPROFILED_EXTRACT + UNPROFILED_MATCH + UNPROFILED_TDOA + UNPROFILED_POS + UNPROFILED_POST + UNPROFILED_SURVEY + UNPROFILED_CHIPSCAN + UNPROFILED_TOADSTATS + UNPROFILED_SYNCSTATS + UNPROFILED_SEGREDUCE + UNPROFILED_DOSSIER + UNPROFILED_RELDIST + UNPROFILED_POSQ + UNPROFILED_TRACK + UNPROFILED_POSG + UNPROFILED_TDMAT + UNPROFILED_COVERAGE + UNPROFILED_POS3 + UNPROFILED_POSG3
+    skipped = HOST_ONLY + UNPROFILED + UNPROFILED_EXTRACT + UNPROFILED_MATCH + UNPROFILED_TDOA + UNPROFILED_POS + UNPROFILED_POST + UNPROFILED_SURVEY + UNPROFILED_CHIPSCAN + UNPROFILED_TOADSTATS + UNPROFILED_SYNCSTATS + UNPROFILED_SEGREDUCE + UNPROFILED_DOSSIER + UNPROFILED_RELDIST + UNPROFILED_POSQ + UNPROFILED_TRACK + UNPROFILED_POSG + UNPROFILED_TDMAT + UNPROFILED_COVERAGE + UNPROFILED_POS3 + UNPROFILED_POSG3 + UNPROFILED_POSQ3
     for name in sorted(x for x in SOURCES + HEADERS if not x.startswith("..") and x not in skipped):
         h.update(name.encode())
         with open(os.path.join(CSRC, name), "rb") as f:

@@ -24,6 +24,14 @@
 //     team sums of pos_lm.hpp (F, the 2 x 2 normal matrix A, the gradient) with the 3-D ranges in the denominators.
 //   free z: ten team sums (F, six entries of A, three of g); the step is solved on the free axes only -- 3 x 3 by
 //     cofactors, 2 x 2 or 1 x 1 -- from identical values in the eight lanes.
+//
+// Weights and row subsets (thr_posq3, posq3.hip) are pos_lm.hpp's, behind two trailing template parameters whose
+// defaults are the solve above: WEIGHTED == false reads no weight and leaves every expression as it stands;
+// WEIGHTED == true counts row i as w_i * (m_used / sum_used w), the sum a group8_sum in team order followed by ONE
+// division, so a column of ones gives the factor 1.0 exactly and the unweighted bits, and a zero sum ends kNonfinite.
+// A `Used` predicate (poslm::AllRows, poslm::NotReceiver) numbers the used rows in order and gives lane j the numbers
+// j, j + 8, ...: what it would hold of the group REBUILT without the other rows.  With the height known the weighted
+// expressions are pos_lm.hpp's weighted ones, operand for operand.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,30 +73,58 @@ struct Fit {  // identical in the team's eight lanes
     double p0, p1, p2;
     Sums cur;  // the last accepted evaluation
     int status, iters;
-    int n_distinct;  // distinct receivers of the rows
-    double snr_mean;
+    int n_distinct;  // distinct receivers of the used rows
+    double snr_mean; // over ALL rows of the group
+    int m_used;      // used rows
+    unsigned long long mask;  // receivers of the used rows
 };
 
-// one row's terms at (px, py, pz), added to the lane's partial sums when `on`
+// the residual of one row at (px, py, pz): the expression every sum and every reported residual goes through (with
+// the height known the row holds rz - h and pz is not read)
 template <bool FREE_Z>
-__device__ __forceinline__ void add_row(const Row& r, bool on, double px, double py, double pz, Sums& s) {
+__device__ __forceinline__ double residual(const Row& r, double px, double py, double pz) {
+    const double ax = r.ax - px, ay = r.ay - py, bx = r.bx - px, by = r.by - py;
+    const double az = FREE_Z ? r.az - pz : r.az, bz = FREE_Z ? r.bz - pz : r.bz;
+    const double da = sqrt((ax * ax + ay * ay) + az * az), db = sqrt((bx * bx + by * by) + bz * bz);
+    return r.tc - (da - db);
+}
+
+// one row's terms at (px, py, pz), added to the lane's partial sums when `on`; w is read only when WEIGHTED
+template <bool FREE_Z, bool WEIGHTED = false>
+__device__ __forceinline__ void add_row(const Row& r, bool on, double px, double py, double pz, Sums& s, double w = 1.0) {
     const double ax = r.ax - px, ay = r.ay - py, bx = r.bx - px, by = r.by - py;
     const double az = FREE_Z ? r.az - pz : r.az, bz = FREE_Z ? r.bz - pz : r.bz;
     const double da = sqrt((ax * ax + ay * ay) + az * az), db = sqrt((bx * bx + by * by) + bz * bz);
     const double res = r.tc - (da - db);
     const double gx = ax / da - bx / db, gy = ay / da - by / db;
-    s.F += on ? res * res : 0.0;
-    s.a00 += on ? gx * gx : 0.0;
-    s.a01 += on ? gx * gy : 0.0;
-    s.a11 += on ? gy * gy : 0.0;
-    s.g0 += on ? gx * res : 0.0;
-    s.g1 += on ? gy * res : 0.0;
+    if (WEIGHTED) {
+        s.F += on ? w * (res * res) : 0.0;
+        s.a00 += on ? w * (gx * gx) : 0.0;
+        s.a01 += on ? w * (gx * gy) : 0.0;
+        s.a11 += on ? w * (gy * gy) : 0.0;
+        s.g0 += on ? w * (gx * res) : 0.0;
+        s.g1 += on ? w * (gy * res) : 0.0;
+    } else {
+        s.F += on ? res * res : 0.0;
+        s.a00 += on ? gx * gx : 0.0;
+        s.a01 += on ? gx * gy : 0.0;
+        s.a11 += on ? gy * gy : 0.0;
+        s.g0 += on ? gx * res : 0.0;
+        s.g1 += on ? gy * res : 0.0;
+    }
     if (FREE_Z) {
         const double gz = az / da - bz / db;
-        s.a02 += on ? gx * gz : 0.0;
-        s.a12 += on ? gy * gz : 0.0;
-        s.a22 += on ? gz * gz : 0.0;
-        s.g2 += on ? gz * res : 0.0;
+        if (WEIGHTED) {
+            s.a02 += on ? w * (gx * gz) : 0.0;
+            s.a12 += on ? w * (gy * gz) : 0.0;
+            s.a22 += on ? w * (gz * gz) : 0.0;
+            s.g2 += on ? w * (gz * res) : 0.0;
+        } else {
+            s.a02 += on ? gx * gz : 0.0;
+            s.a12 += on ? gy * gz : 0.0;
+            s.a22 += on ? gz * gz : 0.0;
+            s.g2 += on ? gz * res : 0.0;
+        }
     }
 }
 
@@ -127,27 +163,60 @@ __device__ __forceinline__ void dop3_of(const Sums& s, double& dop, double& hdop
     vdop = bad ? -1.0 : sqrt(i22);
 }
 
-// Rows beg .. beg + m of a group, lane j of the team (j = threadIdx.x & 7).  A team that is not `live` (past the
-// last group) runs along with m == 0.  group_ptr, rx0 / rx1 (< 64) and the table were checked on the host.
-// FREE_Z == false: h is the group's height, z0 and the box's z are not read, and Fit::p2 is h.
-template <bool FREE_Z, int REG_ROWS>
+// Rows beg .. beg + m of a group, lane j of the team (j = threadIdx.x & 7); `used(i)` says whether row i (its
+// position in the columns) belongs to the task, and Used::kAll that it always does (the rows are then not walked).
+// A team that is not `live` (past the last task) runs along with m == 0.  group_ptr, rx0 / rx1 (< 64) and the table
+// were checked on the host.  FREE_Z == false: h is the group's height, z0 and the box's z are not read, and Fit::p2
+// is h.  `weight` is read only when WEIGHTED.
+template <bool FREE_Z, int REG_ROWS, bool WEIGHTED = false, class Used = poslm::AllRows>
 __device__ __forceinline__ Fit solve_team(bool live, long long beg, int m, int j, const int* __restrict__ rx0,
                                           const int* __restrict__ rx1, const double* __restrict__ tdoa,
                                           const double* __restrict__ snr, const double* __restrict__ xyz, double h,
-                                          double x0, double y0, double z0, const Box& box, int max_iter) {
+                                          double x0, double y0, double z0, const Box& box, int max_iter,
+                                          const double* __restrict__ weight = nullptr, Used used = Used{}) {
     const double lo0 = box.lo0, lo1 = box.lo1, lo2 = box.lo2, hi0 = box.hi0, hi1 = box.hi1, hi2 = box.hi2;
     constexpr int kNeeded = FREE_Z ? 4 : 3;  // distinct receivers
+    // ---- the lane's rows.  Every row: lane j owns rows j, j + 8, ...  A subset: used row number n of the group
+    // (counted over the used rows only) belongs to lane n % 8 as its row n / 8 -- the layout of the group rebuilt
+    // without the rows that are off
     Row reg[REG_ROWS];
     bool on[REG_ROWS];
+    double wreg[REG_ROWS];
     unsigned long long mask = 0;
+    int n_used = m, resume = m;  // resume: the first row that no register holds a used row up to
+    if (Used::kAll) {
 #pragma unroll
-    for (int k = 0; k < REG_ROWS; ++k) {
-        const int r = j + kTeam * k;
-        on[k] = r < m;
-        if (on[k]) mask |= (1ull << rx0[beg + r]) | (1ull << rx1[beg + r]);
-        reg[k] = on[k] ? load_row(rx0, rx1, tdoa, xyz, h, beg + r) : Row{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0};
+        for (int k = 0; k < REG_ROWS; ++k) {
+            const int r = j + kTeam * k;
+            on[k] = r < m;
+            if (on[k]) mask |= (1ull << rx0[beg + r]) | (1ull << rx1[beg + r]);
+            reg[k] = on[k] ? load_row(rx0, rx1, tdoa, xyz, h, beg + r) : Row{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0};
+            wreg[k] = (WEIGHTED && on[k]) ? weight[beg + r] : 0.0;
+        }
+        for (int r = j + kTeam * REG_ROWS; r < m; r += kTeam) mask |= (1ull << rx0[beg + r]) | (1ull << rx1[beg + r]);
+    } else {
+        int row_of[REG_ROWS];  // relative to beg; -1: none
+#pragma unroll
+        for (int k = 0; k < REG_ROWS; ++k) row_of[k] = -1;
+        n_used = 0;
+        for (int r = 0; r < m; ++r) {  // every lane walks the whole group: two ints per row
+            if (!used(beg + r)) continue;
+            mask |= (1ull << rx0[beg + r]) | (1ull << rx1[beg + r]);
+            if ((n_used & (kTeam - 1)) == j) {
+#pragma unroll
+                for (int k = 0; k < REG_ROWS; ++k)
+                    if (k == n_used / kTeam) row_of[k] = r;
+            }
+            ++n_used;
+            if (n_used == kTeam * REG_ROWS) resume = r + 1;
+        }
+#pragma unroll
+        for (int k = 0; k < REG_ROWS; ++k) {
+            on[k] = row_of[k] >= 0;
+            reg[k] = on[k] ? load_row(rx0, rx1, tdoa, xyz, h, beg + row_of[k]) : Row{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0};
+            wreg[k] = (WEIGHTED && on[k]) ? weight[beg + row_of[k]] : 0.0;
+        }
     }
-    for (int r = j + kTeam * REG_ROWS; r < m; r += kTeam) mask |= (1ull << rx0[beg + r]) | (1ull << rx1[beg + r]);
     unsigned mlo = unsigned(mask), mhi = unsigned(mask >> 32);
 #pragma unroll
     for (int d = 1; d < kTeam; d <<= 1) {
@@ -156,15 +225,46 @@ __device__ __forceinline__ Fit solve_team(bool live, long long beg, int m, int j
     }
     const int n_distinct = __popc(mlo) + __popc(mhi);
     double snr_sum = 0.0;
-    for (int r = j; r < m; r += kTeam) snr_sum += snr[beg + r];
+    for (int r = j; r < m; r += kTeam) snr_sum += snr[beg + r];  // ALL rows, in the lanes of the whole group
     const double snr_mean = group8_sum(snr_sum) / double(m);
+
+    // the rows past the registers: f(row) for this lane's, in order
+    auto reread = [&](auto&& f) {
+        if (Used::kAll) {
+            for (int r = j + kTeam * REG_ROWS; r < m; r += kTeam) f(beg + r);
+        } else {
+            int n = kTeam * REG_ROWS;
+            for (int r = resume; r < m; ++r) {
+                if (!used(beg + r)) continue;
+                if ((n & (kTeam - 1)) == j) f(beg + r);
+                ++n;
+            }
+        }
+    };
+
+    double w_scale = 1.0;
+    if (WEIGHTED) {
+        double w_sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < REG_ROWS; ++k) w_sum += wreg[k];
+        reread([&](long long i) { w_sum += weight[i]; });
+        w_scale = double(n_used) / group8_sum(w_sum);
+#pragma unroll
+        for (int k = 0; k < REG_ROWS; ++k) wreg[k] = wreg[k] * w_scale;
+    }
 
     auto evaluate = [&](double px, double py, double pz) {
         Sums s{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int k = 0; k < REG_ROWS; ++k) add_row<FREE_Z>(reg[k], on[k], px, py, pz, s);
-        for (int r = j + kTeam * REG_ROWS; r < m; r += kTeam)  // long groups re-read their rows
-            add_row<FREE_Z>(load_row(rx0, rx1, tdoa, xyz, h, beg + r), true, px, py, pz, s);
+        for (int k = 0; k < REG_ROWS; ++k) add_row<FREE_Z, WEIGHTED>(reg[k], on[k], px, py, pz, s, wreg[k]);
+        if (Used::kAll && !WEIGHTED) {
+            for (int r = j + kTeam * REG_ROWS; r < m; r += kTeam)  // long groups re-read their rows
+                add_row<FREE_Z>(load_row(rx0, rx1, tdoa, xyz, h, beg + r), true, px, py, pz, s);
+        } else {
+            reread([&](long long i) {
+                add_row<FREE_Z, WEIGHTED>(load_row(rx0, rx1, tdoa, xyz, h, i), true, px, py, pz, s, WEIGHTED ? weight[i] * w_scale : 1.0);
+            });
+        }
         Sums t{group8_sum(s.F), group8_sum(s.a00), group8_sum(s.a01), group8_sum(s.a11), group8_sum(s.g0),
                group8_sum(s.g1), 0.0, 0.0, 0.0, 0.0};
         if (FREE_Z) {
@@ -284,7 +384,7 @@ __device__ __forceinline__ Fit solve_team(bool live, long long beg, int m, int j
     }
     if (status == kOk && (p0 <= lo0 || p0 >= hi0 || p1 <= lo1 || p1 >= hi1 || (FREE_Z && (p2 <= lo2 || p2 >= hi2))))
         status = kAtBound;
-    return Fit{p0, p1, p2, cur, status, iters, n_distinct, snr_mean};
+    return Fit{p0, p1, p2, cur, status, iters, n_distinct, snr_mean, n_used, (unsigned long long)mhi << 32 | mlo};
 }
 
 }  // namespace pos3lm
