@@ -605,7 +605,8 @@ FREQ_RANGE_DTYPE = np.dtype([("rxid", "<i4"), ("txid", "<i4"), ("lo", "<f8"), ("
 def identify(rxid, block, timestamp, carrier_bin, carrier_offset, energy, freq_ranges=None,
              device_id=0):
     """thr_identify on columns -> (txid int32[n], keep bool[n], kept_order int64[k]).
-    freq_ranges: None (automatic windows) or rows (rxid, txid, lo, hi) in map order."""
+    freq_ranges: None (automatic windows) or rows (rxid, txid, lo, hi) in map order.  ValueError for what
+    thr_identify refuses."""
     lib = load_library()
     n = len(rxid)
     cols = [np.ascontiguousarray(rxid, dtype=np.int32), np.ascontiguousarray(block, dtype=np.int32),
@@ -622,10 +623,13 @@ def identify(rxid, block, timestamp, carrier_bin, carrier_offset, energy, freq_r
     keep = np.zeros(n, dtype=np.uint8)
     order = np.zeros(n, dtype=np.int64)
     n_kept = C.c_size_t(0)
-    _check(lib, lib.thr_identify(int(device_id), n, *[c.ctypes.data for c in cols],
-                                 fmap.ctypes.data if len(fmap) else None, len(fmap),
-                                 txid.ctypes.data, keep.ctypes.data, order.ctypes.data,
-                                 C.byref(n_kept)))
+    rc = lib.thr_identify(int(device_id), n, *[c.ctypes.data for c in cols],
+                          fmap.ctypes.data if len(fmap) else None, len(fmap),
+                          txid.ctypes.data, keep.ctypes.data, order.ctypes.data,
+                          C.byref(n_kept))
+    if rc == ERR_ARG:       # like every other post-detect wrapper: what the library refuses is a ValueError
+        raise ValueError(lib.thr_last_error().decode())
+    _check(lib, rc)
     return txid, keep.astype(bool), order[:n_kept.value]
 
 
