@@ -119,7 +119,10 @@ extern "C" {
  *      further starts of thr_pos3's own iteration, the best minimum, the runner-up, and a flag where the two differ
  *      in height only (the mirror about nearly coplanar antennas)
  *    + thr_posq3 / thr_posq3_fetch / thr_posq3_free / thr_debug_posq3_times -- thr_posq's weights, residuals,
- *      inverse normal matrix and receiver exclusion for thr_pos3's two modes */
+ *      inverse normal matrix and receiver exclusion for thr_pos3's two modes
+ *    + thr_extract_average / thr_extract_average_counts / thr_extract_average_result and thr_average_opts -- an
+ *      extraction that also sums the cut of EVERY qualifying detection, per transmitter class: the averaged
+ *      template, its standard error per sample and the counts (thr_extract_result's outputs unchanged) */
 #define THR_ABI_VERSION 11
 
 /* status codes */
@@ -752,6 +755,58 @@ int thr_run_extract_card(thr_handle* h, const char* text, size_t text_len, const
                          thr_extract* x, thr_run_stats* stats);
 int thr_run_extract_stream(thr_handle* h, const uint8_t* stream, size_t n_bytes, int64_t first_block_idx,
                            const thr_run_opts* opts, thr_extract* x, thr_run_stats* stats);
+
+/*
+ * Averaged templates -- the cut of EVERY qualifying detection summed on the device, per transmitter class,
+ * where thr_extract_result remembers one block.  The single best block carries all of that block's receiver
+ * noise; a capture made for extraction holds hundreds of qualifying detections.  The sums ride behind every
+ * batch like the fold and the keep (csrc/template_average.hip), whatever the input form.  W = template_len.
+ *
+ * Armed: thr_extract_average with `opts` arms averaging on `x`, with NULL disarms it.  Allowed only while
+ *   nothing has been fed since thr_extract_create or thr_extract_reset (else THR_ERR_STATE).  THR_ERR_ARG with
+ *   a sentence: n_classes outside 0 .. THR_AVERAGE_MAX_CLASSES, a bound that is not finite, lo > hi.  While
+ *   armed, a feed of THR_IN_C64 samples is THR_ERR_ARG: the sums are exact integers of the u8 quantiser.
+ * Qualifies: the extraction's rule, unchanged: THR_FLAG_CORR set and |corr_offset| <= max_offset.
+ * Class of a qualifying record: n_classes == 0: class 0.  Otherwise v = double(carrier_bin) + carrier_offset
+ *   and the class is the LAST k with lo[k] <= v <= hi[k] (thr_identify's rule: inclusive, last match wins).
+ *   No match: the record is counted in n_unclassified and accumulated nowhere.
+ * Per sample n = 0 .. W-1 of the cut, (bI, bQ) the bytes of sample corr_sample + n of that block:
+ *   q = (5 bI - 637)^2 + (5 bQ - 637)^2       640^2 times the squared magnitude of (b - 127.4) / 128, exact,
+ *                                             q < 2^20
+ *   e = floor(sqrt(q * 2^40))                 the INTEGER square root (a float square root corrected by
+ *                                             integer comparison): exact in any arithmetic
+ *   acc_e[k][n] += e, acc_q[k][n] += q        uint64; count[k] += 1 once per record
+ *   Integer sums: the result depends on the SET of qualifying records only -- not on the batching, the input
+ *   form, the order of lanes, or the order the atomic additions arrive in.
+ * Finish, per class with count >= 1 (float64, conversions round to nearest):
+ *   m[n] = double(acc_e[k][n]) / (double(count) * 671088640.0)                 671088640 = 2^20 * 640
+ *   template = the extraction kernel's arithmetic on m: mean and population standard deviation by the same
+ *     fixed tree, scale = 2 / (mean + std), times scale, minus the recomputed mean (one device function)
+ *   var[n] = max(double(acc_q[k][n]) / (double(count) * 409600.0) - m[n] * m[n], 0)       not contracted
+ *   sem[n] = sqrt(var[n] / double(count)) * scale
+ * The single-best result is untouched: thr_extract_result returns the same bytes armed or not.
+ *
+ * thr_extract_average_counts: waits like thr_extract_result; count[0 .. 16) (classes beyond n_classes: 0; with
+ *   n_classes == 0 everything is in count[0]) and *n_unclassified.  Either may be NULL.  Not armed: THR_ERR_STATE.
+ * thr_extract_average_result: waits, finishes class `k` and copies out template_out[W], sem_out[W] (float64),
+ *   acc_e_out[W], acc_q_out[W] (the sums; `capacity` in elements holds for all four, too small -> THR_ERR_ARG).
+ *   Any output may be NULL.  A class with count == 0: THR_ERR_STATE with a sentence, as thr_extract_result
+ *   answers when nothing qualified; the sums (zeros) are written in that case too and the counts stay readable.
+ *   Not armed: THR_ERR_STATE; `k` outside the armed classes: THR_ERR_ARG.
+ * thr_extract_reset zeroes the sums and keeps the arming.  thr_run_extract_card / thr_run_extract_stream
+ * enqueue whatever `x` has armed.  Not offered: complex64 input, weights, sub-sample alignment of the cuts
+ * (with |offset| <= 0.2 the jitter costs about 6 % of the amplitude at the Nyquist frequency).
+ */
+#define THR_AVERAGE_MAX_CLASSES 16
+typedef struct thr_average_opts {
+    int32_t n_classes;                      /* 0: one class, every qualifying record */
+    double lo[THR_AVERAGE_MAX_CLASSES];     /* carrier_bin + carrier_offset, inclusive */
+    double hi[THR_AVERAGE_MAX_CLASSES];
+} thr_average_opts;
+int thr_extract_average(thr_extract* x, const thr_average_opts* opts);
+int thr_extract_average_counts(thr_extract* x, uint64_t count[THR_AVERAGE_MAX_CLASSES], uint64_t* n_unclassified);
+int thr_extract_average_result(thr_extract* x, int k, double* template_out, double* sem_out, size_t capacity,
+                               uint64_t* acc_e_out, uint64_t* acc_q_out);
 
 /*
  * Detection dossiers -- the numbers behind the reference's `thrifty analyze_detect` (detect_analysis.py:

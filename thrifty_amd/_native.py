@@ -39,6 +39,7 @@ EXPORTS = [
     "thr_extract_create", "thr_extract_destroy", "thr_extract_reset", "thr_extract_feed", "thr_extract_feed_card",
     "thr_extract_feed_stream", "thr_extract_submit_card", "thr_extract_submit_stream", "thr_extract_result",
     "thr_run_extract_card", "thr_run_extract_stream",
+    "thr_extract_average", "thr_extract_average_counts", "thr_extract_average_result",
     "thr_match", "thr_debug_match_times",
     "thr_tdoa", "thr_debug_tdoa_times", "thr_tdoa_model",
     "thr_pos", "thr_debug_pos_times",
@@ -83,6 +84,14 @@ POSG3_COUNTS = ("groups", "rows", "tasks", "starts", "grid", "grid_z", "map_grou
 TDMAT_COUNTS = ("tasks", "cells", "rows", "tdoas")
 COVERAGE_COUNTS = ("cells", "nx", "ny", "n_rx", "trials", "covered", "tasks", "rows", "slabs", "slab_groups", "slab_bytes",
                    "keep_tasks", "keep_rows")
+
+
+AVERAGE_MAX_CLASSES = 16      # THR_AVERAGE_MAX_CLASSES
+
+
+class ThrAverageOpts(C.Structure):        # thr_average_opts
+    _fields_ = [("n_classes", C.c_int32), ("lo", C.c_double * AVERAGE_MAX_CLASSES),
+                ("hi", C.c_double * AVERAGE_MAX_CLASSES)]
 
 
 class ThrBsyncCounts(C.Structure):        # thr_bsync_counts
@@ -411,6 +420,9 @@ def load_library():
     lib.thr_extract_submit_card.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp, u64p]
     lib.thr_extract_submit_stream.argtypes = [vp, vp, C.c_size_t, C.c_int64, C.c_double, vp, C.c_size_t, szp, u64p]
     lib.thr_extract_result.argtypes = [vp, vp, C.POINTER(C.c_double), vp, C.c_size_t, u64p]
+    lib.thr_extract_average.argtypes = [vp, C.POINTER(ThrAverageOpts)]
+    lib.thr_extract_average_counts.argtypes = [vp, vp, u64p]
+    lib.thr_extract_average_result.argtypes = [vp, C.c_int, vp, vp, C.c_size_t, vp, vp]
     lib.thr_dossier_create.argtypes = [vp, vp, C.c_int, C.c_int64, C.POINTER(vp)]
     lib.thr_dossier_destroy.argtypes = [vp]
     lib.thr_dossier_destroy.restype = None
@@ -1356,6 +1368,44 @@ class Extraction(object):
             raise ValueError(self._lib.thr_last_error().decode())
         _check(self._lib, rc)
         return rec[0], ts.value, out, n.value
+
+    def average(self, classes=()):
+        """thr_extract_average: arm averaging before the first feed.  `classes`: a sequence of (lo, hi) ranges of
+        carrier_bin + carrier_offset (inclusive, the last match wins), empty: one class of every qualifying
+        record; None disarms."""
+        if classes is None:
+            _check(self._lib, self._lib.thr_extract_average(self._x, None))
+            self.n_classes = None
+            return
+        classes = [(float(lo), float(hi)) for lo, hi in classes]
+        if len(classes) > AVERAGE_MAX_CLASSES:
+            raise ValueError("an extraction averages at most %d classes, %d given" % (AVERAGE_MAX_CLASSES, len(classes)))
+        o = ThrAverageOpts()
+        o.n_classes = len(classes)
+        for k, (lo, hi) in enumerate(classes):
+            o.lo[k], o.hi[k] = lo, hi
+        _check(self._lib, self._lib.thr_extract_average(self._x, C.byref(o)))
+        self.n_classes = len(classes)
+
+    def average_counts(self):
+        """thr_extract_average_counts -> (count uint64[16], n_unclassified)."""
+        count = np.zeros(AVERAGE_MAX_CLASSES, dtype=np.uint64)
+        n = C.c_uint64(0)
+        _check(self._lib, self._lib.thr_extract_average_counts(self._x, count.ctypes.data, C.byref(n)))
+        return count, n.value
+
+    def average_result(self, k, template_len):
+        """thr_extract_average_result of class `k` -> (template, sem float64[W], acc_e, acc_q uint64[W]).
+        ValueError (with the library's sentence) if no record of the class has qualified."""
+        w = int(template_len)
+        tpl, sem = np.empty(w, dtype=np.float64), np.empty(w, dtype=np.float64)
+        acc_e, acc_q = np.zeros(w, dtype=np.uint64), np.zeros(w, dtype=np.uint64)
+        rc = self._lib.thr_extract_average_result(self._x, int(k), tpl.ctypes.data, sem.ctypes.data, w,
+                                                  acc_e.ctypes.data, acc_q.ctypes.data)
+        if rc == ERR_STATE:
+            raise ValueError(self._lib.thr_last_error().decode())
+        _check(self._lib, rc)
+        return tpl, sem, acc_e, acc_q
 
 
 class Dossiers(object):

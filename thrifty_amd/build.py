@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libthriftyhip.so")
-SOURCES = ["handle.hip", "window.hip", "pipeline.hip", "entry.hip", "text.hip", "detect16k.hip", "detect16k_geom0.hip", "detect16k_geom1.hip", "detect16k_geom2.hip", "detect16k_carrier.hip", "detect16k_preshift.hip", "detect16k_sec.hip", "detect_seg.hip", "detect_long.hip", "detect_small.hip", "generic.hip", "card_ingest.hip", "identify.hip", "run_file.hip", "card_gate.hip", "run_gate.hip", "template_extract.hip", "run_extract.hip", "match.hip", "tdoa.hip", "pos.hip", "postdetect.hip", "survey.hip", "chipscan.hip", "toadstats.hip", "syncstats.hip", "dossier.hip", "reldist.hip", "posq.hip", "track.hip", "posg.hip", "tdoamatrix.hip", "coverage.hip", "pos3.hip", "posg3.hip", "posq3.hip"]
+SOURCES = ["handle.hip", "window.hip", "pipeline.hip", "entry.hip", "text.hip", "detect16k.hip", "detect16k_geom0.hip", "detect16k_geom1.hip", "detect16k_geom2.hip", "detect16k_carrier.hip", "detect16k_preshift.hip", "detect16k_sec.hip", "detect_seg.hip", "detect_long.hip", "detect_small.hip", "generic.hip", "card_ingest.hip", "identify.hip", "run_file.hip", "card_gate.hip", "run_gate.hip", "template_extract.hip", "template_average.hip", "run_extract.hip", "match.hip", "tdoa.hip", "pos.hip", "postdetect.hip", "survey.hip", "chipscan.hip", "toadstats.hip", "syncstats.hip", "dossier.hip", "reldist.hip", "posq.hip", "track.hip", "posg.hip", "tdoamatrix.hip", "coverage.hip", "pos3.hip", "posg3.hip", "posq3.hip"]
 HEADERS = ["host_internal.hpp", "correlate16k.hpp", "correlate16k_geom.hpp", "detect_common.hpp", "fft_regs.hpp", "kernel_util.hpp", "lmdif8.hpp", "passes_w8.hpp", "card_gate.hpp", "template_extract.hpp", "post_stages.hpp", "run_loop.hpp", "hip_own.hpp", "input_window.hpp", "survey.hpp", "chipscan.hpp", "dossier.hpp", "seg_reduce.hpp", "seg_cells.hpp", "pos_lm.hpp", "track_scan.hpp", "tdoa_task.hpp", "pos3_lm.hpp", os.path.join("..", "..", "include", "thrifty_hip.h")]
 HOST_ONLY = ("handle.hip", "window.hip", "pipeline.hip", "entry.hip", "text.hip", "run_file.hip", "run_gate.hip", "run_extract.hip",
              "host_internal.hpp", "run_loop.hpp", "hip_own.hpp", "input_window.hpp")     # no kernels: csrc_hash() leaves these out
@@ -22,6 +22,9 @@ UNPROFILED = ("card_gate.hip", "card_gate.hpp")
 # the same for template extraction's fold, keep and cut kernels (a list of its own: tests/test_gate_host.py
 # pins UNPROFILED to the gate's two files)
 UNPROFILED_EXTRACT = ("template_extract.hip", "template_extract.hpp")
+# and for the averaged templates' classify, accumulate and finish kernels (a list of its own again:
+# tests/test_template_extract_host.py pins UNPROFILED_EXTRACT to the extraction's two files)
+UNPROFILED_AVERAGE = ("template_average.hip",)
 # and for the matcher (thr_match), which no workload of bench.py reaches
 UNPROFILED_MATCH = ("match.hip",)
 # and for the TDOA estimator (thr_tdoa)
@@ -129,11 +132,11 @@ def compile_cmd(src, path, obj, extra=()):
 
 def csrc_hash():
     """sha256 (first 16 hex digits) over the kernel sources and headers (everything but the host
-    side, HOST_ONLY, and the kernels no profiled workload launches, UNPROFILED / UNPROFILED_EXTRACT / UNPROFILED_MATCH / UNPROFILED_TDOA / UNPROFILED_POS / UNPROFILED_POST / UNPROFILED_SURVEY / UNPROFILED_CHIPSCAN / UNPROFILED_TOADSTATS / UNPROFILED_SYNCSTATS / UNPROFILED_SEGREDUCE / UNPROFILED_DOSSIER / UNPROFILED_RELDIST / UNPROFILED_POSQ / UNPROFILED_TRACK / UNPROFILED_POSG / UNPROFILED_TDMAT / UNPROFILED_COVERAGE / UNPROFILED_POS3 / UNPROFILED_POSG3 / UNPROFILED_POSQ3): profiles/hbm_traffic.json records the hash its counter passes were taken on,
+    side, HOST_ONLY, and the kernels no profiled workload launches, UNPROFILED / UNPROFILED_EXTRACT / UNPROFILED_AVERAGE / UNPROFILED_MATCH / UNPROFILED_TDOA / UNPROFILED_POS / UNPROFILED_POST / UNPROFILED_SURVEY / UNPROFILED_CHIPSCAN / UNPROFILED_TOADSTATS / UNPROFILED_SYNCSTATS / UNPROFILED_SEGREDUCE / UNPROFILED_DOSSIER / UNPROFILED_RELDIST / UNPROFILED_POSQ / UNPROFILED_TRACK / UNPROFILED_POSG / UNPROFILED_TDMAT / UNPROFILED_COVERAGE / UNPROFILED_POS3 / UNPROFILED_POSG3 / UNPROFILED_POSQ3): profiles/hbm_traffic.json records the hash its counter passes were taken on,
     bench.py flags a mismatch (`traffic_stale`)."""
     import hashlib
     h = hashlib.sha256()
-    skipped = HOST_ONLY + UNPROFILED + UNPROFILED_EXTRACT + UNPROFILED_MATCH + UNPROFILED_TDOA + UNPROFILED_POS + UNPROFILED_POST + UNPROFILED_SURVEY + UNPROFILED_CHIPSCAN + UNPROFILED_TOADSTATS + UNPROFILED_SYNCSTATS + UNPROFILED_SEGREDUCE + UNPROFILED_DOSSIER + UNPROFILED_RELDIST + UNPROFILED_POSQ + UNPROFILED_TRACK + UNPROFILED_POSG + UNPROFILED_TDMAT + UNPROFILED_COVERAGE + UNPROFILED_POS3 + UNPROFILED_POSG3 + UNPROFILED_POSQ3
+    skipped = HOST_ONLY + UNPROFILED + UNPROFILED_EXTRACT + UNPROFILED_AVERAGE + UNPROFILED_MATCH + UNPROFILED_TDOA + UNPROFILED_POS + UNPROFILED_POST + UNPROFILED_SURVEY + UNPROFILED_CHIPSCAN + UNPROFILED_TOADSTATS + UNPROFILED_SYNCSTATS + UNPROFILED_SEGREDUCE + UNPROFILED_DOSSIER + UNPROFILED_RELDIST + UNPROFILED_POSQ + UNPROFILED_TRACK + UNPROFILED_POSG + UNPROFILED_TDMAT + UNPROFILED_COVERAGE + UNPROFILED_POS3 + UNPROFILED_POSG3 + UNPROFILED_POSQ3
     for name in sorted(x for x in SOURCES + HEADERS if not x.startswith("..") and x not in skipped):
         h.update(name.encode())
         with open(os.path.join(CSRC, name), "rb") as f:

@@ -23,7 +23,6 @@ namespace {
 
 constexpr int kFoldThreads = 1024;
 constexpr int kKeepThreads = 256;
-constexpr int kCutThreads = 256;
 
 // float32 bits -> unsigned that orders like the float (negative values below positive ones)
 __device__ __forceinline__ unsigned orderable(float v) {
@@ -101,18 +100,6 @@ __global__ __launch_bounds__(kKeepThreads) void k_keep_block(ExtractState* __res
     if (blockIdx.x == 0 && threadIdx.x == 0) state->keep_format = format;
 }
 
-// sum over the workgroup in a fixed tree (every thread gets it)
-__device__ __forceinline__ double tree_sum(double v, double* scratch) {
-    __syncthreads();
-    scratch[threadIdx.x] = v;
-    __syncthreads();
-    for (int half = kCutThreads / 2; half > 0; half >>= 1) {
-        if (int(threadIdx.x) < half) scratch[threadIdx.x] += scratch[threadIdx.x + half];
-        __syncthreads();
-    }
-    return scratch[0];
-}
-
 __global__ __launch_bounds__(kCutThreads) void k_extract_template(const ExtractState* __restrict__ state,
                                                                   const void* __restrict__ keep, int block_len,
                                                                   int w, double* __restrict__ out) {
@@ -138,22 +125,7 @@ __global__ __launch_bounds__(kCutThreads) void k_extract_template(const ExtractS
         out[i] = m;
         acc += m;
     }
-    const double mean = tree_sum(acc, scratch) / double(w);
-    acc = 0;
-    for (int i = threadIdx.x; i < w; i += kCutThreads) {
-        const double d = out[i] - mean;
-        acc += d * d;
-    }
-    const double sd = sqrt(tree_sum(acc, scratch) / double(w));      // ddof = 0
-    const double scale = 2.0 / (mean + sd);
-    acc = 0;
-    for (int i = threadIdx.x; i < w; i += kCutThreads) {
-        const double v = out[i] * scale;
-        out[i] = v;
-        acc += v;
-    }
-    const double mean2 = tree_sum(acc, scratch) / double(w);         // (the reference recomputes it)
-    for (int i = threadIdx.x; i < w; i += kCutThreads) out[i] -= mean2;
+    scale_and_centre(out, w, acc, scratch);
 }
 
 }  // namespace
@@ -244,7 +216,8 @@ int extract_after_chunk(thr_handle* h, int b, const void* d_in, int format, size
                                   h->stream));
     HIP_TRY(thr::launch_keep_block(x->d_state, d_in, stride ? stride : blk_bytes, blk_bytes, format, x->fed,
                                    int(nb), x->d_keep, h->stream));
-    x->fed += nb;
+    x->fed += nb;       // (the fold is enqueued: the blocks count, whatever the averaging hook answers)
+    if (x->avg_armed) THR_TRY(average_after_chunk(x, b, d_in, format, stride ? stride : blk_bytes, nb));
     return THR_OK;
 }
 
@@ -290,6 +263,7 @@ int thr_extract_reset(thr_extract* x) try {
         return fail(THR_ERR_STATE, "thr_extract_reset: %d submitted batch(es) not collected yet", x->h->hp.async_open);
     HIP_TRY(hipSetDevice(x->h->device));
     HIP_TRY(hipMemsetAsync(x->d_state, 0, sizeof(thr::ExtractState), x->h->stream));
+    THR_TRY(thr::host::average_reset(x));
     x->fed = 0;
     return THR_OK;
 } catch (...) {
@@ -300,6 +274,9 @@ int thr_extract_feed(thr_extract* x, const void* samples, int format, const int6
                      const double* timestamps, size_t n_blocks, thr_record* out) try {
     int rc = thr::host::feed_enter(x, "thr_extract_feed", n_blocks);
     if (rc != THR_OK || n_blocks == 0) return rc;
+    if (x->avg_armed && format != THR_IN_U8)
+        return fail(THR_ERR_ARG, "thr_extract_feed: averaging is armed and its sums are exact integers of the u8 "
+                                 "quantiser: complex64 samples cannot be averaged (feed u8, or disarm)");
     std::vector<thr_record> scratch;
     if (!out) {
         scratch.resize(n_blocks);

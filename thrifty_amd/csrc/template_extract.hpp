@@ -34,12 +34,56 @@ hipError_t launch_keep_block(ExtractState* d_state, const void* d_in, unsigned l
 hipError_t launch_extract_template(const ExtractState* d_state, const void* d_keep, int block_len,
                                    int template_len, double* d_out, hipStream_t stream);
 
+#ifdef __HIPCC__
+constexpr int kCutThreads = 256;      // workgroup of k_extract_template and of template_average.hip's k_avg_finish
+
+// sum over the workgroup in a fixed tree (every thread gets it)
+__device__ __forceinline__ double tree_sum(double v, double* scratch) {
+    __syncthreads();
+    scratch[threadIdx.x] = v;
+    __syncthreads();
+    for (int half = kCutThreads / 2; half > 0; half >>= 1) {
+        if (int(threadIdx.x) < half) scratch[threadIdx.x] += scratch[threadIdx.x + half];
+        __syncthreads();
+    }
+    return scratch[0];
+}
+
+// The extraction's arithmetic on magnitudes: out[0 .. w) holds them, `acc` is this thread's sum of the ones it
+// wrote (i = threadIdx.x, + kCutThreads, ...).  Mean and population standard deviation by the fixed tree, times
+// scale = 2 / (mean + std), minus the recomputed mean.  Returns the scale.  Stated ONCE: k_extract_template and
+// k_avg_finish both call it.
+__device__ __forceinline__ double scale_and_centre(double* __restrict__ out, int w, double acc, double* scratch) {
+    const double mean = tree_sum(acc, scratch) / double(w);
+    acc = 0;
+    for (int i = threadIdx.x; i < w; i += kCutThreads) {
+        const double d = out[i] - mean;
+        acc += d * d;
+    }
+    const double sd = sqrt(tree_sum(acc, scratch) / double(w));      // ddof = 0
+    const double scale = 2.0 / (mean + sd);
+    acc = 0;
+    for (int i = threadIdx.x; i < w; i += kCutThreads) {
+        const double v = out[i] * scale;
+        out[i] = v;
+        acc += v;
+    }
+    const double mean2 = tree_sum(acc, scratch) / double(w);         // (the reference recomputes it)
+    for (int i = threadIdx.x; i < w; i += kCutThreads) out[i] -= mean2;
+    return scale;
+}
+#endif
+
 namespace host {
 // pipeline.hip calls this behind the kernels of every chunk, in front of the records' way back (the
 // chunk's done event then covers it: buffer b is not refilled under k_keep_block).  Does nothing
 // unless the calling thread is inside a thr_extract_feed* / thr_extract_submit* call on `h`.
 int extract_after_chunk(thr_handle* h, int b, const void* d_in, int format, size_t stride, size_t first,
                         size_t nb);
+// template_average.hip: extract_after_chunk calls it behind the fold and the keep when `x` has averaging armed
+// (block i of the batch at d_in + i * blk_stride, u8); thr_extract_reset calls average_reset
+int average_after_chunk(thr_extract* x, int b, const void* d_in, int format, size_t blk_stride, size_t nb);
+int average_reset(thr_extract* x);
 }  // namespace host
 }  // namespace thr
 
@@ -55,4 +99,11 @@ struct thr_extract {
     // the call in progress (extract_after_chunk reads them)
     const double* cur_ts = nullptr;                      // [n_blocks] of the call, or nullptr: cur_ts_all
     double cur_ts_all = 0;
+    // averaging (thr_extract_average, template_average.hip): nothing is allocated until it is armed
+    bool avg_armed = false;
+    thr_average_opts avg_opts{};
+    Dev<unsigned long long> d_avg_acc;                   // [max(1, n_classes)][2][template_len]: acc_e, acc_q
+    Dev<unsigned long long> d_avg_cnt;                   // thr::kAvgCounters: count[16], n_unclassified, out of range
+    Dev<signed char> d_avg_cls;                          // [max_batch]: the class of a record of the batch, or -1
+    Dev<double> d_avg_out;                               // [2][template_len]: template, sem
 };
